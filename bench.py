@@ -12,11 +12,16 @@ sharded across the N GPUs.
   frequencies in total, rank r sweeps its contiguous block
   ``shard_range(4096, r, N)`` (512 per rank at N = 8); one all-reduce (RCCL) of
   the loss/gradient partials per step.  ``--weak``: ``--freqs`` per rank.  With
-  N > 1 a strong run also times the weak workload (4096 per rank) and reports it
+  N > 1 a strong ``--full`` run also times the weak workload (4096 per rank) and reports it
   in the ``weak`` field;
 * ``value`` = all frequencies of all ranks / (max-over-ranks seconds per step);
 * each GPU runs ``lanes`` (default 2) solvers on their own HIP streams over
   contiguous halves of its frequencies, concurrently;
+* a plain run sets up, warms up, times the K steps and prints the headline (``value``, ``ms_per_step``, the
+  configuration, the loss of the last timed step); ``--dump-outputs DIR`` writes what that last step returned,
+  ``DIR/loss.npy`` and ``DIR/grad.npy`` (float64; the inputs are fixed, so two builds compare output for
+  output).  Everything below, and the ``weak`` figure above, is measured after the timed steps and only
+  with ``--full``;
 * ``roofline``: the dominant kernel class by device time -- at C3 with the MMD ordering
   ``k_offdiag_level`` (the L21 rows of the multifrontal factorisation, HBM-bound; within a few
   % of ``k_schur_sym_blk``): algorithmic bytes per launch (the solver's count: L21 stores +
@@ -37,7 +42,8 @@ sharded across the N GPUs.
 * ``parity``: the oracle partials of the CPU leg against a GPU sweep of the same
   frequencies (full-size C3 parity, paid for by the CPU leg).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--freqs F] [--weak] [--ny NY]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--freqs F] [--weak] [--ny NY] [--full]
+                       [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -227,8 +233,15 @@ def main():
     ap.add_argument("--freqs", type=int, default=4096, help="frequencies in total (strong) / per GPU (--weak)")
     ap.add_argument("--weak", action="store_true", help="--freqs per GPU instead of in total")
     ap.add_argument("--ny", type=int, default=25, help="mesh cells across the width (25 -> 19,353 DOF)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-strong-proxy", action="store_true", help="skip the 512-frequency per-rank sweep (C4 share)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beside the headline: device phase / "
+                         "kernel times and rooflines, backward errors, the weak figure (N > 1), the strong proxy, "
+                         "the CPU baseline and its parity")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (loss, gradient) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity")
+    ap.add_argument("--no-strong-proxy", action="store_true",
+                    help="with --full: skip the 512-frequency per-rank sweep (C4 share)")
     ap.add_argument("--chunk", type=int, default=None, help="frequencies per chunk (default: from free HBM)")
     args = ap.parse_args()
 
@@ -265,8 +278,8 @@ def main():
     freqs, ref, lo, hi, step = workload(n_total)
     eng = prob.engine()
     solver = eng.solver
-    # timed region: no device timing at all; per-phase HIP events in one extra untimed step, per-launch
-    # events (which cost host time that delays the second lane's launches) in another
+    # timed region: no device timing at all; with --full, per-phase HIP events in one extra untimed step,
+    # per-launch events (which cost host time that delays the second lane's launches) in another
     eng.set_timing(False)
     n_coll0 = pdist.N_COLLECTIVES
     last = {}
@@ -276,11 +289,78 @@ def main():
 
     elapsed = timed(step_acc, args.steps, args.warmup, world, device)
     collectives = (pdist.N_COLLECTIVES - n_coll0) / (args.steps + args.warmup)
+    val = last["val"]
+    ms_per_step = 1e3 * elapsed / args.steps
+    value = n_total / (elapsed / args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, val, last["grad"])
+
+    st = eng.stats
+    nv = hi - lo
+    chunk = solver.max_batch
+    out = {
+        "metric": "freq-solves/sec (forward+adjoint) @20k DOF",
+        "value": value,
+        "unit": "freq-solves/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "weak" if args.weak else "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (FE plate model built in-repo; reference FR = forward sweep at theta_true)",
+        "config": {"workload": ("C3" if world == 1 else "C4") + ": orthotropic CFRP-like plate, sh_i strip "
+                               f"100x20x2 mm + AP1030, {st['n']} DOF, {n_total} freqs in 40-600 Hz "
+                               f"({'per GPU' if args.weak else 'in total'}, {nv} on rank 0), forward+adjoint, "
+                               "loss MSE_LOG_AFC + gradient",
+                   "n_dofs": st["n"], "freqs_total": n_total, "freqs_rank0": nv, "chunk": chunk,
+                   "lanes": eng.n_lanes,
+                   "factorisation": "symmetric: A = L U, U = diag(U) L^T implicit, Dirichlet nodes decoupled"
+                                    if eng.symmetric else "general: A = L U",
+                   "nnz_lu": st["nnz_lu"], "factor_gflop_per_freq": st["factor_flops"] / 1e9,
+                   "parallelism": f"frequency shards x{world} + 1 all-reduce/step; {eng.n_lanes} concurrent "
+                                  "solver lanes (HIP streams) per GPU",
+                   "backend": backend, "collectives_per_step": collectives},
+        "loss": val,
+    }
+    if args.full:
+        out.update(device_report(eng, step, freqs, ref, lo, hi, n_total, device))
+    if args.full and world > 1 and not args.weak:
+        # the weak-scaling figure beside the strong one: 4096 frequencies per rank
+        n_w = args.freqs * world
+        _, _, lo_w, hi_w, step_w = workload(n_w)
+        el_w = timed(step_w, args.steps, args.warmup, world, device)
+        out["weak"] = {"value": n_w / (el_w / args.steps), "ms_per_step": 1e3 * el_w / args.steps,
+                       "freqs_per_gpu": args.freqs, "freqs_total": n_w}
+    if args.full and rank == 0 and world == 1 and not args.weak and args.freqs == 4096 and not args.no_strong_proxy:
+        out["strong_proxy"] = strong_proxy(value, args.ny)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"], sample = cpu_baseline(prob, freqs, ref, theta)
+        out["parity"] = gpu_parity(prob, sample, theta)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if backend is not None:
+        dist.destroy_process_group()
+
+
+def dump_outputs(directory, loss, grad):
+    """What one timed step hands its caller, from the last of them: the loss (``loss.npy``, shape (1,)) and
+    its gradient with respect to the material parameters (``grad.npy``), both float64."""
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "loss.npy"), np.array([loss], dtype=np.float64))
+    np.save(os.path.join(directory, "grad.npy"), grad.detach().cpu().numpy().astype(np.float64))
+
+
+def device_report(eng, step, freqs, ref, lo, hi, n_total, device):
+    """``--full``: per-phase and per-kernel-class device times, the backward errors and the kernel rooflines,
+    each from untimed sweeps of their own after the timed region."""
+    solver = eng.solver
     eng.set_timing(True, kernels=False)
     step()
     torch.cuda.synchronize()
     phase = np.asarray(eng.last_timings(), dtype=np.float64)
-    val = last["val"]
     # backward errors of the solves of this untimed step (same workload and theta as the timed steps;
     # checked on the device in every sweep)
     berr = eng.last_berr.cpu().numpy()
@@ -294,8 +374,6 @@ def main():
     step()
     torch.cuda.synchronize()
     kms, klaunch = eng.last_kernel_timings()
-    ms_per_step = 1e3 * elapsed / args.steps
-    value = n_total / (elapsed / args.steps)
 
     from plate_inverse_problem_amd import _native
     st = eng.stats
@@ -338,31 +416,7 @@ def main():
     trsv_gbs = trsv_bytes / (trsv_ms * 1e-3) / 1e9
     trsv_traffic = pmc_solve_traffic(eng.symmetric)
     conc_launch = kms / np.maximum(klaunch, 1)
-    out = {
-        "metric": "freq-solves/sec (forward+adjoint) @20k DOF",
-        "value": value,
-        "unit": "freq-solves/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "weak" if args.weak else "strong",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (FE plate model built in-repo; reference FR = forward sweep at theta_true)",
-        "config": {"workload": ("C3" if world == 1 else "C4") + ": orthotropic CFRP-like plate, sh_i strip "
-                               f"100x20x2 mm + AP1030, {st['n']} DOF, {n_total} freqs in 40-600 Hz "
-                               f"({'per GPU' if args.weak else 'in total'}, {nv} on rank 0), forward+adjoint, "
-                               "loss MSE_LOG_AFC + gradient",
-                   "n_dofs": st["n"], "freqs_total": n_total, "freqs_rank0": nv, "chunk": chunk,
-                   "lanes": eng.n_lanes,
-                   "factorisation": "symmetric: A = L U, U = diag(U) L^T implicit, Dirichlet nodes decoupled"
-                                    if eng.symmetric else "general: A = L U",
-                   "nnz_lu": st["nnz_lu"], "factor_gflop_per_freq": st["factor_flops"] / 1e9,
-                   "parallelism": f"frequency shards x{world} + 1 all-reduce/step; {eng.n_lanes} concurrent "
-                                  "solver lanes (HIP streams) per GPU",
-                   "backend": backend, "collectives_per_step": collectives},
+    return {
         "roofline": {"bound": "hbm", "kernel": kernels[dom], "achieved": gbs[dom], "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": gbs[dom] / HBM_PEAK_GBS, "traffic": traffic[dom],
                      "alg_bytes_per_launch": alg_launch[dom], "avg_launch_ms": ms_launch[dom],
@@ -391,25 +445,8 @@ def main():
                              "functional = its dot products + loss terms, adj_solves = the adjoint's bottom-up "
                              "combination + the paired top-down pass, contract = residual walks (checks and the "
                              "functional correction) + gradient contraction"},
-        "loss": val,
         "backward_error": check,
     }
-    if world > 1 and not args.weak:
-        # the weak-scaling figure beside the strong one: 4096 frequencies per rank
-        n_w = args.freqs * world
-        _, _, lo_w, hi_w, step_w = workload(n_w)
-        el_w = timed(step_w, args.steps, args.warmup, world, device)
-        out["weak"] = {"value": n_w / (el_w / args.steps), "ms_per_step": 1e3 * el_w / args.steps,
-                       "freqs_per_gpu": args.freqs, "freqs_total": n_w}
-    if rank == 0 and world == 1 and not args.weak and args.freqs == 4096 and not args.no_strong_proxy:
-        out["strong_proxy"] = strong_proxy(value, args.ny)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"], sample = cpu_baseline(prob, freqs, ref, theta)
-        out["parity"] = gpu_parity(prob, sample, theta)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if backend is not None:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -20,7 +20,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["--ny", "6", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--chunk", "256"]
+ARGS = ["--ny", "6", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--chunk", "256"]
 
 
 def _port():

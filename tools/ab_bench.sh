@@ -6,7 +6,7 @@ for i in $(seq 1 "${REPS:-3}"); do
   k=0
   for cfg in "$@"; do
     k=$((k + 1))
-    env $cfg timeout -k 10 200 python3 -u bench.py --no-cpu-baseline --no-strong-proxy --steps "${STEPS:-10}" --warmup 2 \
+    env $cfg timeout -k 10 200 python3 -u bench.py --full --no-cpu-baseline --no-strong-proxy --steps "${STEPS:-10}" --warmup 2 \
       > "$O/b${k}_$i.json" 2> "$O/b${k}_$i.err" || { tail -5 "$O/b${k}_$i.err"; exit 1; }
     echo "$cfg | $(python3 -c "import json;d=json.load(open('$O/b${k}_$i.json'));print(round(d['value']), round(d['ms_per_step'],2), [round(x,2) for x in d['factor_roofline']['ms']])")"
   done
