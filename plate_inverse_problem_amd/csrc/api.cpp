@@ -805,6 +805,7 @@ int pfr_solver_create(const pfr_symbolic* sym, const int32_t* colptr, const int3
   // the solve update-part split target, the A11 LU in LDS, the functional from the bottom-up passes, the
   // contraction in the forward walk, the cotangent's solve-error scale, the one-wave top-down pass, the
   // Schur block-kernel threshold and the pipelined L21 prefix
+  // (tests/synthetic.py restates the defaults of us2_small, fac_g_ns, us2_nar, fac_lds_wg and blk_min)
   s->solve_wmax = knob("PFR_SOLVE_WMAX", 8, 1, 8);
   s->fac_wmax = knob("PFR_FAC_WMAX", 16, 1, 16);
   s->fac_g_wg = knob("PFR_FAC_G_WG", 0, 0, 1 << 20);

@@ -2051,6 +2051,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(WPE))) void
 // frequency).
 constexpr int RL_Q = 16, RL_WMAX = 8, RL_RING = 16;   // ring entries per lane: PF = RL_RING / RPL pivots ahead
 // rows per lane slot for a level whose largest pivot block is maxns (1, 2 or 4: maxns <= 128), and the waves
+// (RL_WMAX and rl_rpl are restated in tests/synthetic.py dispatch_classes)
 inline int rl_rpl(int maxns) { return maxns <= 4 * RL_WMAX ? 1 : maxns <= 8 * RL_WMAX ? 2 : 4; }
 inline int rl_waves(int maxns) { return std::min(RL_WMAX, (maxns + 4 * rl_rpl(maxns) - 1) / (4 * rl_rpl(maxns))); }
 template <bool UP, int NV, int RPL, int PF>

@@ -51,6 +51,8 @@ constexpr int CEG_EW = 8;                     // entries per wave of k_contract_
 constexpr int64_t LDS_BYTES = 160 * 1024;
 
 // ---- launch geometry shared by the launchers and the checks
+// (tests/synthetic.py restates FAC_G, LS_NAR_DYN_MAX, waves_for, solve_waves, F0_NS / F0_RM and the knob defaults of
+// api.cpp to prove which launch class each synthetic shape reaches: change them there too)
 inline int residual_parts(int n) { return (int)std::min<int64_t>((n + 3) / 4, 256); }   // k_residual grid.x
 inline int contract_eg_parts(int nent) { return ((nent + CEG_EW - 1) / CEG_EW + 3) / 4; }   // k_contract_eg grid
 // dynamic LDS of k_factor_sym_lds for a level whose largest pivot block is maxns (triangle + 8 W columns)

@@ -176,6 +176,9 @@ def test_c2_forward_sweep_matches_truth():
     {"PFR_US2_TINY": "0"},
     {"PFR_US2_NAR": "0"},               # the narrow-level solve forms never (right-looking, global memory)
     {"PFR_US2_NAR": "1000000000"},      # ... on every level whose pivot block fits the LDS
+    {"PFR_US2_RL": "0"},                # the narrow levels' paired top-down pivot blocks left-looking (k_usolve2_updc)
+    {"PFR_LS_RL": "0"},                 # the bottom-up chain's pivot blocks through the LDS-staged narrow form
+    {"PFR_US2_RL": "0", "PFR_LS_RL": "0"},
 ])
 def test_kernel_variants_match_oracle(env, monkeypatch):
     from oracle.plate_oracle import loss_and_grad

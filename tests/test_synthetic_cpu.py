@@ -1,0 +1,226 @@
+"""CPU: the synthetic shapes of tests/synthetic.py land in the launch classes tests/test_gpu_synthetic.py runs
+them for, and the fp64 multifrontal model (tests/mf_model.py) solves them to rounding level.
+
+The dispatch assertions read the exported fronts (FRONTS, LEVEL_PTR, LEVEL_FRONTS) and restate the launchers'
+thresholds (csrc/kernels.hip launch_usolve2 / launch_lsolve_multi, csrc/api.cpp sym_top_down_pair / factor_level,
+csrc/plan.hpp): if the analysis changes, the GPU tests cannot silently stop covering a branch.
+
+Which test reaches which dispatch point (ids of tests/test_gpu_synthetic.py; "narrow" = the launch has fewer than
+us2_nar = 256 workgroups, which every level of every shape at 64-frequency chunks has):
+  k_usolve2_rl<1|2|4>, k_lsolve_rl_z<*,1|2|4>   rows per lane slot 1: test_shape[A-*] level 0, T; 2: A root, B
+                                          level 0; 4: B root, D / F level 0, T root (default knobs: narrow,
+                                          right-looking)
+  maxns > 128: right-looking off          test_shape[C-*] (root 129), D (161), E (256): k_usolve2_updc +
+                                          k_usolve2_level(upd_done = 1); the same on B, C, F by test_knob[*-US2_RL=0]
+  ls_nar_fits 112 / 113                   test_shape[F-*] and test_knob[F-LS_RL=0] (level 0: 112 fits, root 113 does
+                                          not); C, D, E roots do not fit
+  k_usolve2_tiny<4|8>                     test_knob[A4-US2_NAR=0,SOLVE_SPLIT=0] (level maxns 4), [A8-...] (8): the
+                                          tiny form is chosen per level, for wide unsplit launches only
+  k_usolve2_level<true,8,2,3> (maxf <= us2_small = 110), not right-looking
+                                          test_knob[B-US2_RL=0], [B-US2_NAR=0], [A4-/A8-...,US2_TINY=0],
+                                          test_solve_waves[A|B|T|F0-...,US2_RL=0,LS_RL=0] and [...,US2_NAR=0];
+                                          <true,4,8,2> (maxf > 110): test_shape[C|D|E] roots, test_knob[C-US2_RL=0],
+                                          [C-US2_NAR=0], test_solve_waves[C|D-...,US2_RL=0,LS_RL=0], [...,US2_NAR=0]
+  k_factor_sym_lds, auto mode             test_shape[A-*] (both levels), B / C / E / T level 0; PFR_FAC_LDS=0 / 1:
+                                          test_knob[A-FAC_LDS=*], [B-FAC_LDS=*]
+  maxns > fac_g_ns (64)                   test_shape[B-*] (root 65), C, D, E, F
+  waves per solve workgroup               every launch of the cases above gets 8 waves: solve_waves raises the
+                                          level's size-based count while the launch has fewer than 4,096
+                                          workgroups.  The size-based counts run under PFR_SOLVE_WMAX=1:
+                                          test_solve_waves[F0-*] 1, [A-*] 3 / 2, [T-*] 4 / 3, [B-*] 5 / 3, [C-*] 8 / 6,
+                                          [D-*] 8 / 7 waves, with the right-looking forms on, off, and on wide
+                                          launches.  The general-mode panel factor takes min(size-based, fill):
+                                          test_general_solve[A|C|E|T-*] 3 / 2, 8 / 6, 8 / 8 / 2, 4 / 3 waves
+  update blocks >= blk_min, ragged        test_shape[A-*] (33 rows = 2 blocks + 1), B (65), E (300, 44),
+                                          test_knob[A|E-SCHUR_BLK_MIN=0|4]
+  max_ns chain                            test_shape[E-*]: (256, 300) -> (44, 44)
+  k_front0 (fused bottom level)           test_shape[F0-*], against test_knob[F0-FRONT0=0]; on A and T (leaves beyond 4
+                                          pivots / 10 update rows) PFR_FRONT0 changes nothing
+  non-contiguous extend-add, Dirichlet    test_shape[T-*]
+"""
+import numpy as np
+import pytest
+
+import synthetic as sy
+from oracle.plate_oracle import loss_term_derivative, loss_terms
+
+
+def _fronts(shape):
+    """[(level, sorted (ns, f) of the non-Dirichlet fronts)], the Dirichlet 1 x 1 fronts counted apart."""
+    dc = sy.dispatch_classes(sy.symbolic(shape))
+    out, n11 = [], 0
+    for d in dc:
+        pairs = sorted(zip(d["ns"], d["f"]))
+        n11 += sum(1 for p in pairs if p == (1, 1))
+        out.append([p for p in pairs if p != (1, 1)])
+    return dc, out, n11
+
+
+BORDER_SHAPES = {"A": ((3, 4, 5, 8, 9, 16, 17), 33), "B": ((4, 8, 31, 32, 33), 65), "C": ((2, 7, 40), 129),
+                 "D": ((5, 70), 161), "A4": ((2, 3, 4, 4), 33), "A8": ((5, 7, 8), 33), "F": ((6, 112), 113)}
+def _solve_w(shape, **kw):
+    return [d["solve_w"] for d in sy.dispatch_classes(sy.symbolic(shape), **kw)]
+
+
+@pytest.mark.parametrize("shape", sorted(BORDER_SHAPES))
+def test_clique_border_fronts_are_exact(shape):
+    """(ns, f) = (m_i, m_i + s) on level 0 and (s, s) as root, in symmetric mode (Dirichlet nodes as 1 x 1 fronts)
+    and in general mode (the pattern without Dirichlet nodes)."""
+    ms, s = BORDER_SHAPES[shape]
+    dc, fr, n11 = _fronts(shape)
+    assert len(dc) == 2 and n11 == 2
+    assert fr[0] == sorted((m, m + s) for m in ms) and fr[1] == [(s, s)]
+    st = sy.symbolic(shape).stats()
+    assert st["symmetric"] == 1 and st["n_dirichlet"] == 2 and st["n_coupling"] > 0
+    if shape in sy.GENERAL_SHAPES:
+        g = sy.dispatch_classes(sy.symbolic(shape, symmetric=False, general=True))
+        assert [sorted(zip(d["ns"], d["f"])) for d in g] == [sorted((m, m + s) for m in ms), [(s, s)]]
+
+
+def test_shape_E_is_the_max_ns_chain():
+    dc, fr, n11 = _fronts("E")
+    assert fr == [[(6, 306), (20, 320)], [(256, 300)], [(44, 44)]] and n11 == 2
+    assert dc[1]["upd"] == [44] and 300 in dc[0]["upd"]          # 44-row and 300-row update blocks
+    g = sy.dispatch_classes(sy.symbolic("E", symmetric=False, general=True))
+    assert [sorted(zip(d["ns"], d["f"])) for d in g] == fr
+
+
+def test_shape_T_scatters_update_blocks():
+    """4+ levels, Dirichlet decoupling, and fronts whose update rows land at non-contiguous parent positions (the
+    extend-add index path the fully coupled family cannot exercise)."""
+    sym = sy.symbolic("T")
+    st = sym.stats()
+    assert st["n_levels"] >= 4 and st["n_dirichlet"] == 3 and st["n_coupling"] > 0
+    fr, relpos = sym.export("FRONTS"), sym.export("RELPOS")
+    scattered = 0
+    for ns, f, row0, col0, parent, *_ in fr:
+        if parent < 0 or f - ns < 2:
+            continue
+        rp = relpos[row0 + ns:row0 + f]
+        assert np.all(rp >= 0) and np.all(rp < fr[parent, 1]) and np.unique(rp).size == rp.size
+        scattered += bool(np.any(np.diff(rp) != 1))
+    assert scattered >= 5
+    # without `last` (the support-outside-the-root case) the tree still has several levels
+    assert sy.symbolic("T", last=False).stats()["n_levels"] >= 3
+    # general mode on the pattern without Dirichlet nodes
+    assert sy.symbolic("T", symmetric=False, general=True).stats()["n_levels"] >= 4
+
+
+def test_dispatch_classes():
+    """The pins of every shape (module docstring): each GPU case runs the branch it is listed for."""
+    A, B, C, D, E, F, T = (sy.dispatch_classes(sy.symbolic(s)) for s in "ABCDEFT")
+    A4, A8 = (sy.dispatch_classes(sy.symbolic(s)) for s in ("A4", "A8"))
+    # A: 1 row per lane slot below, 2 at the root; LDS A11 in auto mode; 33-row ragged update blocks; 3 waves
+    assert (A[0]["maxns"], A[0]["rpl"], A[1]["maxns"], A[1]["rpl"]) == (17, 1, 33, 2)
+    assert A[0]["fac_lds_auto"] and A[1]["fac_lds_auto"] and not A[1]["fac_big"]
+    assert set(A[0]["upd"]) == {33, 0} and 33 % 16 == 1 and A[0]["blk"] == [33] * 7
+    assert (A[0]["maxf"], A[0]["level_w"], A[1]["level_w"]) == (50, 3, 2) and A[0]["us2_small"]
+    assert {16, 17} <= set(A[0]["ns"]) and {4, 5, 8, 9} <= set(A[0]["ns"])
+    # A4 / A8: levels of pivot blocks <= 4 / <= 8
+    assert (A4[0]["maxns"], A4[0]["tiny"], A8[0]["maxns"], A8[0]["tiny"]) == (4, 4, 8, 8)
+    assert A4[1]["tiny"] == 0 and A8[1]["tiny"] == 0
+    # B: 31 / 32 / 33 pivots in one launch of 2 rows per slot; root 65: 4 rows per slot, > fac_g_ns
+    assert {31, 32, 33} <= set(B[0]["ns"]) and (B[0]["rpl"], B[1]["maxns"], B[1]["rpl"]) == (2, 65, 4)
+    assert B[1]["fac_big"] and not B[0]["fac_big"] and B[0]["rl"] and B[1]["rl"] and set(B[0]["upd"]) == {65, 0}
+    assert B[0]["us2_small"] and (B[0]["level_w"], B[1]["level_w"]) == (5, 3)
+    # C: root 129 pivots: right-looking off; fronts of 131 .. 169 rows: large-front top-down, 6 and 8 waves
+    assert C[1]["maxns"] == 129 and not C[1]["rl"] and C[0]["rl"] and not C[1]["ls_nar_fits"]
+    assert sorted(C[0]["f"])[-3:] == [131, 136, 169] and not C[0]["us2_small"] and not C[1]["us2_small"]
+    assert (C[0]["level_w"], C[1]["level_w"]) == (8, 6)
+    # D: 161 pivots; a leaf of 70 pivots and 231 rows
+    assert D[1]["maxns"] == 161 and not D[1]["ls_nar_fits"] and not D[1]["rl"]
+    assert (70, 231) in zip(D[0]["ns"], D[0]["f"]) and D[0]["fac_big"] and D[0]["rpl"] == 4 and D[0]["level_w"] == 8
+    # E: the chain; 320-row fronts
+    assert [d["maxns"] for d in E] == [20, 256, 44] and E[0]["maxf"] == 320 and not E[1]["rl"]
+    assert [d["level_w"] for d in E] == [8, 8, 2] and E[1]["blk"] == [44] and 300 in E[0]["blk"]
+    # F: ls_nar_fits on both sides of its threshold
+    assert (F[0]["maxns"], F[0]["ls_nar_fits"], F[1]["maxns"], F[1]["ls_nar_fits"]) == (112, True, 113, False)
+    assert F[0]["rl"] and F[1]["rl"] and F[0]["rpl"] == 4
+    # T: 1 and 4 rows per slot over its levels (2 is on A's root and B's level 0), small fronts
+    assert {d["rpl"] for d in T} == {1, 4} and all(d["us2_small"] and d["rl"] for d in T)
+    assert T[-1]["maxns"] == 65 and max(d["level_w"] for d in T) == 4
+    # LDS A11 in auto mode: only where the pivot blocks are 16 .. 64 (few workgroups everywhere here)
+    assert [d["fac_lds_auto"] for d in B] == [True, False] and [d["fac_lds_auto"] for d in A4] == [False, True]
+    # the fused bottom level: F0 only
+    F0 = sy.dispatch_classes(sy.symbolic("F0"))
+    assert F0[0]["fused0"] and max(F0[0]["ns"]) == 4 and {1, 2} <= set(F0[0]["ns"]) and max(F0[0]["upd"]) == 10
+    assert not any(d[0]["fused0"] for d in (A, A4, A8, B, C, D, E, F, T))
+
+
+def test_solve_launch_waves():
+    """The waves a solve launch really gets (csrc/plan.hpp solve_waves): 8 on every level of every shape under the
+    default knobs, since no launch here has 4,096 workgroups; the levels' size-based counts 1 .. 8 only under
+    PFR_SOLVE_WMAX=1 (test_gpu_synthetic.py::test_solve_waves).  Every level is narrow at 64-frequency chunks; the
+    2,048-lane chunk makes shape A's level 0 wide."""
+    for shape in sy.SHAPES:
+        dc = sy.dispatch_classes(sy.symbolic(shape))
+        assert all(d["solve_w"] == 8 and d["narrow"] for d in dc), shape
+        assert _solve_w(shape, solve_wmax=1) == [d["level_w"] for d in dc]
+    want = {"F0": [1, 1], "A": [3, 2], "T": [4, 4, 4, 4, 3], "B": [5, 3], "C": [8, 6], "D": [8, 7]}
+    for shape, w in want.items():
+        assert _solve_w(shape, solve_wmax=1) == w, shape
+    assert set(sum(want.values(), [])) == {1, 2, 3, 4, 5, 6, 7, 8}
+    wide = sy.dispatch_classes(sy.symbolic("A"), Fc=2048)
+    assert [d["narrow"] for d in wide] == [False, True] and [d["solve_w"] for d in wide] == [8, 8]
+    # general mode: the panel factor runs at the size-based counts
+    panel = {s: [d["panel_w"] for d in sy.dispatch_classes(sy.symbolic(s, symmetric=False, general=True))]
+             for s in sy.GENERAL_SHAPES}
+    assert panel == {"A": [3, 2], "C": [8, 6], "E": [8, 8, 2], "T": [4, 4, 4, 4, 3]}
+
+
+@pytest.mark.parametrize("shape", sorted(sy.SHAPES))
+def test_values_qualify(shape):
+    """The symmetric analysis' condition holds on the values; K is exact; Dirichlet rows hold only their diagonal."""
+    from plate_inverse_problem_amd.Problem import decoupled_symmetric
+    pat, op = sy.case(shape)
+    assert decoupled_symmetric(pat.rows, pat.cols, np.vstack([op.S, op.M[None], op.K.real[None], op.K.imag[None]]),
+                               pat.n)
+    for d in pat.dirichlet:
+        assert np.array_equal(pat.cols[pat.rows == d], [d]) and np.sum(pat.cols == d) > 1
+    # exact: every partial sum of coef_k S_k is a multiple of 2^-18 far below 2^53
+    K2 = sum(op.coef[k] * op.S[k] for k in reversed(range(op.n_stiff)))
+    assert np.array_equal(K2, op.K)
+    diag = pat.rows == pat.cols
+    nd = ~np.isin(pat.rows, pat.dirichlet)
+    rowsum = np.zeros(pat.n)
+    np.add.at(rowsum, pat.rows[~diag], np.abs(op.K[~diag]))
+    want = 1.3 * rowsum[pat.rows[diag & nd]] * (1 + 0.02j)
+    assert np.allclose(op.K[diag & nd], want, rtol=2e-3)
+    assert np.all(op.M >= 0) and not np.isin(op.sup, pat.dirichlet).any()
+
+
+def test_extended_loss_formulas_match_the_oracle():
+    rng = np.random.default_rng(5)
+    fr = sy.LD(0.5) + rng.random(7).astype(sy.LD)
+    ref = (0.4 + rng.random(7)) * np.exp(0.1j)
+    for lt in ("MSE", "RMSE", "MSE_AFC", "MSE_LOG_AFC"):
+        for i in range(7):
+            t, d = sy.loss_ld(fr[i], ref[i], lt)
+            assert float(t) == pytest.approx(float(loss_terms(fr[i], ref[i], lt)), rel=1e-12)
+            assert float(d) == pytest.approx(float(loss_term_derivative(fr[i], ref[i], lt)), rel=1e-12)
+
+
+# e_model / e_dense of tests/test_gpu_synthetic.py's table; the sanity limit is not a test tolerance of the kernels:
+# the fp64 model and the dense solve must themselves sit at rounding level on these systems (cond <= 1e4)
+MODEL_SANE = 1e-10
+
+
+@pytest.mark.parametrize("shape", sorted(sy.SHAPES))
+def test_model_matches_refined_dense(shape):
+    pat, op = sy.case(shape)
+    freqs = sy.FREQS[sy.three(sy.FREQS)]
+    e_model, e_dense = sy.model_errors(op, sy.symbolic(shape), freqs)
+    print(f"{shape} n={pat.n} e_model " + " ".join(f"{k}={v:.1e}" for k, v in e_model.items()))
+    print(f"{shape} n={pat.n} e_dense " + " ".join(f"{k}={v:.1e}" for k, v in e_dense.items()))
+    for k in e_model:
+        assert e_model[k] < MODEL_SANE and e_dense[k] < MODEL_SANE, (k, e_model[k], e_dense[k])
+
+
+@pytest.mark.parametrize("shape", sorted(sy.GENERAL_SHAPES))
+def test_general_model_matches_refined_dense(shape):
+    """General mode (explicit unsymmetric values, no Dirichlet nodes): MFModel.solve of A and A^T."""
+    gc = sy.general_case(shape)
+    for tr in (False, True):
+        _, e_model, e_dense = gc.bound(tr, ((0, 0), (32, 32), (64, 64)))
+        print(f"general {shape} transpose={tr} e_model {e_model:.1e} e_dense {e_dense:.1e}")
+        assert e_model < MODEL_SANE and e_dense < MODEL_SANE
