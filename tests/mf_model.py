@@ -1,10 +1,21 @@
 """Numpy model of the HIP multifrontal algorithm, driven by the C-ABI's exported
 symbolic maps (test infrastructure: validates the host symbolic analysis on
-CPU, without a GPU).  Mirrors csrc/kernels.hip phase by phase, for ONE matrix.
+CPU, without a GPU).  Mirrors csrc/kernels.hip phase by phase, for ONE matrix --
+or, with a trailing batch axis on ``data`` (nnz, B) and ``b`` (n, B), for B
+matrices at once (the same operations per matrix, vectorised over the batch).
 """
 from __future__ import annotations
 
 import numpy as np
+
+
+def _mv(M, v):
+    """M v per batch item: M (r, c) or (r, c, B), v (c,) or (c, B)."""
+    return M @ v if M.ndim == 2 else np.einsum("ijb,jb->ib", M, v)
+
+
+def _diag(A):
+    return np.diag(A) if A.ndim == 2 else np.einsum("iib->ib", A)
 
 
 class MFModel:
@@ -39,7 +50,7 @@ class MFModel:
         for lvl in self.levels():
             for t in lvl:
                 ns, f, row0 = int(self.fr[t, 0]), int(self.fr[t, 1]), int(self.fr[t, 2])
-                A = np.zeros((f, f), dtype=complex)
+                A = np.zeros((f, f) + data.shape[1:], dtype=complex)
                 for a in range(f):
                     r = row0 + a
                     for e in range(self.asm_ptr[r], self.asm_ptr[r + 1]):
@@ -49,17 +60,17 @@ class MFModel:
                         c = self.row_front[src]
                         cns, cf, crow0 = int(self.fr[c, 0]), int(self.fr[c, 1]), int(self.fr[c, 2])
                         lr = src - crow0
-                        for b in range(cns, cf):
-                            A[a, self.relpos[crow0 + b]] += F[c][lr, b]
+                        # the child's update row lr, scattered: its parent positions are distinct
+                        A[a, self.relpos[crow0 + cns:crow0 + cf]] += F[c][lr, cns:cf]
                 for k in range(ns):
                     A[k + 1:, k] /= A[k, k]
-                    A[k + 1:, k + 1:] -= np.outer(A[k + 1:, k], A[k, k + 1:])
+                    A[k + 1:, k + 1:] -= A[k + 1:, k][:, None] * A[k, k + 1:][None, :]
                 F[t] = A
         return F
 
     def _gather(self, F, WV, t, rhs_perm):
         ns, f, row0 = int(self.fr[t, 0]), int(self.fr[t, 1]), int(self.fr[t, 2])
-        w = np.zeros(f, dtype=complex)
+        w = np.zeros((f,) + rhs_perm.shape[1:], dtype=complex)
         for a in range(f):
             r = row0 + a
             if a < ns:
@@ -71,9 +82,9 @@ class MFModel:
     def solve(self, F, b, transpose=False):
         """x = A^{-1} b (or A^{-T} b, non-conjugate), b in caller numbering."""
         bp = b[self.perm]
-        WV = np.zeros(int(self.fr[:, 1].sum()), dtype=complex)
-        Y = np.zeros(self.n, dtype=complex)
-        X = np.zeros(self.n, dtype=complex)
+        WV = np.zeros((int(self.fr[:, 1].sum()),) + bp.shape[1:], dtype=complex)
+        Y = np.zeros((self.n,) + bp.shape[1:], dtype=complex)
+        X = np.zeros((self.n,) + bp.shape[1:], dtype=complex)
         for lvl in self.levels():
             for t in lvl:
                 ns, f, row0, col0 = (int(v) for v in self.fr[t, :4])
@@ -94,16 +105,16 @@ class MFModel:
                 A = F[t]
                 xr = X[self.idx[row0 + ns:row0 + f]]
                 if not transpose:         # U
-                    v = Y[col0:col0 + ns] - A[:ns, ns:] @ xr
+                    v = Y[col0:col0 + ns] - _mv(A[:ns, ns:], xr)
                     for k in range(ns - 1, -1, -1):
                         v[k] /= A[k, k]
                         v[:k] -= A[:k, k] * v[k]
                 else:                     # L^T (unit upper)
-                    v = Y[col0:col0 + ns] - A[ns:, :ns].T @ xr
+                    v = Y[col0:col0 + ns] - _mv(np.swapaxes(A[ns:, :ns], 0, 1), xr)
                     for k in range(ns - 1, -1, -1):
                         v[:k] -= A[k, :k] * v[k]
                 X[col0:col0 + ns] = v
-        out = np.zeros(self.n, dtype=complex)
+        out = np.zeros(X.shape, dtype=complex)
         out[self.perm] = X
         return out
 
@@ -121,9 +132,9 @@ class MFModel:
             for p_i, ds, nz in cpl:
                 p_d, nz_dd = dirs[ds]
                 bp[p_i] -= data[nz] * bp[p_d] / data[nz_dd]
-        WV = np.zeros(int(self.fr[:, 1].sum()), dtype=complex)
-        Y = np.zeros(self.n, dtype=complex)
-        X = np.zeros(self.n, dtype=complex)
+        WV = np.zeros((int(self.fr[:, 1].sum()),) + bp.shape[1:], dtype=complex)
+        Y = np.zeros((self.n,) + bp.shape[1:], dtype=complex)
+        X = np.zeros((self.n,) + bp.shape[1:], dtype=complex)
         for lvl in self.levels():
             for t in lvl:
                 ns, f, row0, col0 = (int(v) for v in self.fr[t, :4])
@@ -138,8 +149,8 @@ class MFModel:
                 ns, f, row0, col0 = (int(v) for v in self.fr[t, :4])
                 A = F[t]
                 xr = X[self.idx[row0 + ns:row0 + f]]
-                U12 = np.diag(A)[:ns, None] * A[ns:, :ns].T
-                v = Y[col0:col0 + ns] - U12 @ xr
+                U12 = _diag(A)[:ns, None] * np.swapaxes(A[ns:, :ns], 0, 1)
+                v = Y[col0:col0 + ns] - _mv(U12, xr)
                 for k in range(ns - 1, -1, -1):
                     v[k] /= A[k, k]
                     v[:k] -= A[:k, k] * v[k]
@@ -148,6 +159,6 @@ class MFModel:
             for p_i, ds, nz in cpl:
                 p_d, nz_dd = dirs[ds]
                 X[p_d] -= data[nz] * X[p_i] / data[nz_dd]
-        out = np.zeros(self.n, dtype=complex)
+        out = np.zeros(X.shape, dtype=complex)
         out[self.perm] = X
         return out

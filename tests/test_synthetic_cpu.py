@@ -224,3 +224,124 @@ def test_general_model_matches_refined_dense(shape):
         _, e_model, e_dense = gc.bound(tr, ((0, 0), (32, 32), (64, 64)))
         print(f"general {shape} transpose={tr} e_model {e_model:.1e} e_dense {e_dense:.1e}")
         assert e_model < MODEL_SANE and e_dense < MODEL_SANE
+
+
+# ----------------------------------------------------------------------------- second order: the Hessian reference
+def _gradient_at(op, refc, sel, coef_ld, loss_type, scale):
+    """The reference gradient partials w (n_stiff,) over the frequencies ``sel`` of the operator with the
+    coefficients ``coef_ld`` (extended precision, not rounded: K = coef S and beta = coef e formed in extended
+    precision), the reference response of ``refc`` kept."""
+    S, pat = op._ld("S"), op.pat
+    K = pat.dense(coef_ld @ S)
+    beta = coef_ld @ op.e.astype(sy.LD)
+    w = 0
+    for q in sel:
+        om2 = sy.LD(op.om2(refc.freqs[q]))
+        A = K - om2 * op._ld("M")
+        b = op.rhs.astype(sy.LD) * (beta - om2 * sy.LD(op.mass_sum))
+        x = sy.refined_solve(A, b)[0]
+        fr, _ = sy.fr_of(op, x)
+        lam = sy.refined_solve(A, sy.adjoint_seed(op, x, sy.loss_ld(fr, refc.ref[q], loss_type)[1]), trans=True)[0]
+        w = w + sy.LD(scale) * sy.partials(op, lam, x)
+    return w
+
+
+HESSIAN_FD = [("A", 12, "MSE_LOG_AFC"), ("T", 12, "MSE"), ("A", 12, "RMSE"), ("F0", 12, "MSE_AFC"),
+              ("A", 18, "MSE_LOG_AFC")]
+
+
+@pytest.mark.parametrize("shape,n_stiff,loss_type", HESSIAN_FD, ids=[f"{s}-{k}-{l}" for s, k, l in HESSIAN_FD])
+def test_hessian_reference_matches_finite_differences(shape, n_stiff, loss_type):
+    """hessian_reference against central differences (t = 1e-7) of the reference gradient along c(t) = coef + t
+    dcoef_i, all in extended precision: H_ij = Re sum_k h_ik dcoef_jk against d g_j / d t_i with
+    g_j = Re sum_k w_k dcoef_jk.  4 frequencies, 3 complex directions.  The bound 1e-9 max|H| covers the O(t^2)
+    truncation; measured <= 8.6e-12 (and asymmetry <= 1e-17) when the formulas were derived."""
+    _, op = sy.case(shape, n_stiff=n_stiff)
+    freqs = np.linspace(40.0, 600.0, 4)
+    refc = sy.reference(op, freqs)
+    sel, scale, t = range(4), 0.25, sy.LD(1e-7)
+    d = sy.direction(3, n_stiff).astype(sy.CLD)
+    h = sy.hessian_reference(refc, loss_type, d, scale)
+    H = (h @ d.T).real
+    coef = op.coef.astype(sy.CLD)
+    Hfd = np.array([[((_gradient_at(op, refc, sel, coef + t * d[i], loss_type, scale)
+                       - _gradient_at(op, refc, sel, coef - t * d[i], loss_type, scale)) @ d[j]).real / (2 * t)
+                     for j in range(3)] for i in range(3)])
+    top = np.abs(H).max()
+    err, asym = float(np.abs(H - Hfd).max() / top), float(np.abs(H - H.T).max() / top)
+    print(f"{shape} n_stiff={n_stiff} {loss_type}: |H - H_fd| / max|H| = {err:.1e}, asymmetry {asym:.1e}")
+    assert err <= 1e-9 and asym <= 1e-15
+
+
+def test_hessian_model_sits_at_rounding_level():
+    """hessian_model_errors (the fp64 sequence through the model and the dense LU): as MODEL_SANE for the first
+    order, on both analyses."""
+    for shape, symmetric in (("A", True), ("A", False), ("T", True)):
+        _, op = sy.case(shape)
+        freqs = sy.FREQS[sy.three(sy.FREQS)]
+        e_model, e_dense = sy.hessian_model_errors(op, sy.symbolic(shape, symmetric=symmetric), freqs, "MSE_LOG_AFC",
+                                                   sy.direction(2, 12), symmetric=symmetric)
+        print(f"{shape} symmetric={symmetric} h: e_model {e_model['h']:.1e} e_dense {e_dense['h']:.1e}")
+        assert e_model["h"] < MODEL_SANE and e_dense["h"] < MODEL_SANE
+
+
+# ----------------------------------------------------------------------------- the weak-pivot variant
+WEAK_SHAPES = tuple(sy.WEAK_BITS)      # tests/test_gpu_synthetic_modes.py runs the weak cases on these
+
+
+@pytest.mark.parametrize("symmetric", [True, False], ids=["symmetric", "general"])
+@pytest.mark.parametrize("shape", WEAK_SHAPES)
+def test_weak_variant_conditions(shape, symmetric):
+    """The conditions the weak-pivot GPU cases rest on (sy.WEAK_BITS per shape): the matrices keep cond <= COND_MAX
+    at every frequency of the sweep (sy.reference asserts it); at each of the first, middle and last frequency of the
+    GPU cases' sweep the unrefined model's errors of x and fr are at least 10 x the refined bounds (so a refinement or
+    correction that does nothing, or the wrong thing, misses them), and its backward errors are above BERR_MAX (so the
+    flags must be set).  Measured gaps (x / fr, the smaller of the two analyses): A 103 / 131, E 60 / 26, F0 285 / 69
+    at 2^-24; C 815 / 202, T 1856 / 232 at 2^-28; the condition bounds are those of the unweakened operators."""
+    _, op = sy.case(shape, weak_bits=sy.WEAK_BITS[shape])
+    sym = sy.symbolic(shape, symmetric=symmetric)
+    freqs = sy.weak_freqs(shape)
+    refc = sy.reference(op, sy.FREQS)               # check_cond over all 130
+    conds = sy.check_cond(refc.mats, shape, refc.lus)
+    for q in sy.three(freqs):
+        f = freqs[[q]]
+        raw, _ = sy.model_errors(op, sym, f, symmetric=symmetric)
+        refined = sy.bounds(*sy.model_errors(op, sym, f, symmetric=symmetric, refine=True))
+        corrected = sy.bounds(*sy.model_errors(op, sym, f, symmetric=symmetric, correct=True))
+        berr = sy.model_berr(op, sym, f, symmetric=symmetric)[0]
+        print(f"{shape} symmetric={symmetric} f={f[0]:.0f} cond<={conds.max():.0f} unrefined x {raw['x']:.1e} "
+              f"fr {raw['fr']:.1e} berr {berr[0]:.1e}/{berr[1]:.1e}; refined bound x {refined['x']:.1e} "
+              f"fr {refined['fr']:.1e}; corrected bound fr {corrected['fr']:.1e}")
+        assert raw["x"] >= 10 * refined["x"] and raw["fr"] >= 10 * refined["fr"] and raw["fr"] >= 10 * corrected["fr"]
+        assert berr.min() > sy.BERR_MAX
+
+
+# ----------------------------------------------------------------------------- the unpaired passes' dispatch
+def test_unpaired_dispatch_classes():
+    """launch_solve as forward_solve / adjoint_solve call it selects differently from the paired passes (see
+    sy.unpaired_classes): only the split of the update parts and the wave count.  Which shapes reach what, at
+    64-frequency chunks (tests/test_gpu_synthetic_hessian.py::test_unpaired_knobs runs them):
+      default (target 256)     every level of every shape has fewer than 17 fronts: split 16 everywhere except T's
+                               bottom level, so PFR_SOLVE_SPLIT=1000000 selects what the default does
+      PFR_SOLVE_SPLIT=64       A level 0 (9 fronts) split 8, B level 0 (7) split 10, roots 16
+      PFR_SOLVE_SPLIT=0        split 1: k_lsolve_level / k_usolve_level do the update parts themselves
+      PFR_SOLVE_WMAX=1         the size-based wave counts, as test_solve_launch_waves lists them
+    A general analysis never splits the U, U^T and L^T passes."""
+    A, B, C, T = (sy.unpaired_classes(sy.symbolic(s)) for s in "ABCT")
+    assert [d["split_L"] for d in A] == [16, 16] and [d["split_L"] for d in C] == [16, 16]
+    assert [d["nf"] for d in A] == [9, 1] and [d["nf"] for d in B] == [7, 1]
+    assert all(d["split_U"] == d["split_L"] for d in A + B + C + T)
+    assert all(d["split_L"] == 16 for d in T[1:]) and T[0]["nf"] < 256
+    big = [sy.unpaired_classes(sy.symbolic(s), split_target=1000000) for s in "ABCT"]
+    assert all(d["split_L"] == 16 for dc in big for d in dc)
+    assert [d["split_L"] for d in sy.unpaired_classes(sy.symbolic("A"), split_target=64)] == [8, 16]
+    assert [d["split_L"] for d in sy.unpaired_classes(sy.symbolic("B"), split_target=64)] == [10, 16]
+    for s in "ABCT":
+        off = sy.unpaired_classes(sy.symbolic(s), split_target=0)
+        assert all(d["split_L"] == 1 and d["split_U"] == 1 for d in off)
+        assert [d["solve_w"] for d in sy.unpaired_classes(sy.symbolic(s), solve_wmax=1)] == \
+            [d["level_w"] for d in sy.dispatch_classes(sy.symbolic(s))]
+        assert all(d["solve_w"] == 8 for d in sy.unpaired_classes(sy.symbolic(s)))
+    for s in sy.GENERAL_SHAPES:      # the general analysis of the shapes WITH Dirichlet nodes (the Hessian cases)
+        g = sy.unpaired_classes(sy.symbolic(s, symmetric=False))
+        assert all(d["split_U"] == 1 and d["split_L"] > 1 for d in g)
