@@ -220,6 +220,17 @@ PFR_API int pfr_sweep_fresh(pfr_solver* s, int32_t nfreq, const double* freqs_de
  * hipGraphLaunch afterwards -- the same kernels with the same arguments; only with PFR_GRAPH=1 (off by default).  The
  * reference's analogue is none: its sweep is a host loop of UMFPACK calls (InnerState.h:276-288). */
 PFR_API int64_t pfr_sweep_graph_launches(const pfr_solver* s);
+/* Per-frequency sensitivities on one factorisation per frequency: fr_dev[q] as pfr_sweep, and
+ *   jc_dev[q * n_stiff + k] = -mu_q^T S_k x_q + e_k mu_q^T rhs,   A_q^T mu_q = d fr_q / d x_q
+ * (complex, WRITTEN not accumulated, every row q < nfreq), in the convention of w: for any real cot,
+ *   sum_q cot_q jc[q][k] = w_k of pfr_sweep(PFR_LOSS_COTANGENT, ref.re = cot, scale 1) in the same check mode,
+ * so d fr_q / d theta_i = Re sum_k jc[q][k] d c_k / d theta_i.  The reverse sweep of a unit cotangent per frequency
+ * with the frequency sum left out: every pfr_set_check mode applies as in a loss sweep (under PFR_CHECK_CORRECT fr is
+ * the corrected response and the rows carry the solve-error scale).  Never part of the PFR_GRAPH graph; the next
+ * loss sweep is bit-identical to one run without it.  The reference has no analogue: jax.jacobian of its fr function
+ * solves one adjoint system per frequency and refactorises for each (InnerState.h:289-305). */
+PFR_API int pfr_jacobian_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, double* fr_dev /* may be NULL */,
+                               double* jc_dev, int32_t* flags_dev /* may be NULL */, void* stream);
 /* Stream ordering for a host that drives several solver lanes: work enqueued on `waiter` after this call starts
  * only after the work enqueued on `signaller` before it (one event of the calling thread and device, recorded on
  * signaller, waited for on waiter; both HIP stream handles of the current device).  The loss step orders each lane's

@@ -3,7 +3,8 @@
 Same names, arguments and ``optResult`` as the reference; ``jax.value_and_grad``
 becomes one fused forward + adjoint GPU sweep (``Problem.getLossFunction``).
 Additions: ``optimize_lbfgs`` (two-loop L-BFGS with a capped step and Armijo
-backtracking, the BASELINE.json C5 driver).  The trust-region Newton model
+backtracking, the BASELINE.json C5 driver) and ``optimize_lm`` (Levenberg-Marquardt
+over the residual and its per-frequency Jacobian, ``Problem.getResidualFunction``).  The trust-region Newton model
 (``Optimizers.py:125-136``, JAX forward-over-reverse there) takes the EXACT Hessian
 from ``Problem.getLossHessianFunction`` when ``solveInverse`` passes it as ``model``
 (one factorisation + forward/adjoint/second-order solves per evaluation, factors
@@ -275,4 +276,63 @@ def optimize_lbfgs(f, x_0, N_steps=50, history_size=10, max_step=0.05, c1=1e-4, 
                 S.pop(0)
                 Y.pop(0)
         x, cur_f, g = x_new, f_new, g_new
+    return optResult(x, cur_f, f_hist, x_hist, g_hist, k, status)
+
+
+def lm_step(Jr, r, lam):
+    """The Marquardt-scaled step p of ``(Jr^T Jr + lam diag(Jr^T Jr)) p = -Jr^T r`` (a parameter the residual does
+    not depend on gets a zero step)."""
+    N = Jr.T @ Jr
+    d = np.diag(N).copy()
+    d[d <= 0] = 1.0
+    return np.linalg.solve(N + lam * np.diag(d), -(Jr.T @ r))
+
+
+def optimize_lm(res, x_0, N_steps=30, lam0=1e-3, lam_down=1.0 / 3.0, lam_up=4.0, lam_min=1e-12, lam_max=1e12,
+                max_step=None, tolerance_grad=1e-12, f_min=1e-16, rtol_f=1e-8):
+    """Levenberg-Marquardt over ``res(x) -> (r (F,), Jr (F, p), const)`` with ``f = (r @ r + const) / F``
+    (``Problem.getResidualFunction``: one Jacobian sweep per evaluation).
+
+    Each iteration solves the Marquardt-scaled ``(Jr^T Jr + lam diag(Jr^T Jr)) p = -Jr^T r`` (``lm_step``).  A step
+    that decreases f is accepted and ``lam`` shrinks by ``lam_down``; a rejected step multiplies ``lam`` by
+    ``lam_up`` and the system is solved again with the SAME r and Jr (no sweep at x again; each trial point costs
+    one).  ``max_step`` caps a trial step's infinity norm as in ``optimize_lbfgs``.  ``f_history`` / ``x_history`` /
+    ``grad_history`` hold the accepted iterates only (the start first); ``niter`` counts the iterations."""
+    x = np.asarray(x_0, dtype=np.float64).copy()
+
+    def evaluate(y):
+        r, Jr, const = res(y)
+        r, Jr = np.asarray(r, dtype=np.float64), np.asarray(Jr, dtype=np.float64)
+        return r, Jr, (float(r @ r) + float(const)) / r.size
+
+    r, Jr, cur_f = evaluate(x)
+    lam = float(lam0)
+    f_hist, x_hist, g_hist = [], [], []
+    status, k = "Running", 0
+    for k in range(N_steps):
+        g = 2.0 / r.size * (Jr.T @ r)
+        f_hist.append(cur_f)               # x changes only by an accepted step: every entry is an accepted iterate
+        x_hist.append(x.copy())
+        g_hist.append(g.copy())
+        if cur_f <= f_min:
+            status = "Converged"
+            break
+        if np.max(np.abs(g)) <= tolerance_grad:
+            status = "Converged (gradient)"
+            break
+        accepted = False
+        while lam <= lam_max:
+            p = lm_step(Jr, r, lam)
+            if max_step is not None:
+                p *= min(1.0, max_step / max(np.max(np.abs(p)), 1e-300))
+            r_new, Jr_new, f_new = evaluate(x + p)
+            if np.isfinite(f_new) and f_new < cur_f:
+                accepted = True
+                break
+            lam *= lam_up                   # rejected: x, r and Jr stay, a shorter step from the same model
+        if not accepted:
+            status = "Converged (no further decrease)" if cur_f <= rtol_f * f_hist[0] else "Damping limit reached"
+            break
+        x, r, Jr, cur_f = x + p, r_new, Jr_new, f_new
+        lam = max(lam * lam_down, lam_min)
     return optResult(x, cur_f, f_hist, x_hist, g_hist, k, status)

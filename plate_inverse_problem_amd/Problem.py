@@ -526,6 +526,25 @@ class _Engine:
                              h=bufs[2], flags=None if flags is None else flags[lo:hi])
         self._run(call, freqs.numel(), [loss, w, h])
 
+    def jacobian_sweep(self, freqs, jc, fr=None, flags=None, berr=None):
+        """``Solver.jacobian_sweep`` over all lanes: every lane writes its own rows of ``jc`` (F, n_stiff) complex
+        (and of fr / flags / berr (F, 2)); nothing is accumulated.  Sets ``last_berr`` and ``last_flags``."""
+        if self.check_mode & _native.PFR_CHECK_REFINE_ADJ:
+            self._seeded = True        # as sweep: the lanes allocate their refinement seed vectors
+
+        def call(sv, lo, hi, bufs):
+            if berr is not None:
+                sv.set_check(self.check_mode, self.check_tol, berr[lo:hi])
+            try:
+                sv.jacobian_sweep(freqs[lo:hi], torch.view_as_real(jc[lo:hi]), fr=None if fr is None else fr[lo:hi],
+                                  flags=None if flags is None else flags[lo:hi])
+            finally:
+                if berr is not None:
+                    sv.set_check(self.check_mode, self.check_tol)
+        self._run(call, freqs.numel(), [])
+        self.last_berr = berr
+        self.last_flags = _check_flags(flags) if flags is not None else None
+
     # ---- measurement (bench.py)
     def set_timing(self, on, kernels=False):
         for sv in self.solvers:
@@ -648,6 +667,53 @@ class _JetSweepLoss(torch.autograd.Function):
         grad = ctx.gt * g
         return (grad.to(dtype=ctx.dtype, device=ctx.device) if ctx.cast else grad), None, None, None, None, None, \
             None, None, None
+
+
+def residual_terms(fr, reference_fr, func_type: str):
+    """The four losses as least squares (host, numpy): ``(r, dr/dfr, const)`` with
+    ``loss = (r @ r + const) / F`` and ``d loss / d fr = 2 r dr/dfr / F``.
+
+        MSE          r = fr - Re ref              const = sum Im(ref)^2
+        RMSE         r = (fr - Re ref) / |ref|    const = sum (Im ref / |ref|)^2
+        MSE_AFC      r = fr - |ref|               const = 0
+        MSE_LOG_AFC  r = log fr - log |ref|       const = 0"""
+    fr = np.asarray(fr, dtype=np.float64)
+    ref = np.asarray(reference_fr, dtype=np.complex128)
+    rabs = np.abs(ref)
+    one = np.ones_like(fr)
+    if func_type == 'MSE':
+        return fr - ref.real, one, float(np.sum(ref.imag ** 2))
+    if func_type == 'RMSE':
+        return (fr - ref.real) / rabs, one / rabs, float(np.sum((ref.imag / rabs) ** 2))
+    if func_type == 'MSE_AFC':
+        return fr - rabs, one, 0.0
+    if func_type == 'MSE_LOG_AFC':
+        return np.log(fr) - np.log(rabs), one / fr, 0.0
+    raise ValueError(f'Function type "{func_type}" is not supported!')
+
+
+def covariance_from_residual(r, Jr, const=0.0, rcond=1e-12):
+    """``(cov, std)`` of the least-squares estimate: ``cov = sigma^2 (Jr^T Jr)^+`` with
+    ``sigma^2 = (r @ r + const) / (F - p)``, the pseudo-inverse from the eigen-decomposition of the
+    column-scaled ``Jr^T Jr`` (unit diagonal: the parameters' units drop out of the singularity test).  Eigenvalues
+    below ``rcond`` times the largest are left out, with a warning: those parameter combinations are not determined
+    by the data."""
+    r, Jr = np.asarray(r, dtype=np.float64), np.asarray(Jr, dtype=np.float64)
+    F, p = Jr.shape
+    if F <= p:
+        raise ValueError(f'the covariance needs more residuals than parameters ({F} <= {p})')
+    N = Jr.T @ Jr
+    d = np.sqrt(np.diag(N))
+    d = np.where(d > 0, d, 1.0)
+    lam, V = np.linalg.eigh(N / np.outer(d, d))
+    keep = lam > rcond * max(float(lam[-1]), 0.0)
+    if not keep.all():
+        warnings.warn(f"Jr^T Jr is numerically singular ({int(np.count_nonzero(~keep))} of {p} eigenvalues below "
+                      f"{rcond:g} of the largest): the covariance is its pseudo-inverse's", RuntimeWarning)
+    Vk = V[:, keep] / d[:, None]
+    cov = (float(r @ r) + float(const)) / (F - p) * (Vk / lam[keep]) @ Vk.T
+    cov = 0.5 * (cov + cov.T)
+    return cov, np.sqrt(np.diag(cov))
 
 
 def _check_flags(flags):
@@ -1004,6 +1070,85 @@ class Problem:
             return float(val), grad, 0.5 * (hess + hess.T)
 
         return model
+
+    def getFRJacobianFunction(self, scaling_params=None) -> Callable:
+        """``fn(freqs, params) -> (fr (F,), J (F, n_params))``, float64 tensors on the device:
+        ``J[q, i] = d fr_q / d params_i`` from ONE sweep (one factorisation and one adjoint solve per frequency,
+        pfr_jacobian_sweep), where reverse mode through ``getFRFunction`` needs one adjoint sweep per frequency.
+        ``scaling_params``: the function is of ``params * scaling_params`` and J is with respect to ``params``."""
+        scaling = 1.0 if scaling_params is None else torch.as_tensor(np.array(scaling_params, dtype=np.float64))
+        transform = self._transform()
+
+        def c_real(p):
+            return torch.view_as_real(_coeffs18(transform, p * scaling)).reshape(-1)      # (36,)
+
+        def fn(freqs, params):
+            f = self._freqs(freqs)
+            p = torch.as_tensor(np.asarray(params.detach().cpu() if isinstance(params, torch.Tensor) else params,
+                                           dtype=np.float64)).detach()
+            n = p.numel()
+            if self.material.atype in _JET_TYPES:
+                # c and d c / d params as getLossHessianFunction forms them
+                from ._abd_jet import abd_and_jacobian
+                sc = np.broadcast_to(np.asarray(scaling, dtype=np.float64), (n,))
+                c, J = abd_and_jacobian(self.material, self.geometry.height, (p * scaling).numpy())
+                dc = J * sc[None, :]                                                      # (18, n)
+            else:
+                c = _coeffs18(transform, p * scaling).detach().numpy()
+                jac = torch.autograd.functional.jacobian(c_real, p).numpy().reshape(18, 2, n)
+                dc = jac[:, 0] + 1j * jac[:, 1]                                            # (18, n)
+            eng = self.engine(f.numel())
+            eng.set_coefficients(c)
+            dev = eng.device
+            F = f.numel()
+            fr = torch.empty(F, dtype=torch.float64, device=dev)
+            jc = torch.empty((F, eng.n_stiff), dtype=torch.complex128, device=dev)
+            flags = torch.zeros(F, dtype=torch.int32, device=dev)
+            berr = torch.full((F, 2), float('nan'), dtype=torch.float64, device=dev)
+            eng.jacobian_sweep(f, jc, fr=fr, flags=flags, berr=berr)
+            # J = Re(expand(jc) @ dc): the contracted matrices' rows of dc (the others' partials vanish)
+            dct = torch.as_tensor(np.ascontiguousarray(dc[eng.kidx]), device=dev)
+            return fr, torch.real(jc @ dct)
+
+        return fn
+
+    def solveForwardJacobian(self, freqs, params=None):
+        """``(fr (F,), J (F, n_params))`` (numpy): the frequency response and its derivative with respect to the
+        material parameters at every frequency."""
+        if params is None:
+            params = self.parameters
+        fr, J = self.getFRJacobianFunction()(freqs, params)
+        return fr.cpu().numpy(), J.cpu().numpy()
+
+    def getResidualFunction(self, frequencies, reference_fr, func_type: str, scaling_params=None) -> Callable:
+        """``res(params) -> (r (F,), Jr (F, p), const)`` (numpy): ``getLossFunction``'s loss as least squares,
+        ``loss = (r @ r + const) / F`` and ``grad = 2 / F * Jr.T @ r`` (``residual_terms``), for Gauss-Newton /
+        Levenberg-Marquardt (``Optimizers.optimize_lm``) and ``parameterCovariance``."""
+        frequencies = np.asarray(frequencies, dtype=np.float64)
+        reference_fr = np.asarray(reference_fr)
+        assert frequencies.shape[0] == reference_fr.shape[0]
+        if func_type not in _native.LOSS_IDS:
+            raise ValueError(f'Function type "{func_type}" is not supported!')
+        fn = self.getFRJacobianFunction(scaling_params)
+        f_dev = self._freqs(frequencies)
+
+        def res(params):
+            fr, J = fn(f_dev, params)
+            r, drdfr, const = residual_terms(fr.cpu().numpy(), reference_fr, func_type)
+            return r, drdfr[:, None] * J.cpu().numpy(), const
+
+        return res
+
+    def parameterCovariance(self, frequencies, reference_fr, func_type: str, params=None, scaling_params=None):
+        """``(cov (p, p), std (p,))`` of the parameters identified from ``reference_fr``: the Gauss-Newton
+        covariance ``sigma^2 (Jr^T Jr)^+`` with ``sigma^2 = (r @ r + const) / (F - p)`` at ``params`` (default: the
+        material's; in the units of ``params``, i.e. scaled ones with ``scaling_params``).  A parameter the
+        experiment does not determine shows as a large ``std``; a numerically singular ``Jr^T Jr`` warns."""
+        if params is None:
+            params = self.parameters if scaling_params is None else \
+                self.parameters / np.asarray(scaling_params, dtype=np.float64)
+        r, Jr, const = self.getResidualFunction(frequencies, reference_fr, func_type, scaling_params)(params)
+        return covariance_from_residual(r, Jr, const)
 
     def solveInverse(self, *args, **kwargs):
         from .inverse import solve_inverse

@@ -77,6 +77,7 @@ _PROTOS = {
     "pfr_sweep_graph_launches": (C.c_int64, [_P]),
     "pfr_stream_order": (C.c_int, [_P, _P]),
     "pfr_sweep_fresh": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, _P, _P, _P, _P]),
+    "pfr_jacobian_sweep": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P]),
     "pfr_solve_multi": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, C.c_int64,
                                   C.c_int32, _P, _P]),
     "pfr_hessian_sweep": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_double, C.c_int32, _P, _P, _P, _P, _P,
@@ -299,6 +300,12 @@ class Solver:
         check(lib().pfr_hessian_sweep(self._h, int(freqs.numel()), _ptr(freqs), int(loss_type), _ptr(ref),
                                       float(scale), int(d.shape[0]), d.ctypes.data_as(_P), _ptr(loss), _ptr(w),
                                       _ptr(h), _ptr(flags), self._stream(freqs)), "pfr_hessian_sweep")
+
+    def jacobian_sweep(self, freqs, jc, fr=None, flags=None, stream=None):
+        """pfr_jacobian_sweep: ``jc`` (nfreq, n_stiff) complex rows -mu_q^T S_k x_q + e_k mu_q^T rhs (written) and
+        ``fr`` (nfreq) on one factorisation per frequency, under the solver's check mode."""
+        check(lib().pfr_jacobian_sweep(self._h, int(freqs.numel()), _ptr(freqs), _ptr(fr), _ptr(jc), _ptr(flags),
+                                       self._stream(freqs) if stream is None else stream), "pfr_jacobian_sweep")
 
     # ---- InnerState-compatible
     def solve(self, data, data_stride, b, b_stride, x, transpose, batch, flags=None):

@@ -1204,10 +1204,15 @@ int pfr_set_functional(pfr_solver* s, int32_t n_support, const int32_t* index, c
 
 namespace {
 // The launches of one sweep (pfr_sweep after its argument checks), direct or under stream capture.
+// jc_dev != NULL (pfr_jacobian_sweep; loss_type = pfr::LOSS_UNIT, scale 1, no ref / loss / w): the reverse sweep of
+// a unit cotangent per frequency whose contraction stays per frequency -- the walk's kpart (or k_contract_q's, where
+// the walk has not formed it) finished by k_jac_finish into the rows of jc instead of k_reduce_q / k_contract_eg +
+// k_reduce into w.
 int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_t loss_type, const double* ref_dev,
                    double scale, double* fr_dev, double* loss_dev, double* w_dev, int32_t* flags_dev, hipStream_t st,
-                   bool fresh) {
+                   bool fresh, double2* jc_dev = nullptr) {
   const bool reverse = loss_type != PFR_LOSS_NONE;
+  const bool jac = jc_dev != nullptr;
   reset_timing(s);
   const int64_t Fc = s->Fc;
   const bool refine = (s->check_mode & PFR_CHECK_REFINE) != 0;
@@ -1327,7 +1332,7 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
       // the gradient contraction rides on the forward residual walk (loss sweeps with the correction)
       const bool cwalk = reverse && correct && s->contract_walk &&
                          (s->n_stiff == 12 || s->n_stiff == 18);
-      if (cwalk && !s->kpart) {
+      if ((cwalk || jac) && !s->kpart) {
         if ((rc = s->alloc(&s->kpart, s->ws.kpart))) return rc;
       }
       // selective adjoint refinement (PFR_CHECK_REFINE_ADJ): the groups next to a resonance, where the unrefined
@@ -1375,7 +1380,10 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
                                    s->mscale, st, nullptr, scorr ? s->tq : nullptr, bsc);
       }
       const double2* msc = correct ? s->mscale : nullptr;
-      if (cwalk)
+      if (jac) {
+        // the walk's kpart is final here (the refined groups redone above); without the walk k_contract_q forms it
+        if (!cwalk) pfr::launch_contract_q(s->d_uent, s->n_uent, s->d_se, s->n_stiff, s->XA, s->X, s->n, Fc, s->kpart, st);
+      } else if (cwalk)
         pfr::launch_reduce_q(s->kpart, pfr::residual_parts(s->n), s->n_stiff, msc, nv, Fc, s->partial, st);
       else if (reverse)
         pfr::launch_contract_eg(s->d_uent, s->n_uent, s->d_se, s->n_stiff, s->XA, s->X, Fc, nv, s->partial, st, msc);
@@ -1384,8 +1392,12 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
       if (want_a) check_solution(s, 1, 0, 2, rg, nullptr, 0, nv, s->XA, nullptr, q0, st);
       if (reverse) {
         if (!scorr) pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st, msc);
-        pfr::launch_reduce(s->partial, cwalk ? (int)(Fc / 64) : pfr::contract_eg_parts(s->n_uent), s->n_stiff, s->tq, s->e,
-                           s->loss_terms, nv, Fc, reinterpret_cast<double2*>(w_dev), loss_dev, st);
+        if (jac)
+          pfr::launch_jac_finish(s->kpart, cwalk ? pfr::residual_parts(s->n) : pfr::contract_q_parts(s->n, s->n_uent),
+                                 s->n_stiff, msc, s->tq, s->e, nv, Fc, jc_dev + q0 * s->n_stiff, st);
+        else
+          pfr::launch_reduce(s->partial, cwalk ? (int)(Fc / 64) : pfr::contract_eg_parts(s->n_uent), s->n_stiff, s->tq,
+                             s->e, s->loss_terms, nv, Fc, reinterpret_cast<double2*>(w_dev), loss_dev, st);
       }
     } else {
       record(s, 4, st);
@@ -1474,6 +1486,21 @@ int pfr_sweep_fresh(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32
 }
 
 int64_t pfr_sweep_graph_launches(const pfr_solver* s) { return s ? s->graph_launches : 0; }
+
+int pfr_jacobian_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, double* fr_dev, double* jc_dev,
+                       int32_t* flags_dev, void* stream) {
+  if (!s || nfreq <= 0 || !freqs_dev || !jc_dev) return fail(PFR_ERR_ARG, "bad jacobian sweep arguments");
+  if (!s->K || !s->M) return fail(PFR_ERR_STATE, "operator not set (pfr_set_operator)");
+  if (!s->has_rhs) return fail(PFR_ERR_STATE, "rhs not set (pfr_set_rhs)");
+  if (!s->has_fn) return fail(PFR_ERR_STATE, "functional not set (pfr_set_functional)");
+  if (!s->stiff) return fail(PFR_ERR_STATE, "jacobian sweep needs pfr_set_stiffness");
+  // never captured, and the loss sweeps' graph is not replayed past it: the next loss sweep runs directly
+  s->drop_graph();
+  s->gkey_valid = false;
+  HIP_TRY(hipSetDevice(s->device));
+  return sweep_launches(s, nfreq, freqs_dev, pfr::LOSS_UNIT, nullptr, 1.0, fr_dev, nullptr, nullptr, flags_dev,
+                        (hipStream_t)stream, false, reinterpret_cast<double2*>(jc_dev));
+}
 
 int pfr_stream_order(void* waiter, void* signaller) {
   // one event per (thread, device), recorded again for every ordering: a wait takes the event's state at the time

@@ -40,6 +40,10 @@ struct RhsScale {
   double mass_sum = 0, beta_re = 0, beta_im = 0;
 };
 
+// internal loss id of pfr_jacobian_sweep: d L / d fr_q = 1 for every frequency, no reference (never accepted from
+// a caller of pfr_sweep)
+constexpr int LOSS_UNIT = PFR_LOSS_COTANGENT + 1;
+
 struct FunctionalArgs {
   int32_t n_support;
   const int32_t* pidx;    // permuted DOF index of each support entry (device)

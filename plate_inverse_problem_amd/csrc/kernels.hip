@@ -2851,7 +2851,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NSK > 0 ? R
 }
 
 // Per-frequency loss term and its derivative d term / d fr (Problem.py:948-975); PFR_LOSS_COTANGENT:
-// no term, derivative = ref.re (dL/dfr supplied by the caller).
+// no term, derivative = ref.re (dL/dfr supplied by the caller); LOSS_UNIT (the Jacobian sweep): no term, derivative 1.
 __device__ __forceinline__ void loss_term(int loss_type, double fr, cplx r, double& term, double& dl) {
   const double rabs = sqrt(r.x * r.x + r.y * r.y);
   term = 0.0;
@@ -2880,9 +2880,17 @@ __device__ __forceinline__ void loss_term(int loss_type, double fr, cplx r, doub
     case PFR_LOSS_COTANGENT:
       dl = r.x;
       break;
+    case LOSS_UNIT:
+      dl = 1.0;
+      break;
     default:
       break;
   }
+}
+
+// the loss's reference value of a frequency; the Jacobian sweep's unit cotangent (LOSS_UNIT) has none
+__device__ __forceinline__ cplx loss_ref(const FunctionalArgs& A, int64_t q) {
+  return A.loss_type == LOSS_UNIT ? make_double2(0, 0) : A.ref[q];
 }
 
 // Functional correction (adjoint-weighted residual): with mu the adjoint of fr (A^T mu = d fr / d x,
@@ -2931,7 +2939,7 @@ __global__ __launch_bounds__(256) void k_correct_finish(FunctionalArgs A, const 
   if (valid && fr_out) fr_out[q_global0 + q] = fr;
   if (A.loss_type < 0) return;
   double term = 0.0, dl = 0.0;
-  if (valid) loss_term(A.loss_type, fr, A.ref[q_global0 + q], term, dl);
+  if (valid) loss_term(A.loss_type, fr, loss_ref(A, q_global0 + q), term, dl);
   loss_terms[q] = term;
   cplx m = make_double2(valid ? dl * A.scale : 0.0, 0.0);
   if (tq) {
@@ -3095,7 +3103,7 @@ __global__ void k_functional(FunctionalArgs A, const cplx* __restrict__ X, int64
     if (valid && fr_out) fr_out[q_global0 + q] = fr;
     if (A.loss_type < 0) return;
     double term = 0.0, dl = 0.0;
-    if (valid) loss_term(A.loss_type, fr, A.ref[q_global0 + q], term, dl);
+    if (valid) loss_term(A.loss_type, fr, loss_ref(A, q_global0 + q), term, dl);
     loss_terms[q] = term;
     s = valid && fr > 0.0 ? dl * A.scale / fr : 0.0;
   }
@@ -3168,7 +3176,7 @@ __global__ void k_functional_fn(FunctionalArgs A, const cplx* __restrict__ parts
     if (valid && fr_out) fr_out[q_global0 + q] = fr;
     if (A.loss_type >= 0) {
       double term = 0.0, dl = 0.0;
-      if (valid) loss_term(A.loss_type, fr, A.ref[q_global0 + q], term, dl);
+      if (valid) loss_term(A.loss_type, fr, loss_ref(A, q_global0 + q), term, dl);
       loss_terms[q] = term;
       s = valid && fr > 0.0 ? dl * A.scale / fr : 0.0;
     }
@@ -3337,6 +3345,89 @@ __global__ __launch_bounds__(256) void k_reduce_q(const cplx* __restrict__ kpart
     }
     if (lane == 0) partial[(int64_t)tile * n_stiff + k] = make_double2(re, im);
   }
+}
+
+// Per-frequency contraction (the Jacobian sweep where the forward walk has not formed it): k_contract_eg's entries
+// and stiffness copy, but lane = frequency and nothing summed over the lanes --
+//   kpart[(b NS + k) Fc + q] = sum_{e of workgroup b} S_k(e) Lam_i(q) X_j(q)
+// in k_residual's layout, so that k_jac_finish is the only finisher.  Grid (parts, Fc / 64), 4 waves: wave
+// (b, w) walks the entries 4 b + w, 4 b + w + 4 parts, ... in batches of CQ_U (their 2 CQ_U 1 KiB runs of Lam and
+// X issued before the products; the entry record and its NS stiffness values are wave-uniform loads), then the
+// four waves are summed in LDS in wave order.  Pseudo entries and entries absent from A carry S = 0: skipped.
+constexpr int CQ_U = 4;
+template <int NS>
+__global__ __launch_bounds__(256) void k_contract_q(const int4* __restrict__ ent, int nent, const double* __restrict__ se,
+                                                    const cplx* __restrict__ Lam, const cplx* __restrict__ X, int64_t Fc,
+                                                    cplx* __restrict__ kpart) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t q = (int64_t)blockIdx.y * 64 + lane;
+  const int wv = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + w);
+  const int nwaves = gridDim.x * 4;
+  cplx ks[NS];
+#pragma unroll
+  for (int k = 0; k < NS; ++k) ks[k] = make_double2(0, 0);
+  for (int e0 = wv; e0 < nent; e0 += CQ_U * nwaves) {
+    cplx li[CQ_U], xj[CQ_U];
+    int ee[CQ_U];
+#pragma unroll
+    for (int u = 0; u < CQ_U; ++u) {
+      const int e = e0 + u * nwaves;
+      const int4 en = ent[min(e, nent - 1)];
+      ee[u] = (e < nent && en.x >= 0 && en.y >= 0) ? e : -1;
+      li[u] = Lam[(int64_t)max(en.w, 0) * Fc + q];
+      xj[u] = X[(int64_t)max(en.x, 0) * Fc + q];
+    }
+#pragma unroll
+    for (int u = 0; u < CQ_U; ++u) {
+      if (ee[u] < 0) continue;               // wave-uniform
+      const cplx lx = cmul(li[u], xj[u]);
+      const double* sk = se + (int64_t)ee[u] * NS;
+#pragma unroll
+      for (int k = 0; k < NS; ++k) {
+        ks[k].x = fma(sk[k], lx.x, ks[k].x);
+        ks[k].y = fma(sk[k], lx.y, ks[k].y);
+      }
+    }
+  }
+  __shared__ cplx sks[4][64];
+#pragma unroll
+  for (int k = 0; k < NS; ++k) {
+    __syncthreads();
+    sks[w][lane] = ks[k];
+    __syncthreads();
+    if (w == 0)
+      kpart[((int64_t)blockIdx.x * NS + k) * Fc + q] =
+          cadd(cadd(sks[0][lane], sks[1][lane]), cadd(sks[2][lane], sks[3][lane]));
+  }
+}
+
+// The Jacobian sweep's finisher (in place of k_reduce_q + k_reduce): per 64-frequency tile
+//   jc[(q0 + q) NS + k] = -m_q sum_b kpart[b][k][q] + e_k t_q      (b ascending: a fixed order)
+// with m_q the loss sweep's cotangent scale of a unit cotangent (msc, NULL: 1) and t_q = m_q mu_q^T rhs (k_rhs_dot /
+// k_correct_finish).  Wave w of the 16 sums k = w, w + 16 (lane = frequency: contiguous 1 KiB runs of kpart); the
+// tile is staged in LDS (rows padded by one entry) and stored as ONE contiguous run of nrows x NS entries -- the
+// rows of jc are NS x 16 B apart, a lane-per-frequency store would scatter 64 16-byte pieces per k.  Only the rows
+// q < nvalid are stored.
+template <int NS>
+__global__ __launch_bounds__(1024) void k_jac_finish(const cplx* __restrict__ kpart, int nparts,
+                                                     const cplx* __restrict__ msc, const cplx* __restrict__ t_q,
+                                                     CoefPack e, int nvalid, int64_t Fc, cplx* __restrict__ jc) {
+  __shared__ cplx tile[64 * (NS + 1)];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t q = (int64_t)blockIdx.x * 64 + lane;
+  const cplx m = msc ? msc[q] : make_double2(1.0, 0.0);
+  const cplx t = t_q[q];
+  for (int k = w; k < NS; k += 16) {
+    cplx s = make_double2(0, 0);
+#pragma unroll 8
+    for (int b = 0; b < nparts; ++b) s = cadd(s, kpart[((int64_t)b * NS + k) * Fc + q]);
+    const cplx ms = cmul(m, s);
+    tile[lane * (NS + 1) + k] = make_double2(fma(e.re[k], t.x, -ms.x), fma(e.re[k], t.y, -ms.y));
+  }
+  __syncthreads();
+  const int nrows = min(64, nvalid - (int)blockIdx.x * 64);
+  cplx* __restrict__ out = jc + (int64_t)blockIdx.x * 64 * NS;
+  for (int i = threadIdx.x; i < nrows * NS; i += blockDim.x) out[i] = tile[(i / NS) * (NS + 1) + i % NS];
 }
 
 __global__ void k_reduce(const cplx* __restrict__ partial, int nparts, int n_stiff, const cplx* __restrict__ t_q,
@@ -3754,6 +3845,20 @@ void launch_rhs_dot(const int* sup, const double* val, int n_sup, const double2*
 void launch_reduce_q(const double2* kpart, int nparts, int n_stiff, const double2* msc, int nvalid, int64_t Fc,
                      double2* partial, hipStream_t st) {
   LAUNCH(k_reduce_q, dim3(n_stiff, (unsigned)(Fc / 64)), dim3(256), st, kpart, nparts, n_stiff, msc, nvalid, Fc, partial);
+}
+
+void launch_contract_q(const int4* ent, int nent, const double* se, int n_stiff, const double2* Lam, const double2* X,
+                       int n, int64_t Fc, double2* kpart, hipStream_t st) {
+  const dim3 g(contract_q_parts(n, nent), (unsigned)(Fc / 64)), b(256);
+  if (n_stiff == 12) LAUNCH(k_contract_q<12>, g, b, st, ent, nent, se, Lam, X, Fc, kpart);
+  else LAUNCH(k_contract_q<18>, g, b, st, ent, nent, se, Lam, X, Fc, kpart);
+}
+
+void launch_jac_finish(const double2* kpart, int nparts, int n_stiff, const double2* msc, const double2* t_q,
+                       const CoefPack& e, int nvalid, int64_t Fc, double2* jc, hipStream_t st) {
+  const dim3 g((unsigned)(Fc / 64)), b(1024);
+  if (n_stiff == 12) LAUNCH(k_jac_finish<12>, g, b, st, kpart, nparts, msc, t_q, e, nvalid, Fc, jc);
+  else LAUNCH(k_jac_finish<18>, g, b, st, kpart, nparts, msc, t_q, e, nvalid, Fc, jc);
 }
 
 void launch_reduce(const double2* partial, int nparts, int n_stiff, const double2* t_q, const CoefPack& e,

@@ -114,6 +114,14 @@ void launch_rhs_dot(const int* sup, const double* val, int n_sup, const double2*
 void launch_reduce(const double2* partial, int nparts, int n_stiff, const double2* t_q, const CoefPack& e,
                    const double* loss_terms, int nvalid, int64_t Fc, double2* w_out, double* loss_out,
                    hipStream_t st);
+// Jacobian sweep.  launch_contract_q: the per-frequency contraction in k_residual's kpart layout,
+// kpart[(b n_stiff + k) Fc + q] over contract_q_parts(n, nent) workgroups b (entries and se as launch_contract_eg).
+// launch_jac_finish: jc[q n_stiff + k] = -msc[q] sum_b kpart[b][k][q] + e_k t_q[q] for the chunk's rows q < nvalid
+// (jc: the chunk's first row; msc NULL: 1; written, not accumulated)
+void launch_contract_q(const int4* ent, int nent, const double* se, int n_stiff, const double2* Lam, const double2* X,
+                       int n, int64_t Fc, double2* kpart, hipStream_t st);
+void launch_jac_finish(const double2* kpart, int nparts, int n_stiff, const double2* msc, const double2* t_q,
+                       const CoefPack& e, int nvalid, int64_t Fc, double2* jc, hipStream_t st);
 // symmetric mode: forward right-hand-side corrections (src 0: operator rhs -> Bc; src 2: G in
 // place) and the adjoint's Dirichlet rows (X in place)
 void launch_dirichlet_rhs(int src, const DirDesc& d, int n_crow, const RhsDesc& rd, double2* G, double2* Bc,

@@ -513,6 +513,7 @@ std::string check_plan(const Symbolic& S, const Plan& P, int64_t Fc, int split_t
   // per-workgroup partial buffers against the grids that write them
   if ((int64_t)residual_parts(S.n) * Fc > W.cpart) return "k_residual partials";                  // cpart[bx Fc + q]
   if ((int64_t)residual_parts(S.n) * 18 * Fc > W.kpart) return "k_residual contraction partials"; // kpart[(bx 18 + k) Fc + q]
+  if ((int64_t)contract_q_parts(S.n, P.n_uent) * 18 * Fc > W.kpart) return "k_contract_q contraction partials";
   {
     const int64_t partial = (int64_t)std::max<int64_t>(contract_eg_parts(P.n_uent), Fc / 64) * 18;   // api.cpp's size
     if ((int64_t)contract_eg_parts(P.n_uent) * 18 > partial || (Fc / 64) * 18 > partial) return "gradient partials";

@@ -55,6 +55,10 @@ constexpr int64_t LDS_BYTES = 160 * 1024;
 // api.cpp to prove which launch class each synthetic shape reaches: change them there too)
 inline int residual_parts(int n) { return (int)std::min<int64_t>((n + 3) / 4, 256); }   // k_residual grid.x
 inline int contract_eg_parts(int nent) { return ((nent + CEG_EW - 1) / CEG_EW + 3) / 4; }   // k_contract_eg grid
+// k_contract_q grid.x: at least 16 entries per wave, never more workgroups than k_residual's (kpart holds them)
+inline int contract_q_parts(int n, int nent) {
+  return (int)std::max<int64_t>(1, std::min<int64_t>(residual_parts(n), ((int64_t)nent + 63) / 64));
+}
 // dynamic LDS of k_factor_sym_lds for a level whose largest pivot block is maxns (triangle + 8 W columns)
 inline int64_t fac_lds_bytes(int maxns) { return ((int64_t)maxns * (maxns + 1) / 2 + (int64_t)maxns * 8) * 16; }
 // k_lsolve_level_z's NAR form: the level's largest pivot block's values in dynamic LDS (ns x 64 x 16 B), beside

@@ -4,8 +4,9 @@ Same arguments, optimizer names, scaling/relative-start semantics, report text
 and ``.npz`` history log as the reference.  The loss is the fused GPU
 forward + adjoint sweep; ``distributed=True`` shards the frequencies over the
 ranks of an initialised ``torch.distributed`` group (one all-reduce per
-evaluation, every rank runs the identical optimiser).  Extra optimizer:
-``'lbfgs'`` (BASELINE.json C5).
+evaluation, every rank runs the identical optimiser).  Extra optimizers:
+``'lbfgs'`` (BASELINE.json C5) and ``'lm'`` / ``'levenberg_marquardt'`` (least squares over
+``Problem.getResidualFunction``'s residual and per-frequency Jacobian; single process).
 """
 from __future__ import annotations
 
@@ -21,7 +22,7 @@ from .Input import Compressor
 
 _LOCAL = {("trust_region", "tr"): opt.optimize_trust_region, ("coord_descent", "cd"): opt.optimize_cd,
           ("coord_descent_mem", "cd_mem"): opt.optimize_cd_mem2, ("grad_descent", "gd"): opt.optimize_gd,
-          ("lbfgs", "l-bfgs"): opt.optimize_lbfgs}
+          ("lbfgs", "l-bfgs"): opt.optimize_lbfgs, ("levenberg_marquardt", "lm"): opt.optimize_lm}
 
 
 def _a2s(s):
@@ -69,6 +70,8 @@ def solve_inverse(prob, arg0, loss_type: str, optimizer: str, compression=(False
     else:
         raise ValueError('Invalid shape of `arg0` argument.')
 
+    if distributed and optimizer in ('levenberg_marquardt', 'lm'):
+        raise NotImplementedError('the Jacobian sweep is not distributed: use `lm` with distributed=False')
     loss = prob.getLossFunction(ref_fr[0], ref_fr[1], loss_type, scaling, distributed=distributed)
     scale_arr = np.ones_like(x0) if scaling is None else (np.tile(scaling, (2, 1)).T if x0.ndim == 2 else scaling)
 
@@ -80,6 +83,9 @@ def solve_inverse(prob, arg0, loss_type: str, optimizer: str, compression=(False
             opt_kwargs['model'] = prob.getLossHessianFunction(ref_fr[0], ref_fr[1], loss_type, scaling,
                                                               distributed=distributed)
         opt_kwargs.pop('exact_hessian', None)
+        if local is opt.optimize_lm:
+            # least squares: the residual and its per-frequency Jacobian (one sweep) in place of the loss
+            loss = prob.getResidualFunction(ref_fr[0], ref_fr[1], loss_type, scaling)
     elif optimizer in ('de', 'shgo'):
         def np_loss(x):
             return float(loss(torch.as_tensor(np.asarray(x, dtype=np.float64))))
