@@ -231,6 +231,26 @@ PFR_API int64_t pfr_sweep_graph_launches(const pfr_solver* s);
  * solves one adjoint system per frequency and refactorises for each (InnerState.h:289-305). */
 PFR_API int pfr_jacobian_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, double* fr_dev /* may be NULL */,
                                double* jc_dev, int32_t* flags_dev /* may be NULL */, void* stream);
+/* A population of parameter sets in one sweep: a lane is a (member, frequency) pair.
+ * pfr_combine_batch: Kpop_dev[m * nnz + nz] = sum_k coef[m * n_stiff + k] S_k(nz) for m < n_members (member-major;
+ * each row bitwise what pfr_combine gives for that member's coefficients), the stiffness read once.
+ * pfr_population_sweep: nlane lanes, a positive multiple of 64; the lanes 64 g .. 64 g + 63 (group g) solve
+ *   (Kpop[member[g]] - omega_q^2 M) x_q = rhs (beta[member[g]] - omega_q^2 mass_sum)
+ * with rhs and mass_sum of pfr_set_rhs and M of pfr_set_operator (that call's K and pfr_set_rhs's beta are not read).
+ * With jc_dev the sweep is pfr_jacobian_sweep's per lane (fr_dev[q], jc_dev[q * n_stiff + k] written); without,
+ * the forward sweep (fr_dev only).  Every pfr_set_check mode applies per lane as in those sweeps, except
+ * PFR_CHECK_REFINE_ADJ (it ranks the groups of a chunk against each other: PFR_ERR_ARG).  A lane's results are
+ * bitwise those of pfr_jacobian_sweep over the same nlane frequencies with that member's K and beta set.  A member
+ * index outside [0, n_members) or an nlane that is no multiple of 64 is PFR_ERR_ARG, checked before anything is
+ * launched.  Never part of the PFR_GRAPH graph; the next loss sweep is bit-identical to one run without it.  The
+ * reference evaluates a population one member at a time (scipy calling its loss function, Optimizers.py). */
+PFR_API int pfr_combine_batch(pfr_solver* s, int32_t n_members, const double* coef_host /* n_members x n_stiff complex */,
+                              double* Kpop_dev /* n_members x nnz complex */, void* stream);
+PFR_API int pfr_population_sweep(pfr_solver* s, int32_t nlane, const double* freqs_dev /* nlane */,
+                                 const int32_t* member_host /* nlane / 64 */, int32_t n_members,
+                                 const double* Kpop_dev, const double* beta_host /* n_members complex */,
+                                 double* fr_dev /* nlane */, double* jc_dev /* nlane x n_stiff complex, may be NULL */,
+                                 int32_t* flags_dev /* may be NULL */, void* stream);
 /* Stream ordering for a host that drives several solver lanes: work enqueued on `waiter` after this call starts
  * only after the work enqueued on `signaller` before it (one event of the calling thread and device, recorded on
  * signaller, waited for on waiter; both HIP stream handles of the current device).  The loss step orders each lane's

@@ -545,6 +545,51 @@ class _Engine:
         self.last_berr = berr
         self.last_flags = _check_flags(flags) if flags is not None else None
 
+    def population_sweep(self, freqs, C, jac=True):
+        """One sweep for a population of coefficient sets ``C`` (P, 18) complex over the same ``freqs`` (F,): a lane
+        is a (member, frequency) pair in ``population_layout``'s order, every 64-lane group assembled from its
+        member's operator (pfr_combine_batch, pfr_population_sweep); the engine is sized for the P Fpad lanes and they
+        are split over the solver lanes as any sweep's frequencies.  Returns ``(fr (P, F), jc (P, F, n_stiff) complex
+        or None without jac, flags (P, F) int32 host, berr (P, F, 2))``, the padded lanes dropped.  The selective
+        adjoint refinement (PFR_CHECK_REFINE_ADJ) ranks the groups of a chunk against each other and is left out
+        of the check mode here."""
+        C = np.asarray(C, dtype=np.complex128)
+        if C.ndim != 2 or C.shape[1] != 18:
+            raise ValueError('population_sweep takes a (members, 18) coefficient array')
+        P, F = C.shape[0], int(freqs.numel())
+        index, member, valid = population_layout(P, F)
+        L = index.size
+        self.ensure(L)
+        dev = self.device
+        Kpop = torch.empty((P, self.keep.size), dtype=torch.complex128, device=dev)
+        self.solver.combine_batch(C[:, self.kidx], torch.view_as_real(Kpop))
+        beta = C @ self.e
+        if self._coef_key is None:
+            # the Dirichlet vector and the mass sum (the population sweep reads them, not this beta)
+            for sv in self.solvers:
+                sv.set_rhs(self.rhs, complex(beta[0]), self.mass_sum)
+        f = freqs[torch.as_tensor(index, device=dev)].contiguous()
+        fr = torch.empty(L, dtype=torch.float64, device=dev)
+        jc = torch.empty((L, self.n_stiff), dtype=torch.complex128, device=dev) if jac else None
+        flags = torch.zeros(L, dtype=torch.int32, device=dev)
+        berr = torch.full((L, 2), float('nan'), dtype=torch.float64, device=dev)
+        mode = self.check_mode & ~_native.PFR_CHECK_REFINE_ADJ
+        Kr = torch.view_as_real(Kpop)
+
+        def call(sv, lo, hi, bufs):
+            sv.set_check(mode, self.check_tol, berr[lo:hi])
+            try:
+                sv.population_sweep(f[lo:hi], member[lo // 64:(hi + 63) // 64], Kr, beta, fr[lo:hi],
+                                    jc=None if jc is None else torch.view_as_real(jc[lo:hi]), flags=flags[lo:hi])
+            finally:
+                sv.set_check(self.check_mode, self.check_tol)
+        self._run(call, L, [])
+        vm = torch.as_tensor(valid, device=dev)
+        pick = lambda t: t[vm].reshape((P, F) + t.shape[1:])                 # noqa: E731
+        self.last_berr = pick(berr)
+        self.last_flags = _check_flags(pick(flags))
+        return pick(fr), None if jc is None else pick(jc), self.last_flags, self.last_berr
+
     # ---- measurement (bench.py)
     def set_timing(self, on, kernels=False):
         for sv in self.solvers:
@@ -714,6 +759,39 @@ def covariance_from_residual(r, Jr, const=0.0, rcond=1e-12):
     cov = (float(r @ r) + float(const)) / (F - p) * (Vk / lam[keep]) @ Vk.T
     cov = 0.5 * (cov + cov.T)
     return cov, np.sqrt(np.diag(cov))
+
+
+def population_layout(n_members: int, n_freqs: int):
+    """Lane layout of a population sweep (host, numpy): member ``p`` owns the ``Fpad = 64 ceil(F / 64)`` lanes from
+    ``p * Fpad``, its frequencies first and the rest repeating its last one.  Returns ``(index (P Fpad,) of each
+    lane's frequency, member (P Fpad / 64,) int32 of each 64-lane group, valid (P Fpad,) bool: not a padded lane)``."""
+    P, F = int(n_members), int(n_freqs)
+    if P <= 0 or F <= 0:
+        raise ValueError('a population sweep needs at least one member and one frequency')
+    fpad = (F + 63) // 64 * 64
+    lane = np.arange(fpad)
+    index = np.tile(np.minimum(lane, F - 1), P)
+    member = np.repeat(np.arange(P, dtype=np.int32), fpad // 64)
+    valid = np.tile(lane < F, P)
+    return index, member, valid
+
+
+def population_loss_grad(fr, jc, dc, reference_fr, func_type: str):
+    """Losses ``(P,)`` and gradients ``(P, n_par)`` (None without ``jc``) of a population from its sweep's results
+    (host, numpy): ``fr`` (P, F), the Jacobian sweep's rows ``jc`` (P, F, K) over the K contracted matrices and each
+    member's ``dc`` (P, K, n_par) = d c_k / d params.  Per member ``loss = (r @ r + const) / F`` and ``grad = 2 Jr^T r
+    / F`` with ``Jr = dr/dfr * Re(jc @ dc)`` (``residual_terms``, ``getFRJacobianFunction``)."""
+    fr = np.asarray(fr, dtype=np.float64)
+    P, F = fr.shape
+    loss = np.empty(P)
+    grad = None if jc is None else np.empty((P, np.asarray(dc).shape[2]))
+    for p in range(P):
+        r, drdfr, const = residual_terms(fr[p], reference_fr, func_type)
+        loss[p] = (float(r @ r) + const) / F
+        if jc is not None:
+            Jr = drdfr[:, None] * np.real(np.asarray(jc[p]) @ np.asarray(dc[p]))
+            grad[p] = 2.0 * (Jr.T @ r) / F
+    return loss, grad
 
 
 def _check_flags(flags):
@@ -1138,6 +1216,68 @@ class Problem:
             return r, drdfr[:, None] * J.cpu().numpy(), const
 
         return res
+
+    def _population_coeffs(self, params, scaling, with_jac: bool):
+        """``(C (P, 18), dC (P, 18, n_par) or None)``: c(params_p * scaling) of every member and, with ``with_jac``,
+        its derivative with respect to params_p (as ``getFRJacobianFunction`` forms them)."""
+        params = np.atleast_2d(np.asarray(params, dtype=np.float64))
+        P, n = params.shape
+        sc = np.broadcast_to(np.asarray(scaling, dtype=np.float64), (n,))
+        transform = self._transform()
+        C = np.empty((P, 18), dtype=np.complex128)
+        dC = np.empty((P, 18, n), dtype=np.complex128) if with_jac else None
+        for i in range(P):
+            p = torch.as_tensor(params[i] * sc)
+            if self.material.atype in _JET_TYPES:
+                from ._abd_jet import abd_and_jacobian
+                C[i], J = abd_and_jacobian(self.material, self.geometry.height, p.numpy())
+                if with_jac:
+                    dC[i] = J * sc[None, :]
+            else:
+                C[i] = _coeffs18(transform, p).detach().numpy()
+                if with_jac:
+                    jac = torch.autograd.functional.jacobian(
+                        lambda x: torch.view_as_real(_coeffs18(transform, x)).reshape(-1), p).numpy().reshape(18, 2, n)
+                    dC[i] = (jac[:, 0] + 1j * jac[:, 1]) * sc[None, :]
+        return C, dC
+
+    def solveForwardPopulation(self, freqs, params) -> np.ndarray:
+        """Frequency responses ``(P, F)`` of the P parameter sets ``params`` (P, n_par) at ``freqs`` [Hz] from ONE
+        sweep whose lanes are (member, frequency) pairs (``_Engine.population_sweep``): narrow sweeps of many
+        parameter sets -- a differential-evolution generation, multi-start trial points -- fill the device that a
+        single one leaves mostly idle."""
+        f = self._freqs(freqs)
+        C, _ = self._population_coeffs(params, 1.0, False)
+        eng = self.engine(population_layout(C.shape[0], f.numel())[0].size)
+        return eng.population_sweep(f, C, jac=False)[0].cpu().numpy()
+
+    def getPopulationLossFunction(self, frequencies, reference_fr, func_type: str, scaling_params=None,
+                                  with_grad: bool = False, *, distributed: bool = False) -> Callable:
+        """``fn(params (P, n_par)) -> losses (P,)`` -- with ``with_grad`` ``(losses, gradients (P, n_par))`` -- (numpy)
+        of ``getLossFunction``'s loss for a whole population in one sweep.  Without ``with_grad`` the sweep is
+        forward-only; with it, the per-frequency Jacobian sweep per lane, from which every member's gradient
+        ``2 Jr^T r / F`` (and, if wanted, its Levenberg-Marquardt Jacobian) is a small host-side product
+        (``population_loss_grad``)."""
+        if distributed:
+            raise NotImplementedError('the population sweep is not distributed: use distributed=False')
+        frequencies = np.asarray(frequencies, dtype=np.float64)
+        reference_fr = np.asarray(reference_fr)
+        assert frequencies.shape[0] == reference_fr.shape[0]
+        if func_type not in _native.LOSS_IDS:
+            raise ValueError(f'Function type "{func_type}" is not supported!')
+        scaling = 1.0 if scaling_params is None else np.array(scaling_params, dtype=np.float64)
+        f_dev = self._freqs(frequencies)
+
+        def fn(params):
+            C, dC = self._population_coeffs(params, scaling, with_grad)
+            P = C.shape[0]
+            eng = self.engine(population_layout(P, f_dev.numel())[0].size)
+            fr, jc, _, _ = eng.population_sweep(f_dev, C, jac=with_grad)
+            loss, grad = population_loss_grad(fr.cpu().numpy(), None if jc is None else jc.cpu().numpy(),
+                                              None if dC is None else dC[:, eng.kidx], reference_fr, func_type)
+            return (loss, grad) if with_grad else loss
+
+        return fn
 
     def parameterCovariance(self, frequencies, reference_fr, func_type: str, params=None, scaling_params=None):
         """``(cov (p, p), std (p,))`` of the parameters identified from ``reference_fr``: the Gauss-Newton

@@ -78,6 +78,8 @@ _PROTOS = {
     "pfr_stream_order": (C.c_int, [_P, _P]),
     "pfr_sweep_fresh": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, _P, _P, _P, _P]),
     "pfr_jacobian_sweep": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P]),
+    "pfr_combine_batch": (C.c_int, [_P, C.c_int32, _DP, _P, _P]),
+    "pfr_population_sweep": (C.c_int, [_P, C.c_int32, _P, _I32P, C.c_int32, _P, _DP, _P, _P, _P, _P]),
     "pfr_solve_multi": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, C.c_int64,
                                   C.c_int32, _P, _P]),
     "pfr_hessian_sweep": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_double, C.c_int32, _P, _P, _P, _P, _P,
@@ -306,6 +308,28 @@ class Solver:
         ``fr`` (nfreq) on one factorisation per frequency, under the solver's check mode."""
         check(lib().pfr_jacobian_sweep(self._h, int(freqs.numel()), _ptr(freqs), _ptr(fr), _ptr(jc), _ptr(flags),
                                        self._stream(freqs) if stream is None else stream), "pfr_jacobian_sweep")
+
+    def combine_batch(self, coef: np.ndarray, out, stream=None):
+        """pfr_combine_batch: ``out`` (P, nnz) complex = the operators of the P coefficient rows ``coef`` (P, n_stiff),
+        each row bitwise ``combine`` of that row."""
+        c = np.ascontiguousarray(np.asarray(coef, dtype=np.complex128))
+        if c.ndim != 2:
+            raise ValueError("combine_batch takes a (members, n_stiff) coefficient array")
+        check(lib().pfr_combine_batch(self._h, int(c.shape[0]), c.view(np.float64).ctypes.data_as(_DP), _ptr(out),
+                                      self._stream(out) if stream is None else stream), "pfr_combine_batch")
+        return out
+
+    def population_sweep(self, freqs, member, Kpop, beta, fr, jc=None, flags=None, stream=None):
+        """pfr_population_sweep over ``freqs.numel()`` lanes (a multiple of 64): group g (64 lanes) is solved with
+        ``Kpop[member[g]]`` and ``beta[member[g]]`` (host arrays ``member`` int32, ``beta`` complex); ``fr`` and,
+        when given, the rows ``jc`` (lanes, n_stiff) are written per lane."""
+        m, mp = _i32(member)
+        if m.size < (int(freqs.numel()) + 63) // 64:
+            raise ValueError("population_sweep: one member index per 64 lanes")
+        b = np.ascontiguousarray(np.asarray(beta, dtype=np.complex128).reshape(-1))
+        check(lib().pfr_population_sweep(self._h, int(freqs.numel()), _ptr(freqs), mp, int(b.size), _ptr(Kpop),
+                                         b.view(np.float64).ctypes.data_as(_DP), _ptr(fr), _ptr(jc), _ptr(flags),
+                                         self._stream(freqs) if stream is None else stream), "pfr_population_sweep")
 
     # ---- InnerState-compatible
     def solve(self, data, data_stride, b, b_stride, x, transpose, batch, flags=None):

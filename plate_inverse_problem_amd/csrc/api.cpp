@@ -233,6 +233,20 @@ struct pfr_solver {
   hipGraph_t graph = nullptr;
   hipGraphExec_t gexec = nullptr;
   int64_t graph_launches = 0;           // sweeps replayed from the graph (pfr_sweep_graph_launches)
+  // population sweep (pfr_population_sweep): while one runs, pop holds the current chunk's group table, the members'
+  // beta and the stride of popK, the members' operators; every operator / rhs launch then takes its POP form.
+  // member == NULL (always, outside that call): the single-theta state K / beta_re / beta_im above.
+  pfr::PopArgs pop{};
+  const double2* popK = nullptr;
+  // host tables of pfr_combine_batch (slot 0) and pfr_population_sweep (slot 1) on their way to the device: a
+  // pinned staging block, its device copy and the event after the copy (waited for before the block is refilled)
+  struct Stage {
+    void* host = nullptr;
+    void* dev = nullptr;
+    size_t cap = 0;
+    hipEvent_t ev = nullptr;
+    bool busy = false;
+  } stage[2];
 
   void drop_graph() {
     if (gexec) (void)hipGraphExecDestroy(gexec);
@@ -243,6 +257,11 @@ struct pfr_solver {
   ~pfr_solver() {
     drop_graph();
     for (void* p : owned) (void)hipFree(p);
+    for (auto& g : stage) {
+      if (g.host) (void)hipHostFree(g.host);
+      if (g.dev) (void)hipFree(g.dev);
+      if (g.ev) (void)hipEventDestroy(g.ev);
+    }
     for (auto& c : tev) {
       for (auto& x : c.ev)
         if (x) (void)hipEventDestroy(x);
@@ -337,6 +356,35 @@ bool level_lds(const pfr_solver* s, int l) {
                          : s->fac_lds < 0 && s->level_maxns[l] >= 16 && wgs < s->fac_lds_wg);
 }
 
+// the operator the launches read: the members' during a population sweep
+const double2* op_K(const pfr_solver* s) { return s->pop.member ? s->popK : s->K; }
+const pfr::PopArgs* op_pop(const pfr_solver* s) { return s->pop.member ? &s->pop : nullptr; }
+
+// bytes of a host table to the device on stream st (stage slot `slot`); *dev: the device copy
+int stage_upload(pfr_solver* s, int slot, const void* src, size_t bytes, void** dev, hipStream_t st) {
+  auto& g = s->stage[slot];
+  if (g.busy) HIP_TRY(hipEventSynchronize(g.ev));   // the previous copy out of the staging block
+  g.busy = false;
+  if (bytes > g.cap) {
+    HIP_TRY(hipStreamSynchronize(st));              // the kernels reading the old device copy
+    if (g.host) (void)hipHostFree(g.host);
+    if (g.dev) (void)hipFree(g.dev);
+    g.host = g.dev = nullptr;
+    g.cap = 0;
+    const size_t cap = std::max<size_t>(4096, 2 * bytes);
+    HIP_TRY(hipHostMalloc(&g.host, cap));
+    HIP_TRY(hipMalloc(&g.dev, cap));
+    g.cap = cap;
+  }
+  if (!g.ev) HIP_TRY(hipEventCreateWithFlags(&g.ev, hipEventDisableTiming));
+  std::memcpy(g.host, src, bytes);
+  HIP_TRY(hipMemcpyAsync(g.dev, g.host, bytes, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipEventRecord(g.ev, st));
+  g.busy = true;
+  *dev = g.dev;
+  return PFR_OK;
+}
+
 int factor_all(pfr_solver* s, int mode, const double2* data, int64_t ds, int nvalid, hipStream_t st) {
   const int L = (int)s->level_ptr.size() - 1;
   const int ngroups = (int)(s->Fc / 64);
@@ -353,7 +401,7 @@ int factor_all(pfr_solver* s, int mode, const double2* data, int64_t ds, int nva
       if (kt) s->tev[s->n_tev].f0 = true;
       // the bottom level's leaf fronts in one pass (k_front0): A11, L21 and update block per frequency in registers
       pfr::launch_front0(s->P, s->d_f0_front, s->n_f0, s->f0_small, s->d_f0_ptr, s->d_f0_nz, ngroups, s->F, s->Fc,
-                         s->freqs, s->K, s->M, s->flags, st);
+                         s->freqs, op_K(s), s->M, s->flags, st, op_pop(s));
       for (int c = 1; c <= 5; ++c) mark(l, c);
       continue;
     }
@@ -374,8 +422,8 @@ int factor_all(pfr_solver* s, int mode, const double2* data, int64_t ds, int nva
     const int Wp = (int)std::max<int64_t>(
         1, s->sym ? std::min<int64_t>(fac_wmax, wfill) : std::min<int64_t>(s->level_W[l], wfill));
     pfr::launch_assemble(mode, s->d_asm + s->asm_ptr[l], s->asm_ptr[l + 1] - s->asm_ptr[l],
-                         s->d_asm_xp + s->asm_ptr[l] / 8, s->d_asm_x, ngroups, s->F, s->Fc, s->freqs, s->K, s->M,
-                         data, ds, nvalid, st);
+                         s->d_asm_xp + s->asm_ptr[l] / 8, s->d_asm_x, ngroups, s->F, s->Fc, s->freqs, op_K(s), s->M,
+                         data, ds, nvalid, st, op_pop(s));
     mark(l, 1);
     if (level_lds(s, l))
       pfr::launch_factor_lds(s->P, s->d_level_fronts + s->level_ptr[l], nf, s->level_maxns[l], s->F, s->Fc, s->flags, st);
@@ -386,8 +434,8 @@ int factor_all(pfr_solver* s, int mode, const double2* data, int64_t ds, int nva
     // the software-pipelined L21 prefix on the launches with few waves (symmetric analyses, operator form)
     const int64_t owaves = (int64_t)(s->item_ptr[l + 1] - s->item_ptr[l]) * ngroups;
     pfr::launch_offdiag(mode, s->P, s->d_items + s->item_ptr[l], s->item_ptr[l + 1] - s->item_ptr[l], s->d_orec,
-                        s->d_oxp + s->item_ptr[l], s->d_ox, ngroups, s->F, s->Fc, s->freqs, s->K, s->M, data, ds,
-                        nvalid, s->level_maxns[l], st, s->sym && owaves < s->off_pu_waves);
+                        s->d_oxp + s->item_ptr[l], s->d_ox, ngroups, s->F, s->Fc, s->freqs, op_K(s), s->M, data, ds,
+                        nvalid, s->level_maxns[l], st, s->sym && owaves < s->off_pu_waves, op_pop(s));
     mark(l, 3);
     pfr::launch_schur_blk(s->P, s->d_blocks + s->blk_ptr[l], s->blk_ptr[l + 1] - s->blk_ptr[l],
                           s->d_bg1 + (int64_t)s->blk_ptr[l] * 16 * 16, s->d_bgxp + s->blk_ptr[l], s->d_bgx, ngroups, s->F,
@@ -436,9 +484,10 @@ pfr::DirDesc dir_desc(const pfr_solver* s) {
   d.ce = s->d_ce;
   d.dptr = s->d_dptr;
   d.de = s->d_de;
-  d.K = s->K;
+  d.K = op_K(s);
   d.M = s->M;
   d.freqs = s->freqs;
+  d.pop = s->pop;
   return d;
 }
 
@@ -528,6 +577,7 @@ int fn_bottom_up(pfr_solver* s, int rhs_mode, const pfr::RhsDesc& rf, hipStream_
     rd[k].mass_sum = 0.0;
     rd[k].beta_re = 1.0;
     rd[k].beta_im = 0.0;
+    rd[k].pop = pfr::PopArgs();      // a_k is the same for every member
     rd[k].cslot = s->d_noslot;
   }
   for (int l = 0; l < L; ++l) {
@@ -609,7 +659,8 @@ void check_solution(pfr_solver* s, int which, int mode, int rhs, const pfr::RhsD
   d.idx = which == 0 ? s->d_ridx : s->d_cidx;
   d.nzs = which == 0 ? s->d_rnz : s->d_cnz;
   d.n = s->n;
-  d.K = s->K;
+  d.K = op_K(s);
+  d.pop = s->pop;
   d.M = s->M;
   d.freqs = s->freqs;
   d.data = data;
@@ -1208,9 +1259,11 @@ namespace {
 // a unit cotangent per frequency whose contraction stays per frequency -- the walk's kpart (or k_contract_q's, where
 // the walk has not formed it) finished by k_jac_finish into the rows of jc instead of k_reduce_q / k_contract_eg +
 // k_reduce into w.
+// pop != NULL (pfr_population_sweep): lane group g of the sweep belongs to pop->member[g] (a device table padded to
+// whole chunks); chunks start at multiples of Fc, so a chunk's table is member + q0 / 64.
 int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_t loss_type, const double* ref_dev,
                    double scale, double* fr_dev, double* loss_dev, double* w_dev, int32_t* flags_dev, hipStream_t st,
-                   bool fresh, double2* jc_dev = nullptr) {
+                   bool fresh, double2* jc_dev = nullptr, const pfr::PopArgs* pop = nullptr) {
   const bool reverse = loss_type != PFR_LOSS_NONE;
   const bool jac = jc_dev != nullptr;
   reset_timing(s);
@@ -1235,12 +1288,17 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
       pfr::launch_chunk_start(s->freqs, freqs_dev + q0, nv, Fc, s->flags, st);
     if (int rc0 = begin_chunk(s)) return rc0;
     record(s, 0, st);
+    if (pop) {
+      s->pop = *pop;
+      s->pop.member += q0 / 64;
+    }
     pfr::RhsDesc rd;
     rd.rhsP = s->rhsP;
     rd.beta_re = s->beta_re;
     rd.beta_im = s->beta_im;
     rd.mass_sum = s->mass_sum;
     rd.freqs = s->freqs;
+    rd.pop = s->pop;
     pfr::RhsDesc rf = rd;
     int rc;
     if (paired) {
@@ -1352,7 +1410,7 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
         want_f = false;
         if (scorr) pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st);
         pfr::launch_correct_finish(fa, s->fr0, s->cpart, pfr::residual_parts(s->n), Fc, nv, q0, fr_dev, s->loss_terms,
-                                   s->mscale, st, refine_adj ? s->gind : nullptr, scorr ? s->tq : nullptr, bsc);
+                                   s->mscale, st, refine_adj ? s->gind : nullptr, scorr ? s->tq : nullptr, bsc, op_pop(s));
       }
       if (refine_adj) {
         // the listed groups (largest first-order fr error estimates above the tolerance, at most REFINE_CAP):
@@ -1377,7 +1435,7 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
         check_solution(s, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st, s->XA, false, true, s->glist);
         if (scorr) pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st);
         pfr::launch_correct_finish(fa, s->fr0, s->cpart, pfr::residual_parts(s->n), Fc, nv, q0, fr_dev, s->loss_terms,
-                                   s->mscale, st, nullptr, scorr ? s->tq : nullptr, bsc);
+                                   s->mscale, st, nullptr, scorr ? s->tq : nullptr, bsc, op_pop(s));
       }
       const double2* msc = correct ? s->mscale : nullptr;
       if (jac) {
@@ -1500,6 +1558,62 @@ int pfr_jacobian_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, do
   HIP_TRY(hipSetDevice(s->device));
   return sweep_launches(s, nfreq, freqs_dev, pfr::LOSS_UNIT, nullptr, 1.0, fr_dev, nullptr, nullptr, flags_dev,
                         (hipStream_t)stream, false, reinterpret_cast<double2*>(jc_dev));
+}
+
+int pfr_combine_batch(pfr_solver* s, int32_t n_members, const double* coef, double* Kpop_dev, void* stream) {
+  if (!s || n_members <= 0 || !coef || !Kpop_dev) return fail(PFR_ERR_ARG, "bad combine batch arguments");
+  if (!s->stiff) return fail(PFR_ERR_STATE, "pfr_set_stiffness not called");
+  HIP_TRY(hipSetDevice(s->device));
+  hipStream_t st = (hipStream_t)stream;
+  void* d_coef = nullptr;
+  if (int rc = stage_upload(s, 0, coef, (size_t)n_members * s->n_stiff * 16, &d_coef, st)) return rc;
+  pfr::launch_combine_batch(s->stiff, s->n_stiff, s->nnz, static_cast<const double2*>(d_coef), n_members,
+                            reinterpret_cast<double2*>(Kpop_dev), st);
+  LAUNCH_TRY();
+  return PFR_OK;
+}
+
+int pfr_population_sweep(pfr_solver* s, int32_t nlane, const double* freqs_dev, const int32_t* member,
+                         int32_t n_members, const double* Kpop_dev, const double* beta, double* fr_dev,
+                         double* jc_dev, int32_t* flags_dev, void* stream) {
+  if (!s || nlane <= 0 || !freqs_dev || !member || n_members <= 0 || !Kpop_dev || !beta || !fr_dev)
+    return fail(PFR_ERR_ARG, "bad population sweep arguments");
+  if (nlane % 64 != 0) return fail(PFR_ERR_ARG, "population sweep: nlane must be a multiple of 64");
+  const int64_t ng = nlane / 64;
+  for (int64_t g = 0; g < ng; ++g)
+    if (member[g] < 0 || member[g] >= n_members) return fail(PFR_ERR_ARG, "population sweep: member index out of range");
+  // ranks the groups of a chunk against each other: a member's result would depend on its neighbours
+  if (s->check_mode & PFR_CHECK_REFINE_ADJ)
+    return fail(PFR_ERR_ARG, "population sweep: PFR_CHECK_REFINE_ADJ is not supported");
+  if (!s->M) return fail(PFR_ERR_STATE, "mass matrix not set (pfr_set_operator)");
+  if (!s->has_rhs) return fail(PFR_ERR_STATE, "rhs not set (pfr_set_rhs)");
+  if (!s->has_fn) return fail(PFR_ERR_STATE, "functional not set (pfr_set_functional)");
+  if (jc_dev && !s->stiff) return fail(PFR_ERR_STATE, "population jacobian sweep needs pfr_set_stiffness");
+  // never captured, and the loss sweeps' graph is not replayed past it (as pfr_jacobian_sweep)
+  s->drop_graph();
+  s->gkey_valid = false;
+  HIP_TRY(hipSetDevice(s->device));
+  hipStream_t st = (hipStream_t)stream;
+  // the group table padded to whole chunks (the lanes past nlane of a short last chunk run too, on repeated
+  // frequencies: their groups take the last member), then the members' beta, 16-byte aligned
+  const int64_t gc = s->Fc / 64, ngp = (ng + gc - 1) / gc * gc;
+  const size_t off_beta = (size_t)((ngp * 4 + 15) / 16 * 16);
+  std::vector<char> tab(off_beta + (size_t)n_members * 16, 0);
+  int32_t* tm = reinterpret_cast<int32_t*>(tab.data());
+  for (int64_t g = 0; g < ngp; ++g) tm[g] = member[std::min(g, ng - 1)];
+  std::memcpy(tab.data() + off_beta, beta, (size_t)n_members * 16);
+  void* d_tab = nullptr;
+  if (int rc = stage_upload(s, 1, tab.data(), tab.size(), &d_tab, st)) return rc;
+  pfr::PopArgs pa;
+  pa.member = static_cast<const int32_t*>(d_tab);
+  pa.beta = reinterpret_cast<const double2*>(static_cast<const char*>(d_tab) + off_beta);
+  pa.nnz = s->nnz;
+  s->popK = reinterpret_cast<const double2*>(Kpop_dev);
+  const int rc = sweep_launches(s, nlane, freqs_dev, jc_dev ? pfr::LOSS_UNIT : PFR_LOSS_NONE, nullptr, 1.0, fr_dev,
+                                nullptr, nullptr, flags_dev, st, false, reinterpret_cast<double2*>(jc_dev), &pa);
+  s->pop = pfr::PopArgs();
+  s->popK = nullptr;
+  return rc;
 }
 
 int pfr_stream_order(void* waiter, void* signaller) {

@@ -34,6 +34,14 @@ struct CoefPack {
   double im[COEF_MAX];
 };
 
+// Population sweep (pfr_population_sweep): the 64-lane group g of the chunk belongs to member[g]; its operator is
+// K + member[g] * nnz and its rhs scale beta[member[g]].  Read only by the kernels' POP instantiations.
+struct PopArgs {
+  const int32_t* member = nullptr;   // the chunk's group table (device, Fc / 64 entries)
+  const double2* beta = nullptr;     // per member (device)
+  int64_t nnz = 0;                   // stride of the members' K
+};
+
 // b = rhsP * (beta_re - omega^2 mass_sum + i beta_im) per frequency (the rhs of a sweep's solves)
 struct RhsScale {
   const double* freqs = nullptr;   // chunk-local frequencies [Hz]

@@ -95,6 +95,13 @@ __device__ __forceinline__ Ctx ctx() {
   return c;
 }
 
+// POP instantiations (the population sweep): the member owning the 64-lane group of frequency q, as a wave-uniform
+// value, so the K and beta loads based on it stay the scalar loads they are without POP (a wave of 16 or 32
+// frequencies lies inside one group)
+__device__ __forceinline__ int pop_member(const PopArgs& p, int64_t q) {
+  return p.member[__builtin_amdgcn_readfirstlane((int)(q >> 6))];
+}
+
 // ------------------------------------------------------------------ K1: combine
 // K[nz] = sum_k coef_k * stiff[nz * n_stiff + k]   (Problem.py:440-445, theta part)
 __global__ void k_combine(const double* __restrict__ stiff, int n_stiff, int64_t nnz, CoefPack coef,
@@ -110,9 +117,33 @@ __global__ void k_combine(const double* __restrict__ stiff, int n_stiff, int64_t
   K[nz] = make_double2(re, im);
 }
 
+// K[m * nnz + nz] = sum_k coef[m * NS + k] * stiff[nz * NS + k] for every member m: the stiffness row read once,
+// each member's sum in k_combine's fma order (bitwise k_combine's K for that member's coefficients)
+template <int NS>
+__global__ void k_combine_batch(const double* __restrict__ stiff, int64_t nnz, const cplx* __restrict__ coef,
+                                int n_members, cplx* __restrict__ K) {
+  int64_t nz = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (nz >= nnz) return;
+  double s[NS];
+#pragma unroll
+  for (int k = 0; k < NS; ++k) s[k] = stiff[nz * NS + k];
+  for (int m = 0; m < n_members; ++m) {
+    const cplx* c = coef + (int64_t)m * NS;
+    double re = 0, im = 0;
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+      re = fma(c[k].x, s[k], re);
+      im = fma(c[k].y, s[k], im);
+    }
+    K[(int64_t)m * nnz + nz] = make_double2(re, im);
+  }
+}
+
 // ------------------------------------------------------------------ K2a: assemble + panel
 // MODE 0: A_q = K - omega_q^2 M assembled on the fly (operator form).
 // MODE 1: A_q = data[q * data_stride + nz] (explicit batch, InnerState::solve data).
+// POP (with MODE 0, the population sweep): K based at the member of the workgroup's 64-lane group (pop_member);
+// the same arithmetic.
 // The front (f x f, row-major, frequency-minor) is assembled, then the first ns
 // pivots are eliminated with static diagonal pivots, restricted right-looking:
 // every block of KB pivots updates the pivot rows (all columns) and the panel
@@ -126,18 +157,19 @@ constexpr int JB = 4;     // columns per batched read-modify-write step
 // update-matrix entry landing there; the rare further child entries of the
 // chunk come from the overflow list.  All loads of a chunk are in flight
 // together; each panel entry is written exactly once.
-template <int MODE>
+template <int MODE, bool POP = false>
 __global__ __launch_bounds__(256) void k_assemble_level(const int4* __restrict__ recs, int nrec,
                                                          const int* __restrict__ xptr, const int2* __restrict__ xl,
                                                          cplx* __restrict__ F, int64_t Fc,
                                                          const double* __restrict__ freqs,
                                                          const cplx* __restrict__ K, const double* __restrict__ M,
                                                          const cplx* __restrict__ data, int64_t data_stride,
-                                                         int nvalid) {
+                                                         int nvalid, PopArgs pop) {
   const int lane = threadIdx.x & 63;
   const int chunk = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
   if (chunk * 8 >= nrec) return;
   const int64_t q = (int64_t)blockIdx.y * 64 + lane;
+  if (POP) K += pop_member(pop, q) * pop.nnz;
   double om2 = 0.0;
   if (MODE == 0) {
     const double om = 6.283185307179586 * freqs[q];
@@ -853,14 +885,15 @@ __device__ __forceinline__ void offdiag_item(const DevPattern& P, const int4* __
 }
 
 // XCD-aware order: a frequency group's items on one XCD, sharing its L2
-template <int MODE, bool SMALL, int PU = 2>
+template <int MODE, bool SMALL, int PU = 2, bool POP = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? 5 : 1))) void k_offdiag_level(
     DevPattern P, const int4* __restrict__ items, int nitems, const int2* __restrict__ orec, const int* __restrict__ oxp,
     const int2* __restrict__ ox, cplx* __restrict__ F, int64_t Fc, const double* __restrict__ freqs,
     const cplx* __restrict__ K, const double* __restrict__ M, const cplx* __restrict__ data, int64_t data_stride,
-    int nvalid) {
+    int nvalid, PopArgs pop) {
   const int64_t lid = xcd_swizzle(blockIdx.x + (int64_t)gridDim.x * blockIdx.y, (int64_t)gridDim.x * gridDim.y);
   const int bx = (int)(lid % gridDim.x), by = (int)(lid / gridDim.x);
+  if (POP) K += pop_member(pop, (int64_t)by * (64 / OFF_G)) * pop.nnz;   // the operator of the group's member
   const int wid = __builtin_amdgcn_readfirstlane(bx * (blockDim.x >> 6) + (threadIdx.x >> 6));
   if (wid < nitems)
     offdiag_item<MODE, SMALL, PU>(P, items, wid, orec, oxp, ox, F, Fc, freqs, K, M, data, data_stride, nvalid, by);
@@ -872,15 +905,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMALL ? 5 :
 // the panel's original entries (K - omega^2 M), the A11 LU (k_factor_sym's 4-pivot diagonal block), the L21 rows
 // (k_offdiag_level's column order) and the lower update block (k_schur_sym_level's pivot order), each stored once
 // and nothing read back.  Same operations in the same order as the four kernels: bit-for-bit the same factors.
-template <int NS>
+template <int NS, bool POP = false>
 __global__ __launch_bounds__(256) void k_front0(DevPattern P, const int* __restrict__ fl, int nfronts,
                                                 const int* __restrict__ fptr, const int* __restrict__ fnz,
                                                 cplx* __restrict__ F, int64_t Fc, const double* __restrict__ freqs,
                                                 const cplx* __restrict__ K, const double* __restrict__ M,
-                                                int* __restrict__ flags) {
+                                                int* __restrict__ flags, PopArgs pop) {
   static_assert(NS <= F0_NS && NS <= KB, "one diagonal block");
   int bx;
   const Ctx c = ctx_xcd(bx);
+  if (POP) K += pop_member(pop, c.q) * pop.nnz;   // the operator of the group's member
   const int slot = bx * 4 + c.w;
   if (slot >= nfronts) return;
   const Front fr = P.fronts[fl[slot]];
@@ -1309,6 +1343,15 @@ struct RhsArgs {
   const int* cslot;       // RHS 3: coupled-row slot of each permuted row (or -1)
   const cplx* Bc;         // RHS 3: Dirichlet corrections, slot-major (slot * Fc + q)
 };
+// RHS 4 / 5 (the population sweep): RHS 0 / 3 in kernels that first take beta_re / beta_im from the member of the
+// workgroup's 64-lane group (pop_beta); the same arithmetic from there on
+constexpr bool rhs_op(int RHS) { return RHS == 0 || RHS == 3 || RHS == 4 || RHS == 5; }
+constexpr bool rhs_cpl(int RHS) { return RHS == 3 || RHS == 5; }
+__device__ __forceinline__ void pop_beta(RhsArgs& R, const PopArgs& pop, int64_t q) {
+  const cplx beta = pop.beta[pop_member(pop, q)];
+  R.beta_re = beta.x;
+  R.beta_im = beta.y;
+}
 
 constexpr int MAX_SLICES = 4;
 struct LSlices {          // k_lsolve_level_z / k_lsolve_rows_z: one bottom-up solve per slice
@@ -1322,14 +1365,14 @@ struct LSlices {          // k_lsolve_level_z / k_lsolve_rows_z: one bottom-up s
 
 template <int RHS>
 __device__ __forceinline__ cplx rhs_value(const DevPattern& P, const RhsArgs& R, int p, int64_t q, int64_t Fc) {
-  if (RHS == 0 || RHS == 3) {
+  if (rhs_op(RHS)) {
     const double v = R.rhsP[p];
     cplx b = make_double2(0.0, 0.0);
     if (v != 0.0) {
       const double om = 6.283185307179586 * R.freqs[q];
       b = make_double2(v * fma(-om * om, R.mass_sum, R.beta_re), v * R.beta_im);
     }
-    if (RHS == 3) {
+    if (rhs_cpl(RHS)) {
       const int c = R.cslot[p];
       if (c >= 0) b = cadd(b, R.Bc[(int64_t)c * Fc + q]);
     }
@@ -1352,10 +1395,10 @@ constexpr int GATHER_CAP = 4096;    // child entries per front staged in LDS (mo
 template <int RHS>
 __device__ __forceinline__ cplx rhs_staged(const RhsArgs& R, int p, double rv, int cs, double om2, int64_t q,
                                            int64_t Fc) {
-  if (RHS == 0 || RHS == 3) {
+  if (rhs_op(RHS)) {
     cplx b = make_double2(0.0, 0.0);
     if (rv != 0.0) b = make_double2(rv * fma(-om2, R.mass_sum, R.beta_re), rv * R.beta_im);
-    if (RHS == 3 && cs >= 0) b = cadd(b, R.Bc[(int64_t)cs * Fc + q]);
+    if (rhs_cpl(RHS) && cs >= 0) b = cadd(b, R.Bc[(int64_t)cs * Fc + q]);
     return b;
   } else if (RHS == 1) {
     return R.B[min(q, (int64_t)R.nvalid - 1) * R.b_stride + p];    // p = perm[idx] here
@@ -1398,11 +1441,11 @@ __device__ __forceinline__ void gather_frontal(const DevPattern& P, const Front&
   for (int t = threadIdx.x; t < ns; t += blockDim.x) {
     const int p = P.idx[fr.row0 + t];
     s_p[t] = RHS == 1 ? P.perm[p] : p;
-    if (RHS == 0 || RHS == 3) s_rv[t] = R.rhsP[p];
-    if (RHS == 3) s_cs[t] = R.cslot[p];
+    if (rhs_op(RHS)) s_rv[t] = R.rhsP[p];
+    if (rhs_cpl(RHS)) s_cs[t] = R.cslot[p];
   }
   double om2 = 0.0;
-  if (RHS == 0 || RHS == 3) {
+  if (rhs_op(RHS)) {
     const double om = 6.283185307179586 * R.freqs[c.q];
     om2 = om * om;
   }
@@ -1601,10 +1644,11 @@ __device__ __forceinline__ void lsolve_front(const DevPattern& P, const Front& f
 template <int RHS>
 __global__ __launch_bounds__(512) void k_lsolve_level(DevPattern P, const int* __restrict__ lvl, const cplx* __restrict__ F, int64_t Fc,
                                cplx* __restrict__ WV, RhsArgs R, cplx* __restrict__ Y, const int* __restrict__ reach,
-                               int rows_split, const int* __restrict__ glist) {
+                               int rows_split, const int* __restrict__ glist, PopArgs pop) {
   int bx;
   Ctx c = ctx_xcd(bx);
   if (!pick_group(c, glist)) return;
+  if (RHS >= 4) pop_beta(R, pop, c.q);
   lsolve_front<RHS>(P, P.fronts[lvl[bx]], F, Fc, WV, R, Y, reach, rows_split, c);
 }
 
@@ -1616,12 +1660,19 @@ __global__ __launch_bounds__(512) void k_lsolve_level(DevPattern P, const int* _
 // Workgroups past a slice's front count return at once (the grid is sized for the largest slice).
 template <int RHS, bool NAR = false>
 __global__ __launch_bounds__(512) void k_lsolve_level_z(DevPattern P, LSlices S, const cplx* __restrict__ F, int64_t Fc,
-                                                        int rows_split) {
+                                                        int rows_split, PopArgs pop) {
   extern __shared__ cplx s_piv[];   // NAR: the pivot values (ns x 64)
   int bx;
   const Ctx c = ctx_xcd(bx);
   const int z = blockIdx.z;
   if (bx >= S.nf[z]) return;
+  if (RHS >= 4) {
+    // the population sweep: slice 0 (the operator rhs) with its group's member's beta; the functional's slices as they are
+    RhsArgs R = S.R[z];
+    if (z == 0) pop_beta(R, pop, c.q);
+    lsolve_front<RHS, NAR>(P, P.fronts[S.lvl[z][bx]], F, Fc, S.WV[z], R, S.Y[z], S.reach[z], rows_split, c, s_piv);
+    return;
+  }
   lsolve_front<RHS, NAR>(P, P.fronts[S.lvl[z][bx]], F, Fc, S.WV[z], S.R[z], S.Y[z], S.reach[z], rows_split, c, s_piv);
 }
 
@@ -2185,7 +2236,8 @@ __global__ __launch_bounds__(64 * RL_WMAX) void k_usolve2_rl(DevPattern P, const
 // lanes' registers, update rows into WV -- then tri_rl16's unit forward substitution, y to Y and to WV's pivot rows.
 // Grid (largest slice's fronts, Fc / 16, slices), 64 W threads with 4 W RPL >= the level's largest ns.
 template <int RHS, int RPL>
-__global__ __launch_bounds__(64 * RL_WMAX) void k_lsolve_rl_z(DevPattern P, LSlices S, const cplx* __restrict__ F, int64_t Fc) {
+__global__ __launch_bounds__(64 * RL_WMAX) void k_lsolve_rl_z(DevPattern P, LSlices S, const cplx* __restrict__ F, int64_t Fc,
+                                                                  PopArgs pop) {
   __shared__ cplx sx[2][1][RL_Q];
   __shared__ int s_ptr[MAX_FRONT + 1];
   __shared__ int s_src[GATHER_CAP];
@@ -2199,7 +2251,12 @@ __global__ __launch_bounds__(64 * RL_WMAX) void k_lsolve_rl_z(DevPattern P, LSli
   const int64_t q = (lid / gridDim.x) * RL_Q + (lane & (RL_Q - 1));
   const Front fr = P.fronts[S.lvl[z][bx]];
   const int f = fr.f, ns = fr.ns, slot = 4 * w + (lane >> 4), nsl = 4 * W;
-  const RhsArgs& R = S.R[z];
+  RhsArgs Rp;                 // RHS 4 / 5 (the population sweep): slice 0 with its group's member's beta
+  if (RHS >= 4) {
+    Rp = S.R[z];
+    if (z == 0) pop_beta(Rp, pop, q);
+  }
+  const RhsArgs& R = RHS >= 4 ? Rp : S.R[z];
   const int* __restrict__ reach = S.reach[z];
   cplx* __restrict__ WV = S.WV[z];
   // the frontal gather (gather_frontal's chains resolved into LDS by all threads; rows per lane slot, so the row
@@ -2217,7 +2274,7 @@ __global__ __launch_bounds__(64 * RL_WMAX) void k_lsolve_rl_z(DevPattern P, LSli
     const int p = P.idx[fr.row0 + t];
     s_p[t] = p;
     s_rv[t] = R.rhsP[p];
-    s_cs[t] = RHS == 3 ? R.cslot[p] : -1;
+    s_cs[t] = rhs_cpl(RHS) ? R.cslot[p] : -1;
   }
   const double om = 6.283185307179586 * R.freqs[q], om2 = om * om;
   __syncthreads();
@@ -2552,11 +2609,15 @@ __device__ __forceinline__ cplx cdiv(cplx a, cplx b) { return cmul(a, crecip(b))
 
 // SRC 0: b from the operator right-hand side (RHS 0), corrections into Bc (slot-major);
 // SRC 2: b = G (permuted, frequency-minor), corrected in place
-template <int SRC>
+template <int SRC, bool POP = false>
 __global__ __launch_bounds__(64) void k_dirichlet_rhs(DirArgs D, RhsArgs R, cplx* __restrict__ G,
-                                                      cplx* __restrict__ Bc, int64_t Fc) {
+                                                      cplx* __restrict__ Bc, int64_t Fc, PopArgs pop) {
   const int slot = blockIdx.x;
   const int64_t q = (int64_t)blockIdx.y * 64 + threadIdx.x;
+  if (POP) {   // the operator and the rhs scale of the group's member
+    D.K += pop_member(pop, q) * pop.nnz;
+    if (SRC == 0) pop_beta(R, pop, q);
+  }
   const double om = 6.283185307179586 * D.freqs[q];
   const double om2 = om * om;
   cplx v = make_double2(0.0, 0.0);
@@ -2581,12 +2642,14 @@ __global__ __launch_bounds__(64) void k_dirichlet_rhs(DirArgs D, RhsArgs R, cplx
   }
 }
 
+template <bool POP = false>
 __global__ __launch_bounds__(64) void k_dirichlet_post(DirArgs D, cplx* __restrict__ X, int64_t Fc,
-                                                        const int* __restrict__ glist) {
+                                                        const int* __restrict__ glist, PopArgs pop) {
   const int gy = glist ? glist[blockIdx.y] : (int)blockIdx.y;
   if (gy < 0) return;
   const int slot = blockIdx.x;
   const int64_t q = (int64_t)gy * 64 + threadIdx.x;
+  if (POP) D.K += pop_member(pop, q) * pop.nnz;
   const double om = 6.283185307179586 * D.freqs[q];
   const double om2 = om * om;
   const int2 d = D.dir[slot];
@@ -2719,10 +2782,11 @@ constexpr int RES_WPE = 4;   // the fused walk at 114 VGPRs with the compensated
 // both read the solve's own error, which a plain fp64 sum of the row's terms rounds away
 // RU: entries per batch of the row loop (all their gathers issued before the batch's products; the products in entry
 // order whatever RU, so every RU gives the same bits)
-template <int MODE, int RHS, bool DOT = false, int NSK = 0, bool CMP = DOT, int RU = 4>
+// POP (MODE 0, the population sweep): the operator and the rhs scale of the group's member; the same arithmetic
+template <int MODE, int RHS, bool DOT = false, int NSK = 0, bool CMP = DOT, int RU = 4, bool POP = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NSK > 0 ? RES_WPE : 1))) void k_residual(ResidArgs A, const cplx* __restrict__ X, int64_t Fc,
                                                   cplx* __restrict__ R, double* __restrict__ acc,
-                                                  const cplx* __restrict__ Mu, cplx* __restrict__ cpart) {
+                                                  const cplx* __restrict__ Mu, cplx* __restrict__ cpart, PopArgs pop) {
   // XCD-aware order: the workgroups of one 64-frequency group run together on one XCD, so the
   // solution rows their window of rows gathers (~2 MB) stay in that XCD's L2 instead of every
   // XCD's L2 holding windows of eight groups
@@ -2732,6 +2796,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NSK > 0 ? R
   const int64_t q = (int64_t)by * 64 + (threadIdx.x & 63);
   const int wave0 = __builtin_amdgcn_readfirstlane(bx * (blockDim.x >> 6) + (threadIdx.x >> 6));
   const int nwaves = gridDim.x * (blockDim.x >> 6);
+  if (POP) {
+    const int m = pop_member(pop, q);
+    A.K += m * pop.nnz;
+    if (RHS == 0) {
+      const cplx beta = pop.beta[m];
+      A.beta_re = beta.x;
+      A.beta_im = beta.y;
+    }
+  }
   double om2 = 0.0;
   if (MODE == 0 || RHS == 0) {
     const double om = 6.283185307179586 * A.freqs[q];
@@ -2910,11 +2983,14 @@ __device__ __forceinline__ cplx loss_ref(const FunctionalArgs& A, int64_t q) {
 // over the sweep); fr = mu*^T A x* = mu*^T b, so mu^T A x = (1 + dx)(1 + dm) fr to first order, and
 // mu^T A x = mu^T b - mu^T r is two dot products the sweep has already formed (k_rhs_dot, the correction's
 // walk): dividing by it removes both factors with no further solve ("Gradient at full size")
+// POP (the population sweep): the rhs scale's beta from the member of the workgroup's group
+template <bool POP = false>
 __global__ __launch_bounds__(256) void k_correct_finish(FunctionalArgs A, const double* __restrict__ fr0,
                                                         const cplx* __restrict__ cpart, int nparts, int64_t Fc,
                                                         int nvalid, int64_t q_global0, double* __restrict__ fr_out,
                                                         double* __restrict__ loss_terms, cplx* __restrict__ mscale,
-                                                        double* __restrict__ gind, cplx* __restrict__ tq, RhsScale bsc) {
+                                                        double* __restrict__ gind, cplx* __restrict__ tq, RhsScale bsc,
+                                                        PopArgs pop) {
   // 4 waves per 64 frequencies: wave w sums the partials b = w, w + 4, ... (8 loads in flight), then
   // wave 0 adds the four in order -- a fixed summation order (deterministic)
   __shared__ cplx sd[4][64];
@@ -2946,6 +3022,11 @@ __global__ __launch_bounds__(256) void k_correct_finish(FunctionalArgs A, const 
     const cplx t0 = tq[q];
     if (valid) {
       const double om = 6.283185307179586 * bsc.freqs[q];
+      if (POP) {
+        const cplx beta = pop.beta[pop_member(pop, q)];
+        bsc.beta_re = beta.x;
+        bsc.beta_im = beta.y;
+      }
       const cplx bs = make_double2(fma(-om * om, bsc.mass_sum, bsc.beta_re), bsc.beta_im);
       const cplx bt = cmul(bs, t0);
       const cplx den = make_double2(bt.x - d.x, bt.y - d.y);        // mu^T A x
@@ -3526,6 +3607,13 @@ void launch_combine(const double* stiff, int n_stiff, int64_t nnz, const CoefPac
   LAUNCH(k_combine, dim3((unsigned)((nnz + 255) / 256)), dim3(256), st, stiff, n_stiff, nnz, coef, K);
 }
 
+void launch_combine_batch(const double* stiff, int n_stiff, int64_t nnz, const double2* coef, int n_members,
+                          double2* K, hipStream_t st) {
+  const dim3 g((unsigned)((nnz + 255) / 256)), b(256);
+  if (n_stiff == 12) LAUNCH(k_combine_batch<12>, g, b, st, stiff, nnz, coef, n_members, K);
+  else LAUNCH(k_combine_batch<18>, g, b, st, stiff, nnz, coef, n_members, K);
+}
+
 void launch_schur(bool sym, const DevPattern& P, const int4* tiles, int ntiles, const int* g1, const int* gxp,
                   const int2* gx, int ngroups, double2* F, int64_t Fc, hipStream_t st) {
   if (ntiles <= 0) return;
@@ -3543,11 +3631,14 @@ void launch_schur_blk(const DevPattern& P, const int4* blocks, int nblocks, cons
 
 void launch_assemble(int mode, const int4* recs, int nrec, const int* xptr, const int2* xl, int ngroups, double2* F,
                      int64_t Fc, const double* freqs, const double2* K, const double* M, const double2* data,
-                     int64_t ds, int nvalid, hipStream_t st) {
+                     int64_t ds, int nvalid, hipStream_t st, const PopArgs* pop) {
   if (nrec <= 0) return;
   dim3 g((nrec / 8 + 3) / 4, ngroups), b(256);
-  if (mode == 0) LAUNCH(k_assemble_level<0>, g, b, st, recs, nrec, xptr, xl, F, Fc, freqs, K, M, data, ds, nvalid);
-  else LAUNCH(k_assemble_level<1>, g, b, st, recs, nrec, xptr, xl, F, Fc, freqs, K, M, data, ds, nvalid);
+  const PopArgs pa = pop ? *pop : PopArgs();
+  if (mode == 0 && pop)
+    LAUNCH((k_assemble_level<0, true>), g, b, st, recs, nrec, xptr, xl, F, Fc, freqs, K, M, data, ds, nvalid, pa);
+  else if (mode == 0) LAUNCH(k_assemble_level<0>, g, b, st, recs, nrec, xptr, xl, F, Fc, freqs, K, M, data, ds, nvalid, pa);
+  else LAUNCH(k_assemble_level<1>, g, b, st, recs, nrec, xptr, xl, F, Fc, freqs, K, M, data, ds, nvalid, pa);
 }
 
 void launch_factor_lds(const DevPattern& P, const int* lvl, int nfronts, int maxns, double2* F, int64_t Fc, int* flags,
@@ -3574,23 +3665,40 @@ void launch_factor(bool sym, const DevPattern& P, const int* lvl, int nfronts, i
 
 void launch_front0(const DevPattern& P, const int* fl, int nfronts, int nsmall, const int* fptr, const int* fnz,
                    int ngroups, double2* F, int64_t Fc, const double* freqs, const double2* K, const double* M,
-                   int* flags, hipStream_t st) {
-  if (nsmall > 0)
-    LAUNCH((k_front0<2>), dim3((nsmall + 3) / 4, ngroups), dim3(256), st, P, fl, nsmall, fptr, fnz, F, Fc, freqs, K,
-           M, flags);
-  if (nfronts > nsmall)
-    LAUNCH((k_front0<F0_NS>), dim3((nfronts - nsmall + 3) / 4, ngroups), dim3(256), st, P, fl + nsmall,
-           nfronts - nsmall, fptr + nsmall, fnz, F, Fc, freqs, K, M, flags);
+                   int* flags, hipStream_t st, const PopArgs* pop) {
+  const PopArgs pa = pop ? *pop : PopArgs();
+#define F0(NS, PP, g, list, cnt, ptr) \
+  LAUNCH((k_front0<NS, PP>), g, dim3(256), st, P, list, cnt, ptr, fnz, F, Fc, freqs, K, M, flags, pa)
+  const dim3 gs((nsmall + 3) / 4, ngroups), gb((nfronts - nsmall + 3) / 4, ngroups);
+  if (nsmall > 0) {
+    if (pop) F0(2, true, gs, fl, nsmall, fptr);
+    else F0(2, false, gs, fl, nsmall, fptr);
+  }
+  if (nfronts > nsmall) {
+    if (pop) F0(F0_NS, true, gb, fl + nsmall, nfronts - nsmall, fptr + nsmall);
+    else F0(F0_NS, false, gb, fl + nsmall, nfronts - nsmall, fptr + nsmall);
+  }
+#undef F0
 }
 
 void launch_offdiag(int mode, const DevPattern& P, const int4* items, int nitems, const int2* orec, const int* oxp,
                     const int2* ox, int ngroups, double2* F, int64_t Fc, const double* freqs, const double2* K,
-                    const double* M, const double2* data, int64_t ds, int nvalid, int maxns, hipStream_t st, bool pipelined) {
+                    const double* M, const double2* data, int64_t ds, int nvalid, int maxns, hipStream_t st, bool pipelined,
+                    const PopArgs* pop) {
   if (nitems <= 0) return;
+  const PopArgs pa = pop ? *pop : PopArgs();
   const bool small = maxns <= 8;
   dim3 g((nitems + 3) / 4, ngroups * OFF_G), b(256);
   static_assert(OB >= 8, "the SMALL variant covers pivot blocks of up to 8");
-#define OL(MD, SM, PU) LAUNCH((k_offdiag_level<MD, SM, PU>), g, b, st, P, items, nitems, orec, oxp, ox, F, Fc, freqs, K, M, data, ds, nvalid)
+#define OL(MD, SM, PU)                                                                                              \
+  do {                                                                                                              \
+    if (MD == 0 && pop)                                                                                             \
+      LAUNCH((k_offdiag_level<MD, SM, PU, MD == 0>), g, b, st, P, items, nitems, orec, oxp, ox, F, Fc, freqs, K, M, \
+             data, ds, nvalid, pa);                                                                                 \
+    else                                                                                                            \
+      LAUNCH((k_offdiag_level<MD, SM, PU>), g, b, st, P, items, nitems, orec, oxp, ox, F, Fc, freqs, K, M, data,    \
+             ds, nvalid, pa);                                                                                       \
+  } while (0)
   // pipelined: the prefix loop with the next pivot's loads issued before the current pivot's products (the
   // narrow levels, where few waves are resident)
   if (mode == 0 && small) OL(0, true, 2);
@@ -3619,10 +3727,13 @@ void launch_solve(int which, int rhs_mode, bool sym, const DevPattern& P, const 
   RhsArgs R = make_rhs(rd);
   switch (which) {
     case 0:  // L solve (split > 1: the update rows by k_lsolve_rows over `split` workgroups per front)
-      if (rhs_mode == 0) LAUNCH(k_lsolve_level<0>, g, b, st, P, lvl, F, Fc, WV, R, Out, reach, rs, glist);
-      else if (rhs_mode == 1) LAUNCH(k_lsolve_level<1>, g, b, st, P, lvl, F, Fc, WV, R, Out, reach, rs, glist);
-      else if (rhs_mode == 2) LAUNCH(k_lsolve_level<2>, g, b, st, P, lvl, F, Fc, WV, R, Out, reach, rs, glist);
-      else LAUNCH(k_lsolve_level<3>, g, b, st, P, lvl, F, Fc, WV, R, Out, reach, rs, glist);
+      // a population sweep's operator right-hand side (rd.pop): RHS 4 / 5, the forms of 0 / 3 with the member's beta
+      if (rhs_mode == 0 && rd.pop.member) LAUNCH(k_lsolve_level<4>, g, b, st, P, lvl, F, Fc, WV, R, Out, reach, rs, glist, rd.pop);
+      else if (rhs_mode == 3 && rd.pop.member) LAUNCH(k_lsolve_level<5>, g, b, st, P, lvl, F, Fc, WV, R, Out, reach, rs, glist, rd.pop);
+      else if (rhs_mode == 0) LAUNCH(k_lsolve_level<0>, g, b, st, P, lvl, F, Fc, WV, R, Out, reach, rs, glist, rd.pop);
+      else if (rhs_mode == 1) LAUNCH(k_lsolve_level<1>, g, b, st, P, lvl, F, Fc, WV, R, Out, reach, rs, glist, rd.pop);
+      else if (rhs_mode == 2) LAUNCH(k_lsolve_level<2>, g, b, st, P, lvl, F, Fc, WV, R, Out, reach, rs, glist, rd.pop);
+      else LAUNCH(k_lsolve_level<3>, g, b, st, P, lvl, F, Fc, WV, R, Out, reach, rs, glist, rd.pop);
       if (rs) LAUNCH(k_lsolve_rows, gs, bs, st, P, lvl, F, Fc, WV, split, glist);
       break;
     case 1:  // U solve (split > 1: the pivot rows' update part first, by k_usolve_upd)
@@ -3660,12 +3771,18 @@ void launch_lsolve_multi(int rhs_mode, const DevPattern& P, int nslices, const i
   if (nmax <= 0) return;
   const dim3 g(nmax, ngroups, nslices), b(64 * W);
   const int rs = split > 1;
+  // a population sweep (slice 0's rhs carries the group table): RHS 4 / 5, the forms of 0 / 3 with the member's beta
+  const bool pop = rd[0].pop.member != nullptr;
   if (rl && maxns > 16 * RL_WMAX) rl = false;   // k_lsolve_rl_z: at most 4 rows per lane slot
   if (rs && nar && rl) {
     const int rpl = rl_rpl(maxns);
     const dim3 gq(nmax, (unsigned)(Fc / RL_Q), nslices), bq(64 * rl_waves(maxns));
-#define LRL(RH, RP) LAUNCH((k_lsolve_rl_z<RH, RP>), gq, bq, st, P, S, F, Fc)
-    if (rhs_mode == 0) {
+#define LRL(RH, RP) LAUNCH((k_lsolve_rl_z<RH, RP>), gq, bq, st, P, S, F, Fc, rd[0].pop)
+    if (pop && rhs_mode == 0) {
+      if (rpl == 1) LRL(4, 1); else if (rpl == 2) LRL(4, 2); else LRL(4, 4);
+    } else if (pop) {
+      if (rpl == 1) LRL(5, 1); else if (rpl == 2) LRL(5, 2); else LRL(5, 4);
+    } else if (rhs_mode == 0) {
       if (rpl == 1) LRL(0, 1); else if (rpl == 2) LRL(0, 2); else LRL(0, 4);
     } else {
       if (rpl == 1) LRL(3, 1); else if (rpl == 2) LRL(3, 2); else LRL(3, 4);
@@ -3674,17 +3791,23 @@ void launch_lsolve_multi(int rhs_mode, const DevPattern& P, int nslices, const i
   } else if (rs && nar) {
     static const bool attr =
         dyn_lds(reinterpret_cast<const void*>(&k_lsolve_level_z<0, true>), (int)LS_NAR_DYN_MAX, "k_lsolve_level_z<0,NAR>") &&
-        dyn_lds(reinterpret_cast<const void*>(&k_lsolve_level_z<3, true>), (int)LS_NAR_DYN_MAX, "k_lsolve_level_z<3,NAR>");
+        dyn_lds(reinterpret_cast<const void*>(&k_lsolve_level_z<3, true>), (int)LS_NAR_DYN_MAX, "k_lsolve_level_z<3,NAR>") &&
+        dyn_lds(reinterpret_cast<const void*>(&k_lsolve_level_z<4, true>), (int)LS_NAR_DYN_MAX, "k_lsolve_level_z<4,NAR>") &&
+        dyn_lds(reinterpret_cast<const void*>(&k_lsolve_level_z<5, true>), (int)LS_NAR_DYN_MAX, "k_lsolve_level_z<5,NAR>");
     if (!attr) {
       const char* none = nullptr;
       g_refused.compare_exchange_strong(none, "k_lsolve_level_z<NAR>");
       return;
     }
     const size_t lds = (size_t)maxns * 64 * 16;
-    if (rhs_mode == 0) LAUNCH_DYN((k_lsolve_level_z<0, true>), g, b, lds, st, P, S, F, Fc, rs);
-    else LAUNCH_DYN((k_lsolve_level_z<3, true>), g, b, lds, st, P, S, F, Fc, rs);
-  } else if (rhs_mode == 0) LAUNCH(k_lsolve_level_z<0>, g, b, st, P, S, F, Fc, rs);
-  else LAUNCH(k_lsolve_level_z<3>, g, b, st, P, S, F, Fc, rs);
+    if (pop && rhs_mode == 0) LAUNCH_DYN((k_lsolve_level_z<4, true>), g, b, lds, st, P, S, F, Fc, rs, rd[0].pop);
+    else if (pop) LAUNCH_DYN((k_lsolve_level_z<5, true>), g, b, lds, st, P, S, F, Fc, rs, rd[0].pop);
+    else if (rhs_mode == 0) LAUNCH_DYN((k_lsolve_level_z<0, true>), g, b, lds, st, P, S, F, Fc, rs, rd[0].pop);
+    else LAUNCH_DYN((k_lsolve_level_z<3, true>), g, b, lds, st, P, S, F, Fc, rs, rd[0].pop);
+  } else if (pop && rhs_mode == 0) LAUNCH(k_lsolve_level_z<4>, g, b, st, P, S, F, Fc, rs, rd[0].pop);
+  else if (pop) LAUNCH(k_lsolve_level_z<5>, g, b, st, P, S, F, Fc, rs, rd[0].pop);
+  else if (rhs_mode == 0) LAUNCH(k_lsolve_level_z<0>, g, b, st, P, S, F, Fc, rs, rd[0].pop);
+  else LAUNCH(k_lsolve_level_z<3>, g, b, st, P, S, F, Fc, rs, rd[0].pop);
   if (rs && nar) {
     const int RB = (std::max(1, maxf - 1) + LRC_SR - 1) / LRC_SR;
     LAUNCH(k_lsolve_rows_zc, dim3(nmax * RB, ngroups, nslices), dim3(64 * LRC_W), st, P, S, F, Fc, RB);
@@ -3765,31 +3888,50 @@ void launch_residual(int mode, int rhs, const ResidDesc& d, const double2* X, in
   a.B = d.B; a.b_stride = d.b_stride; a.perm = d.perm; a.G = d.G; a.walk = d.walk;
   a.se = d.se; a.kpart = d.kpart; a.glist = d.glist;
   const dim3 g((unsigned)residual_parts(d.n), (unsigned)(d.glist ? REFINE_CAP : Fc / 64)), b(256);
+  if (d.pop.member) {
+    // the population sweep: the POP twins of the operator-form instantiations below, chosen the same way
+#define RP(RH, DT, NK, CM, RU) LAUNCH((k_residual<0, RH, DT, NK, CM, RU, true>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop)
+    if (mode != 0) return;                               // explicit batches have no population form
+    if (rhs == 0 && Mu && d.kpart && d.n_stiff == 12) RP(0, true, 12, true, 4);
+    else if (rhs == 0 && Mu && d.kpart && d.n_stiff == 18) RP(0, true, 18, true, 4);
+    else if (rhs == 0 && Mu) RP(0, true, 0, true, 4);
+    else if (R && rhs == 0) RP(0, false, 0, true, 4);
+    else if (R) RP(2, false, 0, true, 4);
+    else if (rhs == 0) RP(0, false, 0, false, 4);
+    else if (d.unroll == 8) RP(2, false, 0, false, 8);
+    else RP(2, false, 0, false, 4);
+#undef RP
+    return;
+  }
   // unroll 8 on the forward walk with the contraction: 1.87 -> 1.94 ms per 2,048-frequency chunk (not taken)
   if (mode == 0 && rhs == 0 && Mu && d.kpart && d.n_stiff == 12)
-    LAUNCH((k_residual<0, 0, true, 12>), g, b, st, a, X, Fc, R, acc, Mu, cpart);
+    LAUNCH((k_residual<0, 0, true, 12>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
   else if (mode == 0 && rhs == 0 && Mu && d.kpart && d.n_stiff == 18)
-    LAUNCH((k_residual<0, 0, true, 18>), g, b, st, a, X, Fc, R, acc, Mu, cpart);
-  else if (mode == 0 && rhs == 0 && Mu) LAUNCH((k_residual<0, 0, true>), g, b, st, a, X, Fc, R, acc, Mu, cpart);
+    LAUNCH((k_residual<0, 0, true, 18>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
+  else if (mode == 0 && rhs == 0 && Mu) LAUNCH((k_residual<0, 0, true>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
   else if (R) {   // the refinement's residual: compensated
-    if (mode == 0 && rhs == 0) LAUNCH((k_residual<0, 0, false, 0, true>), g, b, st, a, X, Fc, R, acc, Mu, cpart);
-    else if (mode == 0) LAUNCH((k_residual<0, 2, false, 0, true>), g, b, st, a, X, Fc, R, acc, Mu, cpart);
-    else if (rhs == 1) LAUNCH((k_residual<1, 1, false, 0, true>), g, b, st, a, X, Fc, R, acc, Mu, cpart);
-    else LAUNCH((k_residual<1, 2, false, 0, true>), g, b, st, a, X, Fc, R, acc, Mu, cpart);
-  } else if (mode == 0 && rhs == 0) LAUNCH((k_residual<0, 0>), g, b, st, a, X, Fc, R, acc, Mu, cpart);
+    if (mode == 0 && rhs == 0) LAUNCH((k_residual<0, 0, false, 0, true>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
+    else if (mode == 0) LAUNCH((k_residual<0, 2, false, 0, true>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
+    else if (rhs == 1) LAUNCH((k_residual<1, 1, false, 0, true>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
+    else LAUNCH((k_residual<1, 2, false, 0, true>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
+  } else if (mode == 0 && rhs == 0) LAUNCH((k_residual<0, 0>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
   // the adjoint's check walk with 8 entries per gather batch: 757 -> 638 us per 2,048-frequency chunk
   // (gpurun_out/ru2_*)
-  else if (mode == 0 && d.unroll == 8) LAUNCH((k_residual<0, 2, false, 0, false, 8>), g, b, st, a, X, Fc, R, acc, Mu, cpart);
-  else if (mode == 0) LAUNCH((k_residual<0, 2>), g, b, st, a, X, Fc, R, acc, Mu, cpart);
-  else if (rhs == 1) LAUNCH((k_residual<1, 1>), g, b, st, a, X, Fc, R, acc, Mu, cpart);
-  else LAUNCH((k_residual<1, 2>), g, b, st, a, X, Fc, R, acc, Mu, cpart);
+  else if (mode == 0 && d.unroll == 8) LAUNCH((k_residual<0, 2, false, 0, false, 8>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
+  else if (mode == 0) LAUNCH((k_residual<0, 2>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
+  else if (rhs == 1) LAUNCH((k_residual<1, 1>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
+  else LAUNCH((k_residual<1, 2>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
 }
 
 void launch_correct_finish(const FunctionalArgs& A, const double* fr0, const double2* cpart, int nparts, int64_t Fc,
                            int nvalid, int64_t q0, double* fr_out, double* loss_terms, double2* mscale,
-                           hipStream_t st, double* gind, double2* tq, const RhsScale& bsc) {
-  LAUNCH(k_correct_finish, dim3((unsigned)(Fc / 64)), dim3(256), st, A, fr0, cpart, nparts, Fc, nvalid, q0,
-         fr_out, loss_terms, mscale, gind, tq, bsc);
+                           hipStream_t st, double* gind, double2* tq, const RhsScale& bsc, const PopArgs* pop) {
+  if (pop)
+    LAUNCH(k_correct_finish<true>, dim3((unsigned)(Fc / 64)), dim3(256), st, A, fr0, cpart, nparts, Fc, nvalid, q0,
+           fr_out, loss_terms, mscale, gind, tq, bsc, *pop);
+  else
+    LAUNCH(k_correct_finish<false>, dim3((unsigned)(Fc / 64)), dim3(256), st, A, fr0, cpart, nparts, Fc, nvalid, q0,
+           fr_out, loss_terms, mscale, gind, tq, bsc, PopArgs());
 }
 
 void launch_berr_finish(double* acc, int64_t Fc, int nvalid, double tol, int flag, int* flags, double* berr_out,
@@ -3889,13 +4031,17 @@ void launch_dirichlet_rhs(int src, const DirDesc& d, int n_crow, const RhsDesc& 
                           int64_t Fc, hipStream_t st) {
   if (n_crow <= 0) return;
   dim3 g(n_crow, (unsigned)(Fc / 64)), b(64);
-  if (src == 0) LAUNCH(k_dirichlet_rhs<0>, g, b, st, make_dir(d), make_rhs(rd), G, Bc, Fc);
-  else LAUNCH(k_dirichlet_rhs<2>, g, b, st, make_dir(d), make_rhs(rd), G, Bc, Fc);
+  if (d.pop.member && src == 0) LAUNCH((k_dirichlet_rhs<0, true>), g, b, st, make_dir(d), make_rhs(rd), G, Bc, Fc, d.pop);
+  else if (d.pop.member) LAUNCH((k_dirichlet_rhs<2, true>), g, b, st, make_dir(d), make_rhs(rd), G, Bc, Fc, d.pop);
+  else if (src == 0) LAUNCH(k_dirichlet_rhs<0>, g, b, st, make_dir(d), make_rhs(rd), G, Bc, Fc, d.pop);
+  else LAUNCH(k_dirichlet_rhs<2>, g, b, st, make_dir(d), make_rhs(rd), G, Bc, Fc, d.pop);
 }
 
 void launch_dirichlet_post(const DirDesc& d, int n_dir, double2* X, int64_t Fc, hipStream_t st, const int* glist) {
   if (n_dir <= 0) return;
-  LAUNCH(k_dirichlet_post, dim3(n_dir, (unsigned)(glist ? REFINE_CAP : Fc / 64)), dim3(64), st, make_dir(d), X, Fc, glist);
+  const dim3 g(n_dir, (unsigned)(glist ? REFINE_CAP : Fc / 64));
+  if (d.pop.member) LAUNCH(k_dirichlet_post<true>, g, dim3(64), st, make_dir(d), X, Fc, glist, d.pop);
+  else LAUNCH(k_dirichlet_post<false>, g, dim3(64), st, make_dir(d), X, Fc, glist, d.pop);
 }
 
 // fill padded frequency slots with the last valid frequency (keeps padded lanes well-posed)

@@ -15,6 +15,7 @@ struct RhsDesc {
   int nvalid = 1;                 // RHS 1: valid batch items of the chunk
   const int* cslot = nullptr;     // RHS 3: coupled-row slot per permuted row (symmetric mode)
   const double2* Bc = nullptr;    // RHS 3: Dirichlet corrections (slot-major)
+  PopArgs pop;                    // member != NULL (population sweep): RHS 0 / 3 with the group's member's beta
 };
 
 // Dirichlet decoupling lists of a symmetric-mode solver (device pointers) + operator
@@ -28,6 +29,7 @@ struct DirDesc {
   const double2* K = nullptr;
   const double* M = nullptr;
   const double* freqs = nullptr;
+  PopArgs pop;                    // member != NULL (population sweep): K and the rhs scale of the group's member
 };
 
 // the first launch configuration refused since the last call (a kernel's dynamic LDS size), NULL: none; the
@@ -35,9 +37,15 @@ struct DirDesc {
 const char* launch_refused();
 
 void launch_combine(const double* stiff, int n_stiff, int64_t nnz, const CoefPack& coef, double2* K, hipStream_t st);
+// K[m * nnz + nz] for n_members coefficient rows (coef: device, n_members x n_stiff; n_stiff 12 or 18), each
+// bitwise launch_combine's K
+void launch_combine_batch(const double* stiff, int n_stiff, int64_t nnz, const double2* coef, int n_members,
+                          double2* K, hipStream_t st);
+// pop != NULL (operator form, here and in launch_front0 / launch_offdiag): the population sweep, K = the members'
+// operators and every 64-lane group assembled from its member's
 void launch_assemble(int mode, const int4* recs, int nrec, const int* xptr, const int2* xl, int ngroups, double2* F,
                      int64_t Fc, const double* freqs, const double2* K, const double* M, const double2* data,
-                     int64_t ds, int nvalid, hipStream_t st);
+                     int64_t ds, int nvalid, hipStream_t st, const PopArgs* pop = nullptr);
 // G: lane groups per wave of the symmetric kernel (FAC_G, 4 or 8)
 void launch_factor(bool sym, const DevPattern& P, const int* lvl, int nfronts, int W, int ngroups, double2* F, int64_t Fc,
                    int* flags, hipStream_t st, int G = FAC_G);
@@ -50,11 +58,11 @@ void launch_factor_lds(const DevPattern& P, const int* lvl, int nfronts, int max
 // the bottom level fused (k_front0, Plan::fused0): fl = level-0 fronts, the first nsmall with <= 2 pivots
 void launch_front0(const DevPattern& P, const int* fl, int nfronts, int nsmall, const int* fptr, const int* fnz,
                    int ngroups, double2* F, int64_t Fc, const double* freqs, const double2* K, const double* M,
-                   int* flags, hipStream_t st);
+                   int* flags, hipStream_t st, const PopArgs* pop = nullptr);
 void launch_offdiag(int mode, const DevPattern& P, const int4* items, int nitems, const int2* orec, const int* oxp,
                     const int2* ox, int ngroups, double2* F, int64_t Fc, const double* freqs, const double2* K,
                     const double* M, const double2* data, int64_t ds, int nvalid, int maxns, hipStream_t st,
-                    bool pipelined = false);
+                    bool pipelined = false, const PopArgs* pop = nullptr);
 // Schur complement A22 -= L21 U12 for a level's tile list (TM x TN = 4 x 4 tiles)
 void launch_schur(bool sym, const DevPattern& P, const int4* tiles, int ntiles, const int* g1, const int* gxp,
                   const int2* gx, int ngroups, double2* F, int64_t Fc, hipStream_t st);
@@ -156,6 +164,7 @@ struct ResidDesc {
   double2* kpart = nullptr;
   const int* glist = nullptr;  // the groups to walk (REFINE_CAP, -1: none; NULL: every group)
   int unroll = 4;              // entries per gather batch of the adjoint check walk (4 or 8; the same bits)
+  PopArgs pop;                 // member != NULL (population sweep, mode 0): K and beta of the group's member
 };
 // Mu != NULL (mode 0, rhs 0): also the functional-correction dot products sum_p Mu_p r_p, one partial
 // per workgroup and frequency in cpart (residual_parts(n) x Fc), summed by launch_correct_finish
@@ -171,7 +180,8 @@ void launch_residual(int mode, int rhs, const ResidDesc& d, const double2* X, in
 void launch_correct_finish(const FunctionalArgs& A, const double* fr0, const double2* cpart, int nparts, int64_t Fc,
                            int nvalid, int64_t q0, double* fr_out, double* loss_terms, double2* mscale,
                            hipStream_t st, double* gind = nullptr, double2* tq = nullptr,
-                           const RhsScale& bsc = RhsScale());
+                           const RhsScale& bsc = RhsScale(),
+                           const PopArgs* pop = nullptr);   // population sweep: bsc's beta from the group's member
 // glist[0 .. REFINE_CAP): the groups with the largest indicators above tol, largest first, -1 past them
 void launch_select_groups(const double* gind, int ngroups, double tol, int* glist, hipStream_t st);
 // flags |= flag where acc[q] > tol (or not finite); acc cleared

@@ -90,7 +90,16 @@ def solve_inverse(prob, arg0, loss_type: str, optimizer: str, compression=(False
         def np_loss(x):
             return float(loss(torch.as_tensor(np.asarray(x, dtype=np.float64))))
         vg = opt.value_and_grad(loss)
-        if optimizer == 'de':
+        if optimizer == 'de' and opt_kwargs.pop('vectorized', False):
+            # a whole generation per call: scipy hands x (n_par, S), the population loss one sweep over S members
+            if distributed:
+                raise NotImplementedError('the population sweep is not distributed: use vectorized with '
+                                          'distributed=False')
+            pop_loss = prob.getPopulationLossFunction(ref_fr[0], ref_fr[1], loss_type, scaling)
+            opt_kwargs.setdefault('updating', 'deferred')
+            fn = lambda f, bounds, **kw: differential_evolution(                          # noqa: E731
+                lambda x: pop_loss(np.asarray(x, dtype=np.float64).T), bounds, vectorized=True, **kw)
+        elif optimizer == 'de':
             fn = lambda f, bounds, **kw: differential_evolution(np_loss, bounds, **kw)   # noqa: E731
         else:
             if use_constraints:
