@@ -233,11 +233,6 @@ struct pfr_solver {
   hipGraph_t graph = nullptr;
   hipGraphExec_t gexec = nullptr;
   int64_t graph_launches = 0;           // sweeps replayed from the graph (pfr_sweep_graph_launches)
-  // population sweep (pfr_population_sweep): while one runs, pop holds the current chunk's group table, the members'
-  // beta and the stride of popK, the members' operators; every operator / rhs launch then takes its POP form.
-  // member == NULL (always, outside that call): the single-theta state K / beta_re / beta_im above.
-  pfr::PopArgs pop{};
-  const double2* popK = nullptr;
   // host tables of pfr_combine_batch (slot 0) and pfr_population_sweep (slot 1) on their way to the device: a
   // pinned staging block, its device copy and the event after the copy (waited for before the block is refilled)
   struct Stage {
@@ -356,9 +351,42 @@ bool level_lds(const pfr_solver* s, int l) {
                          : s->fac_lds < 0 && s->level_maxns[l] >= 16 && wgs < s->fac_lds_wg);
 }
 
-// the operator the launches read: the members' during a population sweep
-const double2* op_K(const pfr_solver* s) { return s->pop.member ? s->popK : s->K; }
-const pfr::PopArgs* op_pop(const pfr_solver* s) { return s->pop.member ? &s->pop : nullptr; }
+// The operator and the operator right-hand side of the chunk starting at q0 (pfr::ChunkOp), built once per chunk and
+// passed to everything that launches on it: the solver's K and rhs scale, or in a population sweep (pop != NULL: the
+// sweep's group table, a device table padded to whole chunks; chunks start at multiples of Fc) the members'
+// operators popK and the chunk's part of the table
+pfr::ChunkOp chunk_op(const pfr_solver* s, const double2* popK = nullptr, const pfr::PopArgs* pop = nullptr,
+                      int64_t q0 = 0) {
+  pfr::ChunkOp op;
+  op.K = pop ? popK : s->K;
+  op.M = s->M;
+  op.freqs = s->freqs;
+  op.rhsP = s->rhsP;
+  op.beta_re = s->beta_re;
+  op.beta_im = s->beta_im;
+  op.mass_sum = s->mass_sum;
+  if (pop) {
+    op.pop = *pop;
+    op.pop.member += q0 / 64;
+  }
+  return op;
+}
+
+// kernel right-hand sides: the operator's (RHS 0) and a permuted vector (RHS 2)
+pfr::RhsArgs rhs_operator(const pfr::ChunkOp& op) {
+  pfr::RhsArgs r;
+  r.rhsP = op.rhsP;
+  r.beta_re = op.beta_re;
+  r.beta_im = op.beta_im;
+  r.mass_sum = op.mass_sum;
+  r.freqs = op.freqs;
+  return r;
+}
+pfr::RhsArgs rhs_vector(const double2* G) {
+  pfr::RhsArgs r;
+  r.G = G;
+  return r;
+}
 
 // bytes of a host table to the device on stream st (stage slot `slot`); *dev: the device copy
 int stage_upload(pfr_solver* s, int slot, const void* src, size_t bytes, void** dev, hipStream_t st) {
@@ -385,7 +413,8 @@ int stage_upload(pfr_solver* s, int slot, const void* src, size_t bytes, void** 
   return PFR_OK;
 }
 
-int factor_all(pfr_solver* s, int mode, const double2* data, int64_t ds, int nvalid, hipStream_t st) {
+int factor_all(pfr_solver* s, const pfr::ChunkOp& op, int mode, const double2* data, int64_t ds, int nvalid,
+               hipStream_t st) {
   const int L = (int)s->level_ptr.size() - 1;
   const int ngroups = (int)(s->Fc / 64);
   const bool kt = (s->timing & 2) && s->n_tev < (int)s->tev.size() && !s->tev[s->n_tev].kev.empty();
@@ -400,8 +429,8 @@ int factor_all(pfr_solver* s, int mode, const double2* data, int64_t ds, int nva
     if (l == 0 && s->fused0 && mode == 0) {
       if (kt) s->tev[s->n_tev].f0 = true;
       // the bottom level's leaf fronts in one pass (k_front0): A11, L21 and update block per frequency in registers
-      pfr::launch_front0(s->P, s->d_f0_front, s->n_f0, s->f0_small, s->d_f0_ptr, s->d_f0_nz, ngroups, s->F, s->Fc,
-                         s->freqs, op_K(s), s->M, s->flags, st, op_pop(s));
+      pfr::launch_front0(s->P, s->d_f0_front, s->n_f0, s->f0_small, s->d_f0_ptr, s->d_f0_nz, ngroups, s->F, s->Fc, op,
+                         s->flags, st);
       for (int c = 1; c <= 5; ++c) mark(l, c);
       continue;
     }
@@ -422,8 +451,7 @@ int factor_all(pfr_solver* s, int mode, const double2* data, int64_t ds, int nva
     const int Wp = (int)std::max<int64_t>(
         1, s->sym ? std::min<int64_t>(fac_wmax, wfill) : std::min<int64_t>(s->level_W[l], wfill));
     pfr::launch_assemble(mode, s->d_asm + s->asm_ptr[l], s->asm_ptr[l + 1] - s->asm_ptr[l],
-                         s->d_asm_xp + s->asm_ptr[l] / 8, s->d_asm_x, ngroups, s->F, s->Fc, s->freqs, op_K(s), s->M,
-                         data, ds, nvalid, st, op_pop(s));
+                         s->d_asm_xp + s->asm_ptr[l] / 8, s->d_asm_x, ngroups, s->F, s->Fc, op, data, ds, nvalid, st);
     mark(l, 1);
     if (level_lds(s, l))
       pfr::launch_factor_lds(s->P, s->d_level_fronts + s->level_ptr[l], nf, s->level_maxns[l], s->F, s->Fc, s->flags, st);
@@ -434,8 +462,8 @@ int factor_all(pfr_solver* s, int mode, const double2* data, int64_t ds, int nva
     // the software-pipelined L21 prefix on the launches with few waves (symmetric analyses, operator form)
     const int64_t owaves = (int64_t)(s->item_ptr[l + 1] - s->item_ptr[l]) * ngroups;
     pfr::launch_offdiag(mode, s->P, s->d_items + s->item_ptr[l], s->item_ptr[l + 1] - s->item_ptr[l], s->d_orec,
-                        s->d_oxp + s->item_ptr[l], s->d_ox, ngroups, s->F, s->Fc, s->freqs, op_K(s), s->M, data, ds,
-                        nvalid, s->level_maxns[l], st, s->sym && owaves < s->off_pu_waves, op_pop(s));
+                        s->d_oxp + s->item_ptr[l], s->d_ox, ngroups, s->F, s->Fc, op, data, ds, nvalid,
+                        s->level_maxns[l], st, s->sym && owaves < s->off_pu_waves);
     mark(l, 3);
     pfr::launch_schur_blk(s->P, s->d_blocks + s->blk_ptr[l], s->blk_ptr[l + 1] - s->blk_ptr[l],
                           s->d_bg1 + (int64_t)s->blk_ptr[l] * 16 * 16, s->d_bgxp + s->blk_ptr[l], s->d_bgx, ngroups, s->F,
@@ -453,8 +481,8 @@ int factor_all(pfr_solver* s, int mode, const double2* data, int64_t ds, int nva
 // which: 0 L, 1 U, 2 U^T, 3 L^T ; bottom-up for 0/2, top-down for 1/3
 // subset (0 forward rhs, 1 loss adjoint, -1 none): bottom-up passes visit only the reached
 // fronts; top-down passes treat the pivot values of unreached fronts as zero
-int solve_all(pfr_solver* s, int which, int rhs_mode, const pfr::RhsDesc& rd, const double2* Yin, double2* Out,
-              hipStream_t st, int subset = -1, const int* glist = nullptr) {
+int solve_all(pfr_solver* s, const pfr::ChunkOp& op, int which, int rhs_mode, const pfr::RhsArgs& rd, const double2* Yin,
+              double2* Out, hipStream_t st, int subset = -1, const int* glist = nullptr) {
   const int L = (int)s->level_ptr.size() - 1;
   const int ngroups = glist ? pfr::REFINE_CAP : (int)(s->Fc / 64);
   const bool up = (which == 0 || which == 2);
@@ -469,62 +497,62 @@ int solve_all(pfr_solver* s, int which, int rhs_mode, const pfr::RhsDesc& rd, co
     }
     // the update parts split over several workgroups: L solves, and U solves in symmetric mode
     const int split = (which == 0 || (which == 1 && s->sym)) ? solve_split(s, nf) : 1;
-    pfr::launch_solve(which, rhs_mode, s->sym, s->P, lvl, nf, solve_W(s, l, nf), ngroups, s->F, s->Fc, s->WV, rd, Yin, Out,
-                      reach, st, split, glist);
+    pfr::launch_solve(which, rhs_mode, s->sym, s->P, lvl, nf, solve_W(s, l, nf), ngroups, s->F, s->Fc, s->WV, rd, op.pop,
+                      Yin, Out, reach, st, split, glist);
   }
   LAUNCH_TRY();
   return PFR_OK;
 }
 
-pfr::DirDesc dir_desc(const pfr_solver* s) {
-  pfr::DirDesc d;
+pfr::DirArgs dir_desc(const pfr_solver* s, const pfr::ChunkOp& op) {
+  pfr::DirArgs d;
   d.dir = s->d_dir;
   d.crow = s->d_crow;
   d.cptr = s->d_cptr_dir;
   d.ce = s->d_ce;
   d.dptr = s->d_dptr;
   d.de = s->d_de;
-  d.K = op_K(s);
-  d.M = s->M;
-  d.freqs = s->freqs;
-  d.pop = s->pop;
+  d.K = op.K;
+  d.M = op.M;
+  d.freqs = op.freqs;
   return d;
 }
 
 // A x = b on the chunk's factors, x -> Out (permuted).  rhs_mode 0: operator right-hand side
 // (rd.rhsP ...); 2: vector rd.G (overwritten in symmetric mode).  Symmetric mode: Dirichlet
 // columns moved to the right-hand side first, then L and U = diag(U) L^T.
-int forward_solve(pfr_solver* s, int rhs_mode, pfr::RhsDesc rd, double2* Out, hipStream_t st, int subset = -1) {
+int forward_solve(pfr_solver* s, const pfr::ChunkOp& op, int rhs_mode, pfr::RhsArgs rd, double2* Out, hipStream_t st,
+                  int subset = -1) {
   int rc;
   if (s->sym) {
-    const pfr::DirDesc dd = dir_desc(s);
+    const pfr::DirArgs dd = dir_desc(s, op);
     if (rhs_mode == 0) {
-      pfr::launch_dirichlet_rhs(0, dd, s->n_crow, rd, nullptr, s->Bc, s->Fc, st);
+      pfr::launch_dirichlet_rhs(0, dd, op.pop, s->n_crow, rd, nullptr, s->Bc, s->Fc, st);
       rd.cslot = s->d_cslot;
       rd.Bc = s->Bc;
       if (s->n_crow > 0) rhs_mode = 3;
     } else {
-      pfr::launch_dirichlet_rhs(2, dd, s->n_crow, rd, const_cast<double2*>(rd.G), nullptr, s->Fc, st);
+      pfr::launch_dirichlet_rhs(2, dd, op.pop, s->n_crow, rd, const_cast<double2*>(rd.G), nullptr, s->Fc, st);
     }
   }
-  if ((rc = solve_all(s, 0, rhs_mode, rd, nullptr, s->Y, st, subset))) return rc;
-  return solve_all(s, 1, 0, rd, s->Y, Out, st, subset);
+  if ((rc = solve_all(s, op, 0, rhs_mode, rd, nullptr, s->Y, st, subset))) return rc;
+  return solve_all(s, op, 1, 0, rd, s->Y, Out, st, subset);
 }
 
 // A^T l = g (g = rg.G, permuted), l -> Out.  Symmetric mode: the decoupled matrix is symmetric,
 // so L and U = diag(U) L^T again, then the Dirichlet rows of l are corrected.
-int adjoint_solve(pfr_solver* s, const pfr::RhsDesc& rg, double2* Out, hipStream_t st, int subset = -1,
-                  const int* glist = nullptr) {
+int adjoint_solve(pfr_solver* s, const pfr::ChunkOp& op, const pfr::RhsArgs& rg, double2* Out, hipStream_t st,
+                  int subset = -1, const int* glist = nullptr) {
   int rc;
   if (s->sym) {
-    if ((rc = solve_all(s, 0, 2, rg, nullptr, s->Y, st, subset, glist)) ||
-        (rc = solve_all(s, 1, 0, rg, s->Y, Out, st, subset, glist)))
+    if ((rc = solve_all(s, op, 0, 2, rg, nullptr, s->Y, st, subset, glist)) ||
+        (rc = solve_all(s, op, 1, 0, rg, s->Y, Out, st, subset, glist)))
       return rc;
-    pfr::launch_dirichlet_post(dir_desc(s), s->n_dir, Out, s->Fc, st, glist);
+    pfr::launch_dirichlet_post(dir_desc(s, op), op.pop, s->n_dir, Out, s->Fc, st, glist);
     return PFR_OK;
   }
-  if ((rc = solve_all(s, 2, 2, rg, nullptr, s->Y, st, subset))) return rc;
-  return solve_all(s, 3, 0, rg, s->Y, Out, st, subset);
+  if ((rc = solve_all(s, op, 2, 2, rg, nullptr, s->Y, st, subset))) return rc;
+  return solve_all(s, op, 3, 0, rg, s->Y, Out, st, subset);
 }
 
 // Row lists and buffers of the functional-from-bottom-up path (allocated on first use, lists rebuilt
@@ -563,12 +591,12 @@ int fn_setup(pfr_solver* s) {
 
 // forward bottom-up over the rhs reach (slice 0) and L w_k = a_k over the support reach (slices 1-3),
 // one launch chain
-int fn_bottom_up(pfr_solver* s, int rhs_mode, const pfr::RhsDesc& rf, hipStream_t st) {
+int fn_bottom_up(pfr_solver* s, const pfr::ChunkOp& op, int rhs_mode, const pfr::RhsArgs& rf, hipStream_t st) {
   const int L = (int)s->level_ptr.size() - 1;
   const int ngroups = (int)(s->Fc / 64);
   int64_t total_rows = 0;
   for (size_t t = 0; t < s->front_f.size(); ++t) total_rows += s->front_f[t];
-  pfr::RhsDesc rd[4] = {rf, rf, rf, rf};
+  pfr::RhsArgs rd[4] = {rf, rf, rf, rf};
   double2* WV[4] = {s->WV, s->WVk, s->WVk + total_rows * s->Fc, s->WVk + 2 * total_rows * s->Fc};
   double2* Y[4] = {s->Y, s->Y2, s->YVk, s->YVk + (int64_t)s->n * s->Fc};
   const int* reach[4] = {s->d_reach[0], s->d_reach[1], s->d_reach[1], s->d_reach[1]};
@@ -577,7 +605,6 @@ int fn_bottom_up(pfr_solver* s, int rhs_mode, const pfr::RhsDesc& rf, hipStream_
     rd[k].mass_sum = 0.0;
     rd[k].beta_re = 1.0;
     rd[k].beta_im = 0.0;
-    rd[k].pop = pfr::PopArgs();      // a_k is the same for every member
     rd[k].cslot = s->d_noslot;
   }
   for (int l = 0; l < L; ++l) {
@@ -593,8 +620,8 @@ int fn_bottom_up(pfr_solver* s, int rhs_mode, const pfr::RhsDesc& rf, hipStream_
     if (nmax == 0) continue;
     const int nsum = nf[0] + 3 * nf[1];
     const bool nar = (int64_t)nsum * ngroups < s->us2_nar && pfr::ls_nar_fits(s->level_maxns[l]);
-    pfr::launch_lsolve_multi(rhs_mode, s->P, 4, lvl, nf, solve_W(s, l, nmax), ngroups, s->F, s->Fc, WV, rd, Y, reach,
-                             st, solve_split(s, nsum), nar, s->level_maxns[l], s->level_maxf[l], s->ls_rl != 0);
+    pfr::launch_lsolve_multi(rhs_mode, s->P, 4, lvl, nf, solve_W(s, l, nmax), ngroups, s->F, s->Fc, WV, rd, op.pop, Y,
+                             reach, st, solve_split(s, nsum), nar, s->level_maxns[l], s->level_maxf[l], s->ls_rl != 0);
   }
   LAUNCH_TRY();
   return PFR_OK;
@@ -604,13 +631,13 @@ int fn_bottom_up(pfr_solver* s, int rhs_mode, const pfr::RhsDesc& rf, hipStream_
 // support reaches only (they hold every support row), then -- once the loss cotangent is known
 // and its bottom-up pass (same fronts) done -- ONE top-down pass computes the adjoint on every
 // front and the forward solution on the rest, each factor value loaded once for both.
-int sym_top_down_support(pfr_solver* s, const pfr::RhsDesc& rd, hipStream_t st) {
+int sym_top_down_support(pfr_solver* s, hipStream_t st) {
   const int L = (int)s->level_ptr.size() - 1;
   const int ngroups = (int)(s->Fc / 64);
   for (int l = L - 1; l >= 0; --l) {
     const int nf = s->reach_ptr[1][l + 1] - s->reach_ptr[1][l];
     pfr::launch_solve(1, 0, true, s->P, s->d_reach_fronts[1] + s->reach_ptr[1][l], nf, solve_W(s, l, nf), ngroups, s->F,
-                      s->Fc, s->WV, rd, s->Y, s->X, s->d_reach[0], st, solve_split(s, nf));
+                      s->Fc, s->WV, pfr::RhsArgs(), pfr::PopArgs(), s->Y, s->X, s->d_reach[0], st, solve_split(s, nf));
   }
   LAUNCH_TRY();
   return PFR_OK;
@@ -648,21 +675,20 @@ int set_reach(pfr_solver* s, int which, const std::vector<int32_t>& prows) {
 
 // Backward error of the solution X (permuted, frequency-minor) of the original system (which = 0:
 // A x = b over the rows, 1: A^T l = g over the columns); mode 0 operator form, 1 explicit batch
-// (data, ds, nvalid); rhs as pfr::ResidDesc (0 operator, 1 explicit B, 2 vector G).  Sets the
+// (data, ds, nvalid); rhs as launch_residual (0 operator, 1 explicit B, 2 vector G).  Sets the
 // chunk's flags and the caller's berr slots (q0 < 0: no berr output).  R != NULL: only the residual
 // b - A x is written there (the refinement step), nothing is checked.
-void check_solution(pfr_solver* s, int which, int mode, int rhs, const pfr::RhsDesc& rd, const double2* data,
-                    int64_t ds, int nvalid, const double2* X, double2* R, int64_t q0, hipStream_t st,
+void check_solution(pfr_solver* s, const pfr::ChunkOp& op, int which, int mode, int rhs, const pfr::RhsArgs& rd,
+                    const double2* data, int64_t ds, int nvalid, const double2* X, double2* R, int64_t q0, hipStream_t st,
                     const double2* Mu = nullptr, bool check = true, bool contract = false, const int* glist = nullptr) {
-  pfr::ResidDesc d;
+  pfr::ResidArgs d;
   d.ptr = which == 0 ? s->d_rptr : s->d_cptr;
   d.idx = which == 0 ? s->d_ridx : s->d_cidx;
   d.nzs = which == 0 ? s->d_rnz : s->d_cnz;
   d.n = s->n;
-  d.K = op_K(s);
-  d.pop = s->pop;
-  d.M = s->M;
-  d.freqs = s->freqs;
+  d.K = op.K;
+  d.M = op.M;
+  d.freqs = op.freqs;
   d.data = data;
   d.data_stride = ds;
   d.nvalid = nvalid;
@@ -676,19 +702,19 @@ void check_solution(pfr_solver* s, int which, int mode, int rhs, const pfr::RhsD
   d.G = rd.G;
   d.walk = s->d_walk;
   d.glist = glist;
-  d.unroll = s->res_unroll;
-  if (contract) {
+  if (contract) {   // the gradient contraction fused into the forward walk: stiffness values nz-major, kpart out
     d.se = s->stiff;
-    d.n_stiff = s->n_stiff;
     d.kpart = s->kpart;
   }
+  const int n_stiff = contract ? s->n_stiff : 0;
   if (R) {   // refinement residual only: no maxima, no flags
-    pfr::launch_residual(mode, rhs, d, X, s->Fc, R, nullptr, st);
+    pfr::launch_residual(mode, rhs, d, n_stiff, s->res_unroll, op.pop, X, s->Fc, R, nullptr, st);
     return;
   }
   // Mu: the forward walk also accumulates the functional correction's dot products (s->cpart);
   // check = false: only those (no backward error)
-  pfr::launch_residual(mode, rhs, d, X, s->Fc, nullptr, check ? s->d_berr_acc : nullptr, st, Mu, Mu ? s->cpart : nullptr);
+  pfr::launch_residual(mode, rhs, d, n_stiff, s->res_unroll, op.pop, X, s->Fc, nullptr, check ? s->d_berr_acc : nullptr,
+                       st, Mu, Mu ? s->cpart : nullptr);
   if (!check) return;
   pfr::launch_berr_finish(s->d_berr_acc, s->Fc, nvalid, s->check_tol,
                           which == 0 ? PFR_FLAG_BACKWARD_ERROR : PFR_FLAG_BACKWARD_ERROR_ADJ, s->flags,
@@ -702,16 +728,6 @@ void contract_rows(pfr_solver* s, const double2* lam, const double2* x, int nv, 
 }
 
 }  // namespace
-
-namespace pfr {
-void launch_flags_merge(const int* chunk, int nvalid, int* out, hipStream_t st);
-// a chunk's frequencies (padded with the last) and its flags cleared, one kernel
-void launch_chunk_start(double* freqs, const double* src, int nvalid, int64_t Fc, int* flags, hipStream_t st,
-                        double* loss = nullptr, double* w = nullptr, int nw = 0, int* out_flags = nullptr,
-                        double* berr = nullptr, int nfreq = 0);
-// p[0 .. n) = 0 (complex entries)
-void launch_zero(double2* p, int64_t n, hipStream_t st);
-}
 
 extern "C" {
 
@@ -1259,11 +1275,12 @@ namespace {
 // a unit cotangent per frequency whose contraction stays per frequency -- the walk's kpart (or k_contract_q's, where
 // the walk has not formed it) finished by k_jac_finish into the rows of jc instead of k_reduce_q / k_contract_eg +
 // k_reduce into w.
-// pop != NULL (pfr_population_sweep): lane group g of the sweep belongs to pop->member[g] (a device table padded to
-// whole chunks); chunks start at multiples of Fc, so a chunk's table is member + q0 / 64.
+// pop != NULL (pfr_population_sweep): lane group g of the sweep belongs to pop->member[g] and reads the operator
+// popK + pop->member[g] * pop->nnz (chunk_op).
 int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_t loss_type, const double* ref_dev,
                    double scale, double* fr_dev, double* loss_dev, double* w_dev, int32_t* flags_dev, hipStream_t st,
-                   bool fresh, double2* jc_dev = nullptr, const pfr::PopArgs* pop = nullptr) {
+                   bool fresh, double2* jc_dev = nullptr, const double2* popK = nullptr,
+                   const pfr::PopArgs* pop = nullptr) {
   const bool reverse = loss_type != PFR_LOSS_NONE;
   const bool jac = jc_dev != nullptr;
   reset_timing(s);
@@ -1288,51 +1305,41 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
       pfr::launch_chunk_start(s->freqs, freqs_dev + q0, nv, Fc, s->flags, st);
     if (int rc0 = begin_chunk(s)) return rc0;
     record(s, 0, st);
-    if (pop) {
-      s->pop = *pop;
-      s->pop.member += q0 / 64;
-    }
-    pfr::RhsDesc rd;
-    rd.rhsP = s->rhsP;
-    rd.beta_re = s->beta_re;
-    rd.beta_im = s->beta_im;
-    rd.mass_sum = s->mass_sum;
-    rd.freqs = s->freqs;
-    rd.pop = s->pop;
-    pfr::RhsDesc rf = rd;
+    const pfr::ChunkOp op = chunk_op(s, popK, pop, q0);
+    const pfr::DirArgs dd = dir_desc(s, op);
+    const pfr::RhsArgs rd = rhs_operator(op);
+    pfr::RhsArgs rf = rd;
     int rc;
     if (paired) {
-      pfr::launch_dirichlet_rhs(0, dir_desc(s), s->n_crow, rd, nullptr, s->Bc, s->Fc, st);
+      pfr::launch_dirichlet_rhs(0, dd, op.pop, s->n_crow, rd, nullptr, s->Bc, s->Fc, st);
       rf.cslot = s->d_cslot;
       rf.Bc = s->Bc;
-      if ((rc = factor_all(s, 0, nullptr, 0, nv, st))) return rc;
+      if ((rc = factor_all(s, op, 0, nullptr, 0, nv, st))) return rc;
       record(s, 1, st);   // the forward bottom-up pass belongs to the solve phases (sptrsv_roofline)
       if (fn_fast) {
-        if ((rc = fn_bottom_up(s, s->n_crow > 0 ? 3 : 0, rf, st))) return rc;
-      } else if ((rc = solve_all(s, 0, s->n_crow > 0 ? 3 : 0, rf, nullptr, s->Y, st, 0))) {
+        if ((rc = fn_bottom_up(s, op, s->n_crow > 0 ? 3 : 0, rf, st))) return rc;
+      } else if ((rc = solve_all(s, op, 0, s->n_crow > 0 ? 3 : 0, rf, nullptr, s->Y, st, 0))) {
         return rc;
       }
     } else {
-      rc = factor_all(s, 0, nullptr, 0, nv, st);
+      rc = factor_all(s, op, 0, nullptr, 0, nv, st);
       if (rc) return rc;
       record(s, 1, st);
     }
     // symmetric mode with an adjoint: forward top-down only over the loss support's fronts, then one
     // combined top-down pass (sym_top_down_pair); otherwise the full forward solve first
     if (paired) {
-      if (!fn_fast && (rc = sym_top_down_support(s, rf, st))) return rc;
+      if (!fn_fast && (rc = sym_top_down_support(s, st))) return rc;
     } else {
-      if ((rc = forward_solve(s, 0, rd, s->X, st, 0))) return rc;
+      if ((rc = forward_solve(s, op, 0, rd, s->X, st, 0))) return rc;
       if (refine) {
         // one refinement step on the same factors: r = b - A x (into G), A d = r (into XA), x += d
-        check_solution(s, 0, 0, 0, rd, nullptr, 0, nv, s->X, s->G, q0, st);
-        pfr::RhsDesc rr;
-        rr.G = s->G;
-        if ((rc = forward_solve(s, 2, rr, s->XA, st))) return rc;
+        check_solution(s, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, s->G, q0, st);
+        if ((rc = forward_solve(s, op, 2, rhs_vector(s->G), s->XA, st))) return rc;
         pfr::launch_axpy_vec(s->X, s->XA, (int64_t)s->n * Fc, st);
       }
       if (!fwd_late && (s->check_mode & PFR_CHECK_FORWARD))
-        check_solution(s, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st);
+        check_solution(s, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st);
     }
     record(s, 2, st);
     pfr::FunctionalArgs fa = s->fn;
@@ -1356,13 +1363,12 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
     }
     record(s, 3, st);
     if (adj) {
-      pfr::RhsDesc rg;
-      rg.G = s->G;
+      const pfr::RhsArgs rg = rhs_vector(s->G);
       if (fn_fast) {
         double2* Yk[3] = {s->Y2, s->YVk, s->YVk + (int64_t)s->n * Fc};
         pfr::launch_fn_combine(s->d_sup_rows, s->n_sup_rows, s->fcoef, Yk, Fc, st);
         if ((rc = sym_top_down_pair(s, st, true))) return rc;
-        pfr::launch_dirichlet_post(dir_desc(s), s->n_dir, s->XA, s->Fc, st);
+        pfr::launch_dirichlet_post(dd, op.pop, s->n_dir, s->XA, s->Fc, st);
         if (correct) {
           // the correction fr(x) + Re(mu^T r) needs fr OF the solution x whose residual r is walked (the
           // dot product's fr has its own rounding error, which the correction does not see): fr0 from x
@@ -1371,16 +1377,14 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
           pfr::launch_functional(fs, s->X, Fc, nv, q0, nullptr, nullptr, nullptr, st);
         }
       } else if (paired) {
-        if ((rc = solve_all(s, 0, 2, rg, nullptr, s->Y2, st, 1)) || (rc = sym_top_down_pair(s, st))) return rc;
-        pfr::launch_dirichlet_post(dir_desc(s), s->n_dir, s->XA, s->Fc, st);
+        if ((rc = solve_all(s, op, 0, 2, rg, nullptr, s->Y2, st, 1)) || (rc = sym_top_down_pair(s, st))) return rc;
+        pfr::launch_dirichlet_post(dd, op.pop, s->n_dir, s->XA, s->Fc, st);
       } else {
-        if ((rc = adjoint_solve(s, rg, s->XA, st, 1))) return rc;
+        if ((rc = adjoint_solve(s, op, rg, s->XA, st, 1))) return rc;
         if (refine) {
           // l += A^{-T} (g - A^T l): residual into Y2, correction into XR
-          check_solution(s, 1, 0, 2, rg, nullptr, 0, nv, s->XA, s->Y2, q0, st);
-          pfr::RhsDesc rr;
-          rr.G = s->Y2;
-          if ((rc = adjoint_solve(s, rr, s->XR, st))) return rc;
+          check_solution(s, op, 1, 0, 2, rg, nullptr, 0, nv, s->XA, s->Y2, q0, st);
+          if ((rc = adjoint_solve(s, op, rhs_vector(s->Y2), s->XR, st))) return rc;
           pfr::launch_axpy_vec(s->XA, s->XR, (int64_t)s->n * Fc, st);
         }
       }
@@ -1398,19 +1402,14 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
       const bool refine_adj = reverse && correct && cwalk && fn_fast && (s->check_mode & PFR_CHECK_REFINE_ADJ);
       // the solve-error scale of the cotangent (k_correct_finish): t_q = mu^T rhsP in, m_q t_q out
       const bool scorr = reverse && correct && s->scale_corr;
-      pfr::RhsScale bsc;
-      bsc.freqs = s->freqs;
-      bsc.mass_sum = s->mass_sum;
-      bsc.beta_re = s->beta_re;
-      bsc.beta_im = s->beta_im;
       if (correct) {
         // the forward residual walk: backward error (when checked) + the correction's dot products,
         // then the corrected fr, its loss terms and the per-frequency cotangent scales
-        check_solution(s, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st, s->XA, want_f, cwalk);
+        check_solution(s, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st, s->XA, want_f, cwalk);
         want_f = false;
         if (scorr) pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st);
         pfr::launch_correct_finish(fa, s->fr0, s->cpart, pfr::residual_parts(s->n), Fc, nv, q0, fr_dev, s->loss_terms,
-                                   s->mscale, st, refine_adj ? s->gind : nullptr, scorr ? s->tq : nullptr, bsc, op_pop(s));
+                                   s->mscale, op, st, refine_adj ? s->gind : nullptr, scorr ? s->tq : nullptr);
       }
       if (refine_adj) {
         // the listed groups (largest first-order fr error estimates above the tolerance, at most REFINE_CAP):
@@ -1425,17 +1424,14 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
         pfr::FunctionalArgs fs = fa;
         fs.fr0 = s->fr0;
         pfr::launch_functional(fs, s->X, Fc, nv, q0, nullptr, nullptr, s->Gx, st);
-        pfr::RhsDesc rgx;
-        rgx.G = s->Gx;
-        check_solution(s, 1, 0, 2, rgx, nullptr, 0, nv, s->XA, s->XR, q0, st, nullptr, false, false, s->glist);
-        pfr::RhsDesc rr;
-        rr.G = s->XR;
-        if ((rc = adjoint_solve(s, rr, s->Y2, st, -1, s->glist))) return rc;
+        check_solution(s, op, 1, 0, 2, rhs_vector(s->Gx), nullptr, 0, nv, s->XA, s->XR, q0, st, nullptr, false, false,
+                       s->glist);
+        if ((rc = adjoint_solve(s, op, rhs_vector(s->XR), s->Y2, st, -1, s->glist))) return rc;
         pfr::launch_axpy_vec(s->XA, s->Y2, (int64_t)s->n * Fc, st, s->glist, Fc);
-        check_solution(s, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st, s->XA, false, true, s->glist);
+        check_solution(s, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st, s->XA, false, true, s->glist);
         if (scorr) pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st);
         pfr::launch_correct_finish(fa, s->fr0, s->cpart, pfr::residual_parts(s->n), Fc, nv, q0, fr_dev, s->loss_terms,
-                                   s->mscale, st, nullptr, scorr ? s->tq : nullptr, bsc, op_pop(s));
+                                   s->mscale, op, st, nullptr, scorr ? s->tq : nullptr);
       }
       const double2* msc = correct ? s->mscale : nullptr;
       if (jac) {
@@ -1446,8 +1442,8 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
       else if (reverse)
         pfr::launch_contract_eg(s->d_uent, s->n_uent, s->d_se, s->n_stiff, s->XA, s->X, Fc, nv, s->partial, st, msc);
       // the checks as row / column walks of the original pattern (k_residual)
-      if (want_f) check_solution(s, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st);
-      if (want_a) check_solution(s, 1, 0, 2, rg, nullptr, 0, nv, s->XA, nullptr, q0, st);
+      if (want_f) check_solution(s, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st);
+      if (want_a) check_solution(s, op, 1, 0, 2, rg, nullptr, 0, nv, s->XA, nullptr, q0, st);
       if (reverse) {
         if (!scorr) pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st, msc);
         if (jac)
@@ -1608,12 +1604,9 @@ int pfr_population_sweep(pfr_solver* s, int32_t nlane, const double* freqs_dev, 
   pa.member = static_cast<const int32_t*>(d_tab);
   pa.beta = reinterpret_cast<const double2*>(static_cast<const char*>(d_tab) + off_beta);
   pa.nnz = s->nnz;
-  s->popK = reinterpret_cast<const double2*>(Kpop_dev);
-  const int rc = sweep_launches(s, nlane, freqs_dev, jc_dev ? pfr::LOSS_UNIT : PFR_LOSS_NONE, nullptr, 1.0, fr_dev,
-                                nullptr, nullptr, flags_dev, st, false, reinterpret_cast<double2*>(jc_dev), &pa);
-  s->pop = pfr::PopArgs();
-  s->popK = nullptr;
-  return rc;
+  return sweep_launches(s, nlane, freqs_dev, jc_dev ? pfr::LOSS_UNIT : PFR_LOSS_NONE, nullptr, 1.0, fr_dev, nullptr,
+                        nullptr, flags_dev, st, false, reinterpret_cast<double2*>(jc_dev),
+                        reinterpret_cast<const double2*>(Kpop_dev), &pa);
 }
 
 int pfr_stream_order(void* waiter, void* signaller) {
@@ -1670,46 +1663,34 @@ int pfr_hessian_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int
   for (int64_t q0 = 0; q0 < nfreq; q0 += Fc) {
     const int nv = (int)std::min<int64_t>(Fc, nfreq - q0);
     pfr::launch_chunk_start(s->freqs, freqs_dev + q0, nv, Fc, s->flags, st);
-    if ((rc = factor_all(s, 0, nullptr, 0, nv, st))) return rc;
+    const pfr::ChunkOp op = chunk_op(s);
+    if ((rc = factor_all(s, op, 0, nullptr, 0, nv, st))) return rc;
     // forward solve, loss, adjoint, gradient partials (as pfr_sweep)
-    pfr::RhsDesc rd;
-    rd.rhsP = s->rhsP;
-    rd.beta_re = s->beta_re;
-    rd.beta_im = s->beta_im;
-    rd.mass_sum = s->mass_sum;
-    rd.freqs = s->freqs;
-    if ((rc = forward_solve(s, 0, rd, s->X, st, 0))) return rc;
+    const pfr::RhsArgs rd = rhs_operator(op);
+    if ((rc = forward_solve(s, op, 0, rd, s->X, st, 0))) return rc;
     pfr::FunctionalArgs fa = s->fn;
     fa.loss_type = loss_type;
     fa.ref = reinterpret_cast<const double2*>(ref_dev);
     fa.scale = scale;
     HIP_TRY(hipMemsetAsync(s->G, 0, (size_t)n * Fc * 16, st));
-    pfr::RhsDesc rg;
-    rg.G = s->G;
-    rg.rhsP = s->rhsP;
-    rg.freqs = s->freqs;
+    const pfr::RhsArgs rg = rhs_vector(s->G);
     if (s->check_mode & PFR_CHECK_CORRECT) {
       // as pfr_sweep: the adjoint of fr, the corrected fr's loss terms and cotangent scales, then
       // lambda = m_q mu in place -- loss and gradient equal the corrected loss sweep's
       pfr::FunctionalArgs fs = fa;
       fs.fr0 = s->fr0;
       pfr::launch_functional(fs, s->X, Fc, nv, q0, nullptr, nullptr, s->G, st);
-      if ((rc = adjoint_solve(s, rg, s->XA, st, 1))) return rc;
-      check_solution(s, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st, s->XA, false);
+      if ((rc = adjoint_solve(s, op, rg, s->XA, st, 1))) return rc;
+      check_solution(s, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st, s->XA, false);
       // the loss sweep's cotangent, solve-error scale included (k_correct_finish): its gradient is the loss sweep's
-      pfr::RhsScale bsc;
-      bsc.freqs = s->freqs;
-      bsc.mass_sum = s->mass_sum;
-      bsc.beta_re = s->beta_re;
-      bsc.beta_im = s->beta_im;
       if (s->scale_corr) pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st);
       pfr::launch_correct_finish(fa, s->fr0, s->cpart, pfr::residual_parts(s->n), Fc, nv, q0, nullptr, s->loss_terms,
-                                 s->mscale, st, nullptr, s->scale_corr ? s->tq : nullptr, bsc);
+                                 s->mscale, op, st, nullptr, s->scale_corr ? s->tq : nullptr);
       pfr::launch_scale_vec(s->XA, s->mscale, s->n, Fc, st);
       // the second-order seeds G (k_functional_tangent) are formed from fa, not the seed mode
     } else {
       pfr::launch_functional(fa, s->X, Fc, nv, q0, nullptr, s->loss_terms, s->G, st);
-      if ((rc = adjoint_solve(s, rg, s->XA, st, 1))) return rc;
+      if ((rc = adjoint_solve(s, op, rg, s->XA, st, 1))) return rc;
     }
     contract_rows(s, s->XA, s->X, nv, st);
     pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st);
@@ -1721,12 +1702,12 @@ int pfr_hessian_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int
     for (int i = 0; i < n_dir; ++i) {
       const double2* Kd = s->Kdir + (int64_t)i * s->nnz;
       pfr::launch_tangent_spmv(s->d_rptr, s->d_ridx, s->d_rnz, (int)n, Kd, s->X, Fc, s->rhsP, beta[i], s->G, 0, st);
-      if ((rc = forward_solve(s, 2, rg, s->DX, st))) return rc;
+      if ((rc = forward_solve(s, op, 2, rg, s->DX, st))) return rc;
       HIP_TRY(hipMemsetAsync(s->G, 0, (size_t)n * Fc * 16, st));
       pfr::launch_functional_tangent(fa, s->X, s->DX, Fc, nv, q0, s->G, st);
       pfr::launch_tangent_spmv(s->d_cptr, s->d_cidx, s->d_cnz, (int)n, Kd, s->XA, Fc, nullptr, make_double2(0, 0),
                                s->G, 1, st);
-      if ((rc = adjoint_solve(s, rg, s->DL, st))) return rc;
+      if ((rc = adjoint_solve(s, op, rg, s->DL, st))) return rc;
       contract_rows(s, s->DL, s->X, nv, st);
       pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->DL, Fc, s->tq, st);
       pfr::launch_reduce(s->partial, pfr::contract_eg_parts(s->n_uent), s->n_stiff, s->tq, s->e, s->loss_terms, nv, Fc,
@@ -1767,41 +1748,41 @@ int pfr_solve_multi(pfr_solver* s, int32_t batch, int32_t nrhs, const double* da
     if (int rc0 = begin_chunk(s)) return rc0;
     record(s, 0, st);
     // padded lanes repeat the last valid item (stride 0 broadcast handled by the kernel's clamp)
-    int rc = factor_all(s, 1, data + q0 * data_stride, data_stride, nv, st);
+    const pfr::ChunkOp op = chunk_op(s);   // explicit matrices: K and the rhs may be unset, none of it is read
+    int rc = factor_all(s, op, 1, data + q0 * data_stride, data_stride, nv, st);
     if (rc) return rc;
     record(s, 1, st);
     // every right-hand side of the chunk on the same factors (reference mode 4
     // refactorises per right-hand side, InnerState.h:289-305)
     for (int32_t r = 0; r < nrhs; ++r) {
-      pfr::RhsDesc rd;
+      pfr::RhsArgs rd;
       rd.B = B + r * b_rhs_stride + q0 * b_stride;
       rd.b_stride = b_stride;
       rd.nvalid = nv;
       if (!transpose) {
-        if ((rc = solve_all(s, 0, 1, rd, nullptr, s->Y, st))) return rc;
-        if ((rc = solve_all(s, 1, 1, rd, s->Y, s->X, st))) return rc;
+        if ((rc = solve_all(s, op, 0, 1, rd, nullptr, s->Y, st))) return rc;
+        if ((rc = solve_all(s, op, 1, 1, rd, s->Y, s->X, st))) return rc;
       }
       if (r == 0) {
         record(s, 2, st);
         record(s, 3, st);
       }
       if (transpose) {
-        if ((rc = solve_all(s, 2, 1, rd, nullptr, s->Y, st))) return rc;
-        if ((rc = solve_all(s, 3, 1, rd, s->Y, s->X, st))) return rc;
+        if ((rc = solve_all(s, op, 2, 1, rd, nullptr, s->Y, st))) return rc;
+        if ((rc = solve_all(s, op, 3, 1, rd, s->Y, s->X, st))) return rc;
       }
       const int which = transpose ? 1 : 0;
       const double2* dq = data + q0 * data_stride;
       if (s->check_mode & PFR_CHECK_REFINE) {
         // x += A^{-1} (b - A x) (or the transposed system) on the same factors
-        check_solution(s, which, 1, 1, rd, dq, data_stride, nv, s->X, s->G, r == 0 ? q0 : -1, st);
-        pfr::RhsDesc rr;
-        rr.G = s->G;
-        if ((rc = solve_all(s, transpose ? 2 : 0, 2, rr, nullptr, s->Y, st))) return rc;
-        if ((rc = solve_all(s, transpose ? 3 : 1, 0, rr, s->Y, s->XA, st))) return rc;
+        check_solution(s, op, which, 1, 1, rd, dq, data_stride, nv, s->X, s->G, r == 0 ? q0 : -1, st);
+        const pfr::RhsArgs rr = rhs_vector(s->G);
+        if ((rc = solve_all(s, op, transpose ? 2 : 0, 2, rr, nullptr, s->Y, st))) return rc;
+        if ((rc = solve_all(s, op, transpose ? 3 : 1, 0, rr, s->Y, s->XA, st))) return rc;
         pfr::launch_axpy_vec(s->X, s->XA, (int64_t)s->n * Fc, st);
       }
       if (s->check_mode & (transpose ? PFR_CHECK_ADJOINT : PFR_CHECK_FORWARD))
-        check_solution(s, which, 1, 1, rd, dq, data_stride, nv, s->X, nullptr, r == 0 ? q0 : -1, st);
+        check_solution(s, op, which, 1, 1, rd, dq, data_stride, nv, s->X, nullptr, r == 0 ? q0 : -1, st);
       pfr::launch_unpermute(s->P.perm, s->n, s->X, Fc, nv, Xo + r * x_rhs_stride + q0 * s->n, st);
     }
     record(s, 4, st);

@@ -48,6 +48,58 @@ struct RhsScale {
   double mass_sum = 0, beta_re = 0, beta_im = 0;
 };
 
+// Right-hand side of a solve, by the kernels' RHS template value (kernels.hip, "right-hand sides"); the host fills
+// the fields of the form it launches
+struct RhsArgs {
+  const double* rhsP = nullptr;   // RHS 0: permuted Dirichlet vector
+  double beta_re = 0, beta_im = 0, mass_sum = 0;
+  const double* freqs = nullptr;  // chunk frequencies (padded)
+  const double2* B = nullptr;     // RHS 1: explicit batch (batch-major, caller numbering)
+  int64_t b_stride = 0;
+  const double2* G = nullptr;     // RHS 2: permuted frequency-minor vector
+  int nvalid = 1;                 // RHS 1: padded lanes repeat the last valid item
+  const int* cslot = nullptr;     // RHS 3: coupled-row slot of each permuted row (or -1)
+  const double2* Bc = nullptr;    // RHS 3: Dirichlet corrections, slot-major (slot * Fc + q)
+};
+
+// Dirichlet decoupling lists of a symmetric-mode solver + the operator (kernels.hip, "Dirichlet decoupling")
+struct DirArgs {
+  const int2* dir = nullptr;      // per Dirichlet node: (permuted node, diagonal entry)
+  const int* crow = nullptr;      // coupled rows (permuted)
+  const int* cptr = nullptr;      // entry range of each coupled row in ce
+  const int2* ce = nullptr;       // (Dirichlet slot, entry)
+  const int* dptr = nullptr;      // entry range of each Dirichlet node in de
+  const int2* de = nullptr;       // (permuted row, entry)
+  const double2* K = nullptr;
+  const double* M = nullptr;
+  const double* freqs = nullptr;
+};
+
+// The residual walk (k_residual): the original system's rows or columns in the permuted numbering, the operator
+// (mode 0) or the explicit batch (mode 1), and the right-hand side (0 operator, 1 explicit B, 2 vector G)
+struct ResidArgs {
+  const int* ptr = nullptr;
+  const int* idx = nullptr;
+  const int* nzs = nullptr;
+  int n = 0;
+  const double2* K = nullptr;
+  const double* M = nullptr;
+  const double* freqs = nullptr;
+  const double2* data = nullptr;
+  int64_t data_stride = 0;
+  int nvalid = 1;
+  const double* rhsP = nullptr;
+  double beta_re = 0, beta_im = 0, mass_sum = 0;
+  const double2* B = nullptr;
+  int64_t b_stride = 0;
+  const int* perm = nullptr;
+  const double2* G = nullptr;
+  const int* walk = nullptr;      // rows in walk order (original numbering: mesh-local gathers of X)
+  const double* se = nullptr;     // NSK > 0: stiffness values, nz-major (se[nz * NSK + k])
+  double2* kpart = nullptr;       // NSK > 0: per (workgroup, k, frequency) sums of S_k(nz) mu_row x_col
+  const int* glist = nullptr;     // the groups to walk, indexed by grid row (REFINE_CAP, -1: none; NULL: grid row = group)
+};
+
 // internal loss id of pfr_jacobian_sweep: d L / d fr_q = 1 for every frequency, no reference (never accepted from
 // a caller of pfr_sweep)
 constexpr int LOSS_UNIT = PFR_LOSS_COTANGENT + 1;

@@ -21,6 +21,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <type_traits>
 
 #include "launch.hpp"
 
@@ -1332,21 +1333,11 @@ __global__ __launch_bounds__(64 * BC) void k_schur_sym_blk(DevPattern P, const i
 // RHS 2: b_p = G[p * Fc + q]                             (permuted device vector)
 // RHS 3: RHS 0 + Bc[cslot[p] * Fc + q]                   (symmetric mode: Dirichlet columns moved
 //        to the right-hand side, b_i - sum_d A_id b_d / A_dd, k_dirichlet_rhs)
-struct RhsArgs {
-  const double* rhsP;     // RHS 0: permuted Dirichlet vector
-  double beta_re, beta_im, mass_sum;
-  const double* freqs;
-  const cplx* B;          // RHS 1
-  int64_t b_stride;
-  const cplx* G;          // RHS 2
-  int nvalid;             // RHS 1: padded lanes repeat the last valid item
-  const int* cslot;       // RHS 3: coupled-row slot of each permuted row (or -1)
-  const cplx* Bc;         // RHS 3: Dirichlet corrections, slot-major (slot * Fc + q)
-};
-// RHS 4 / 5 (the population sweep): RHS 0 / 3 in kernels that first take beta_re / beta_im from the member of the
-// workgroup's 64-lane group (pop_beta); the same arithmetic from there on
-constexpr bool rhs_op(int RHS) { return RHS == 0 || RHS == 3 || RHS == 4 || RHS == 5; }
-constexpr bool rhs_cpl(int RHS) { return RHS == 3 || RHS == 5; }
+// (RhsArgs: device_types.hpp)
+constexpr bool rhs_op(int RHS) { return RHS == 0 || RHS == 3; }
+constexpr bool rhs_cpl(int RHS) { return RHS == 3; }
+// POP (the population sweep): the kernel first takes beta_re / beta_im from the member of the workgroup's 64-lane
+// group; the same arithmetic from there on
 __device__ __forceinline__ void pop_beta(RhsArgs& R, const PopArgs& pop, int64_t q) {
   const cplx beta = pop.beta[pop_member(pop, q)];
   R.beta_re = beta.x;
@@ -1641,14 +1632,14 @@ __device__ __forceinline__ void lsolve_front(const DevPattern& P, const Front& f
 #undef V
 }
 
-template <int RHS>
+template <int RHS, bool POP = false>
 __global__ __launch_bounds__(512) void k_lsolve_level(DevPattern P, const int* __restrict__ lvl, const cplx* __restrict__ F, int64_t Fc,
                                cplx* __restrict__ WV, RhsArgs R, cplx* __restrict__ Y, const int* __restrict__ reach,
                                int rows_split, const int* __restrict__ glist, PopArgs pop) {
   int bx;
   Ctx c = ctx_xcd(bx);
   if (!pick_group(c, glist)) return;
-  if (RHS >= 4) pop_beta(R, pop, c.q);
+  if (POP) pop_beta(R, pop, c.q);
   lsolve_front<RHS>(P, P.fronts[lvl[bx]], F, Fc, WV, R, Y, reach, rows_split, c);
 }
 
@@ -1658,7 +1649,7 @@ __global__ __launch_bounds__(512) void k_lsolve_level(DevPattern P, const int* _
 // that fr comes from  a_k^T x = (L^-1 a_k)^T diag(U)^-1 (L^-1 b)  without a top-down pass over the
 // support's fronts, and the adjoint's bottom-up result is a combination of the slices' (k_fn_combine).
 // Workgroups past a slice's front count return at once (the grid is sized for the largest slice).
-template <int RHS, bool NAR = false>
+template <int RHS, bool NAR = false, bool POP = false>
 __global__ __launch_bounds__(512) void k_lsolve_level_z(DevPattern P, LSlices S, const cplx* __restrict__ F, int64_t Fc,
                                                         int rows_split, PopArgs pop) {
   extern __shared__ cplx s_piv[];   // NAR: the pivot values (ns x 64)
@@ -1666,7 +1657,7 @@ __global__ __launch_bounds__(512) void k_lsolve_level_z(DevPattern P, LSlices S,
   const Ctx c = ctx_xcd(bx);
   const int z = blockIdx.z;
   if (bx >= S.nf[z]) return;
-  if (RHS >= 4) {
+  if (POP) {
     // the population sweep: slice 0 (the operator rhs) with its group's member's beta; the functional's slices as they are
     RhsArgs R = S.R[z];
     if (z == 0) pop_beta(R, pop, c.q);
@@ -2235,7 +2226,7 @@ __global__ __launch_bounds__(64 * RL_WMAX) void k_usolve2_rl(DevPattern P, const
 // k_lsolve_rows_zc): per (front, 16 frequencies, slice) the frontal vector gathered -- pivot rows into the owning
 // lanes' registers, update rows into WV -- then tri_rl16's unit forward substitution, y to Y and to WV's pivot rows.
 // Grid (largest slice's fronts, Fc / 16, slices), 64 W threads with 4 W RPL >= the level's largest ns.
-template <int RHS, int RPL>
+template <int RHS, int RPL, bool POP = false>
 __global__ __launch_bounds__(64 * RL_WMAX) void k_lsolve_rl_z(DevPattern P, LSlices S, const cplx* __restrict__ F, int64_t Fc,
                                                                   PopArgs pop) {
   __shared__ cplx sx[2][1][RL_Q];
@@ -2251,12 +2242,12 @@ __global__ __launch_bounds__(64 * RL_WMAX) void k_lsolve_rl_z(DevPattern P, LSli
   const int64_t q = (lid / gridDim.x) * RL_Q + (lane & (RL_Q - 1));
   const Front fr = P.fronts[S.lvl[z][bx]];
   const int f = fr.f, ns = fr.ns, slot = 4 * w + (lane >> 4), nsl = 4 * W;
-  RhsArgs Rp;                 // RHS 4 / 5 (the population sweep): slice 0 with its group's member's beta
-  if (RHS >= 4) {
+  RhsArgs Rp;                 // POP (the population sweep): slice 0 with its group's member's beta
+  if (POP) {
     Rp = S.R[z];
     if (z == 0) pop_beta(Rp, pop, q);
   }
-  const RhsArgs& R = RHS >= 4 ? Rp : S.R[z];
+  const RhsArgs& R = POP ? Rp : S.R[z];
   const int* __restrict__ reach = S.reach[z];
   cplx* __restrict__ WV = S.WV[z];
   // the frontal gather (gather_frontal's chains resolved into LDS by all threads; rows per lane slot, so the row
@@ -2588,18 +2579,6 @@ __global__ __launch_bounds__(512) void k_ltsolve_level(DevPattern P, const int* 
 //   forward  A x = b:       b_i -= sum_d A_id b_d / A_dd        (before the solve)
 //   adjoint  A^T l = g:     l_d -= sum_i A_id l_i / A_dd        (after the solve)
 // A = K - omega^2 M (operator form).  One wave per coupled row / Dirichlet node (64 frequencies).
-struct DirArgs {
-  const int2* dir;        // per Dirichlet node: (permuted node, diagonal entry)
-  const int* crow;        // coupled rows (permuted)
-  const int* cptr;        // entry range of each coupled row in ce
-  const int2* ce;         // (Dirichlet slot, entry)
-  const int* dptr;        // entry range of each Dirichlet node in de
-  const int2* de;         // (permuted row, entry)
-  const cplx* K;
-  const double* M;
-  const double* freqs;
-};
-
 __device__ __forceinline__ cplx op_entry(const DirArgs& D, int nz, double om2) {
   const cplx k = D.K[nz];
   return make_double2(fma(-om2, D.M[nz], k.x), k.y);
@@ -2713,29 +2692,6 @@ __global__ __launch_bounds__(256) void k_tangent_spmv(const int* __restrict__ pt
 // per wave into acc[q] by atomicMax on its bit pattern (non-negative doubles order like their
 // 64-bit patterns).  RHS: 0 = operator rhs (rhsP (beta - omega^2 mass_sum)), 1 = explicit batch B
 // (caller numbering, through perm), 2 = vector G (permuted).  R (may be NULL) receives r.
-struct ResidArgs {
-  const int* ptr;
-  const int* idx;
-  const int* nzs;
-  int n;
-  const cplx* K;
-  const double* M;
-  const double* freqs;
-  const cplx* data;
-  int64_t data_stride;
-  int nvalid;
-  const double* rhsP;
-  double beta_re, beta_im, mass_sum;
-  const cplx* B;
-  int64_t b_stride;
-  const int* perm;
-  const cplx* G;
-  const int* walk;   // rows in walk order (original numbering: mesh-local gathers of X)
-  const double* se;  // NSK > 0: stiffness values, nz-major (se[nz * NSK + k])
-  cplx* kpart;       // NSK > 0: per (workgroup, k, frequency) sums of S_k(nz) mu_row x_col
-  const int* glist;  // the groups to walk, indexed by grid row (-1: none; NULL: grid row = group)
-};
-
 __device__ __forceinline__ double cabs1(cplx z) { return fabs(z.x) + fabs(z.y); }
 
 // Compensated residual (the functional correction's walk): r = b - sum A x accumulated as an unevaluated sum
@@ -3596,12 +3552,33 @@ __global__ void k_matvec(const int* __restrict__ colptr, const int* __restrict__
 // this name (api.cpp LAUNCH_TRY), instead of a later generic launch error.
 static std::atomic<const char*> g_refused{nullptr};
 const char* launch_refused() { return g_refused.exchange(nullptr); }
-static bool dyn_lds(const void* fn, int bytes, const char* name) {
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess) return true;
+// ok, or the refusal recorded under `name` (a launcher whose static dyn_lds result is false: on every call)
+static bool dyn_ok(bool ok, const char* name) {
   const char* none = nullptr;
-  g_refused.compare_exchange_strong(none, name);
-  return false;
+  if (!ok) g_refused.compare_exchange_strong(none, name);
+  return ok;
 }
+static bool dyn_lds(const void* fn, int bytes, const char* name) {
+  return dyn_ok(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess, name);
+}
+
+// Runtime values as template arguments: dispatch(f, flag(b), pick<1, 2, 4>(v), ...) calls the generic lambda f with
+// one std::integral_constant per selector (CV(c): its value).  pick takes the V equal to v, the last V for any other
+// v (a ladder's final else).  A combination that is never launched is kept from being instantiated by an
+// `if constexpr` around the launch.
+template <class F> void with_bool(bool b, F&& f) { b ? f(std::true_type{}) : f(std::false_type{}); }
+template <int V, int... Vs, class F> void with_int(int v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V>{});
+  else if (v == V) f(std::integral_constant<int, V>{});
+  else with_int<Vs...>(v, f);
+}
+static auto flag(bool b) { return [b](auto&& g) { with_bool(b, g); }; }
+template <int... Vs> auto pick(int v) { return [v](auto&& g) { with_int<Vs...>(v, g); }; }
+template <class F> void dispatch(F&& f) { f(); }
+template <class F, class S, class... Ss> void dispatch(F&& f, S s, Ss... ss) {
+  s([&](auto c) { dispatch([&](auto... cs) { f(c, cs...); }, ss...); });
+}
+#define CV(c) decltype(c)::value
 
 void launch_combine(const double* stiff, int n_stiff, int64_t nnz, const CoefPack& coef, double2* K, hipStream_t st) {
   LAUNCH(k_combine, dim3((unsigned)((nnz + 255) / 256)), dim3(256), st, stiff, n_stiff, nnz, coef, K);
@@ -3609,9 +3586,9 @@ void launch_combine(const double* stiff, int n_stiff, int64_t nnz, const CoefPac
 
 void launch_combine_batch(const double* stiff, int n_stiff, int64_t nnz, const double2* coef, int n_members,
                           double2* K, hipStream_t st) {
-  const dim3 g((unsigned)((nnz + 255) / 256)), b(256);
-  if (n_stiff == 12) LAUNCH(k_combine_batch<12>, g, b, st, stiff, nnz, coef, n_members, K);
-  else LAUNCH(k_combine_batch<18>, g, b, st, stiff, nnz, coef, n_members, K);
+  with_int<12, 18>(n_stiff, [&](auto ns) {
+    LAUNCH(k_combine_batch<CV(ns)>, dim3((unsigned)((nnz + 255) / 256)), dim3(256), st, stiff, nnz, coef, n_members, K);
+  });
 }
 
 void launch_schur(bool sym, const DevPattern& P, const int4* tiles, int ntiles, const int* g1, const int* gxp,
@@ -3630,15 +3607,13 @@ void launch_schur_blk(const DevPattern& P, const int4* blocks, int nblocks, cons
 }
 
 void launch_assemble(int mode, const int4* recs, int nrec, const int* xptr, const int2* xl, int ngroups, double2* F,
-                     int64_t Fc, const double* freqs, const double2* K, const double* M, const double2* data,
-                     int64_t ds, int nvalid, hipStream_t st, const PopArgs* pop) {
+                     int64_t Fc, const ChunkOp& op, const double2* data, int64_t ds, int nvalid, hipStream_t st) {
   if (nrec <= 0) return;
-  dim3 g((nrec / 8 + 3) / 4, ngroups), b(256);
-  const PopArgs pa = pop ? *pop : PopArgs();
-  if (mode == 0 && pop)
-    LAUNCH((k_assemble_level<0, true>), g, b, st, recs, nrec, xptr, xl, F, Fc, freqs, K, M, data, ds, nvalid, pa);
-  else if (mode == 0) LAUNCH(k_assemble_level<0>, g, b, st, recs, nrec, xptr, xl, F, Fc, freqs, K, M, data, ds, nvalid, pa);
-  else LAUNCH(k_assemble_level<1>, g, b, st, recs, nrec, xptr, xl, F, Fc, freqs, K, M, data, ds, nvalid, pa);
+  dispatch([&](auto md, auto pop) {
+    if constexpr (CV(md) == 0 || !CV(pop))   // explicit batches have no population form
+      LAUNCH((k_assemble_level<CV(md), CV(pop)>), dim3((nrec / 8 + 3) / 4, ngroups), dim3(256), st, recs, nrec, xptr, xl,
+             F, Fc, op.freqs, op.K, op.M, data, ds, nvalid, op.pop);
+  }, pick<0, 1>(mode), flag(mode == 0 && op.pop.member));
 }
 
 void launch_factor_lds(const DevPattern& P, const int* lvl, int nfronts, int maxns, double2* F, int64_t Fc, int* flags,
@@ -3647,105 +3622,78 @@ void launch_factor_lds(const DevPattern& P, const int* lvl, int nfronts, int max
   static_assert(FAC_LB == 8, "fac_lds_bytes: 8 W columns per row");
   // dynamic LDS beyond the default 64 KiB (up to 64 pivots: 37 KiB; headroom)
   static const bool attr = dyn_lds(reinterpret_cast<const void*>(&k_factor_sym_lds), 160 * 1024, "k_factor_sym_lds");
-  if (!attr) {
-    const char* none = nullptr;
-    g_refused.compare_exchange_strong(none, "k_factor_sym_lds");
-    return;
-  }
+  if (!dyn_ok(attr, "k_factor_sym_lds")) return;
   LAUNCH_DYN(k_factor_sym_lds, dim3((unsigned)(nfronts * Fc)), dim3(256), lds, st, P, lvl, F, Fc, flags, maxns);
 }
 
 void launch_factor(bool sym, const DevPattern& P, const int* lvl, int nfronts, int W, int ngroups, double2* F,
                    int64_t Fc, int* flags, hipStream_t st, int G) {
-  if (sym && G == 8) LAUNCH(k_factor_sym<8>, dim3(nfronts, ngroups * 8), dim3(64 * W), st, P, lvl, F, Fc, flags);
-  else if (sym && G == 4) LAUNCH(k_factor_sym<4>, dim3(nfronts, ngroups * 4), dim3(64 * W), st, P, lvl, F, Fc, flags);
-  else if (sym) LAUNCH(k_factor_sym<FAC_G>, dim3(nfronts, ngroups * FAC_G), dim3(64 * W), st, P, lvl, F, Fc, flags);
-  else LAUNCH(k_factor_level<true>, dim3(nfronts, ngroups * FAC_G), dim3(64 * W), st, P, lvl, F, Fc, flags);
+  if (!sym) {
+    LAUNCH(k_factor_level<true>, dim3(nfronts, ngroups * FAC_G), dim3(64 * W), st, P, lvl, F, Fc, flags);
+    return;
+  }
+  with_int<8, 4, FAC_G>(G, [&](auto g) {
+    LAUNCH(k_factor_sym<CV(g)>, dim3(nfronts, ngroups * CV(g)), dim3(64 * W), st, P, lvl, F, Fc, flags);
+  });
 }
 
 void launch_front0(const DevPattern& P, const int* fl, int nfronts, int nsmall, const int* fptr, const int* fnz,
-                   int ngroups, double2* F, int64_t Fc, const double* freqs, const double2* K, const double* M,
-                   int* flags, hipStream_t st, const PopArgs* pop) {
-  const PopArgs pa = pop ? *pop : PopArgs();
-#define F0(NS, PP, g, list, cnt, ptr) \
-  LAUNCH((k_front0<NS, PP>), g, dim3(256), st, P, list, cnt, ptr, fnz, F, Fc, freqs, K, M, flags, pa)
-  const dim3 gs((nsmall + 3) / 4, ngroups), gb((nfronts - nsmall + 3) / 4, ngroups);
-  if (nsmall > 0) {
-    if (pop) F0(2, true, gs, fl, nsmall, fptr);
-    else F0(2, false, gs, fl, nsmall, fptr);
-  }
-  if (nfronts > nsmall) {
-    if (pop) F0(F0_NS, true, gb, fl + nsmall, nfronts - nsmall, fptr + nsmall);
-    else F0(F0_NS, false, gb, fl + nsmall, nfronts - nsmall, fptr + nsmall);
-  }
-#undef F0
+                   int ngroups, double2* F, int64_t Fc, const ChunkOp& op, int* flags, hipStream_t st) {
+  // the fronts [n0, n0 + cnt) of the list with NS pivot columns in registers
+  auto part = [&](auto ns, int n0, int cnt) {
+    if (cnt <= 0) return;
+    with_bool(op.pop.member != nullptr, [&](auto pop) {
+      LAUNCH((k_front0<CV(ns), CV(pop)>), dim3((cnt + 3) / 4, ngroups), dim3(256), st, P, fl + n0, cnt, fptr + n0, fnz, F,
+             Fc, op.freqs, op.K, op.M, flags, op.pop);
+    });
+  };
+  part(std::integral_constant<int, 2>{}, 0, nsmall);
+  part(std::integral_constant<int, F0_NS>{}, nsmall, nfronts - nsmall);
 }
 
 void launch_offdiag(int mode, const DevPattern& P, const int4* items, int nitems, const int2* orec, const int* oxp,
-                    const int2* ox, int ngroups, double2* F, int64_t Fc, const double* freqs, const double2* K,
-                    const double* M, const double2* data, int64_t ds, int nvalid, int maxns, hipStream_t st, bool pipelined,
-                    const PopArgs* pop) {
+                    const int2* ox, int ngroups, double2* F, int64_t Fc, const ChunkOp& op, const double2* data, int64_t ds,
+                    int nvalid, int maxns, hipStream_t st, bool pipelined) {
   if (nitems <= 0) return;
-  const PopArgs pa = pop ? *pop : PopArgs();
   const bool small = maxns <= 8;
-  dim3 g((nitems + 3) / 4, ngroups * OFF_G), b(256);
   static_assert(OB >= 8, "the SMALL variant covers pivot blocks of up to 8");
-#define OL(MD, SM, PU)                                                                                              \
-  do {                                                                                                              \
-    if (MD == 0 && pop)                                                                                             \
-      LAUNCH((k_offdiag_level<MD, SM, PU, MD == 0>), g, b, st, P, items, nitems, orec, oxp, ox, F, Fc, freqs, K, M, \
-             data, ds, nvalid, pa);                                                                                 \
-    else                                                                                                            \
-      LAUNCH((k_offdiag_level<MD, SM, PU>), g, b, st, P, items, nitems, orec, oxp, ox, F, Fc, freqs, K, M, data,    \
-             ds, nvalid, pa);                                                                                       \
-  } while (0)
   // pipelined: the prefix loop with the next pivot's loads issued before the current pivot's products (the
   // narrow levels, where few waves are resident)
-  if (mode == 0 && small) OL(0, true, 2);
-  else if (mode == 0 && pipelined) OL(0, false, 3);
-  else if (mode == 0) OL(0, false, 2);
-  else if (small) OL(1, true, 2);
-  else OL(1, false, 2);
-#undef OL
-}
-
-static RhsArgs make_rhs(const RhsDesc& d) {
-  RhsArgs r;
-  r.rhsP = d.rhsP; r.beta_re = d.beta_re; r.beta_im = d.beta_im; r.mass_sum = d.mass_sum;
-  r.freqs = d.freqs; r.B = d.B; r.b_stride = d.b_stride; r.G = d.G; r.nvalid = d.nvalid;
-  r.cslot = d.cslot; r.Bc = d.Bc;
-  return r;
+  dispatch([&](auto md, auto sm, auto pu, auto pop) {
+    if constexpr ((CV(pu) == 2 || (CV(md) == 0 && !CV(sm))) && (CV(md) == 0 || !CV(pop)))
+      LAUNCH((k_offdiag_level<CV(md), CV(sm), CV(pu), CV(pop)>), dim3((nitems + 3) / 4, ngroups * OFF_G), dim3(256), st, P,
+             items, nitems, orec, oxp, ox, F, Fc, op.freqs, op.K, op.M, data, ds, nvalid, op.pop);
+  }, pick<0, 1>(mode), flag(small), pick<2, 3>(mode == 0 && !small && pipelined ? 3 : 2),
+     flag(mode == 0 && op.pop.member));
 }
 
 void launch_solve(int which, int rhs_mode, bool sym, const DevPattern& P, const int* lvl, int nfronts, int W, int ngroups,
-                  const double2* F, int64_t Fc, double2* WV, const RhsDesc& rd, const double2* Yin, double2* Out,
-                  const int* reach, hipStream_t st, int split, const int* glist) {
+                  const double2* F, int64_t Fc, double2* WV, const RhsArgs& R, const PopArgs& pop, const double2* Yin,
+                  double2* Out, const int* reach, hipStream_t st, int split, const int* glist) {
   if (nfronts <= 0) return;
   dim3 g(nfronts, ngroups), b(64 * W);
   const dim3 gs(nfronts * split, ngroups), bs(64 * SPLIT_W);
   const int rs = split > 1;
-  RhsArgs R = make_rhs(rd);
   switch (which) {
     case 0:  // L solve (split > 1: the update rows by k_lsolve_rows over `split` workgroups per front)
-      // a population sweep's operator right-hand side (rd.pop): RHS 4 / 5, the forms of 0 / 3 with the member's beta
-      if (rhs_mode == 0 && rd.pop.member) LAUNCH(k_lsolve_level<4>, g, b, st, P, lvl, F, Fc, WV, R, Out, reach, rs, glist, rd.pop);
-      else if (rhs_mode == 3 && rd.pop.member) LAUNCH(k_lsolve_level<5>, g, b, st, P, lvl, F, Fc, WV, R, Out, reach, rs, glist, rd.pop);
-      else if (rhs_mode == 0) LAUNCH(k_lsolve_level<0>, g, b, st, P, lvl, F, Fc, WV, R, Out, reach, rs, glist, rd.pop);
-      else if (rhs_mode == 1) LAUNCH(k_lsolve_level<1>, g, b, st, P, lvl, F, Fc, WV, R, Out, reach, rs, glist, rd.pop);
-      else if (rhs_mode == 2) LAUNCH(k_lsolve_level<2>, g, b, st, P, lvl, F, Fc, WV, R, Out, reach, rs, glist, rd.pop);
-      else LAUNCH(k_lsolve_level<3>, g, b, st, P, lvl, F, Fc, WV, R, Out, reach, rs, glist, rd.pop);
+      // a population sweep's operator right-hand side (rhs_mode 0 / 3): the POP forms, with the member's beta
+      dispatch([&](auto rh, auto pp) {
+        if constexpr (rhs_op(CV(rh)) || !CV(pp))
+          LAUNCH((k_lsolve_level<CV(rh), CV(pp)>), g, b, st, P, lvl, F, Fc, WV, R, Out, reach, rs, glist,
+                 CV(pp) ? pop : PopArgs());
+      }, pick<0, 1, 2, 3>(rhs_mode), flag(pop.member && rhs_op(rhs_mode)));
       if (rs) LAUNCH(k_lsolve_rows, gs, bs, st, P, lvl, F, Fc, WV, split, glist);
       break;
     case 1:  // U solve (split > 1: the pivot rows' update part first, by k_usolve_upd)
-      if (rs && sym) LAUNCH(k_usolve_upd<true>, gs, bs, st, P, lvl, F, Fc, WV, Yin, Out, reach, split, glist);
-      else if (rs) LAUNCH(k_usolve_upd<false>, gs, bs, st, P, lvl, F, Fc, WV, Yin, Out, reach, split, glist);
-      if (sym) LAUNCH(k_usolve_level<true>, g, b, st, P, lvl, F, Fc, WV, Yin, Out, reach, rs, glist);
-      else LAUNCH(k_usolve_level<false>, g, b, st, P, lvl, F, Fc, WV, Yin, Out, reach, rs, glist);
+      with_bool(sym, [&](auto sy) {
+        if (rs) LAUNCH(k_usolve_upd<CV(sy)>, gs, bs, st, P, lvl, F, Fc, WV, Yin, Out, reach, split, glist);
+        LAUNCH(k_usolve_level<CV(sy)>, g, b, st, P, lvl, F, Fc, WV, Yin, Out, reach, rs, glist);
+      });
       break;
     case 2:  // U^T solve
-      if (rhs_mode == 0) LAUNCH(k_utsolve_level<0>, g, b, st, P, lvl, F, Fc, WV, R, Out, reach);
-      else if (rhs_mode == 1) LAUNCH(k_utsolve_level<1>, g, b, st, P, lvl, F, Fc, WV, R, Out, reach);
-      else LAUNCH(k_utsolve_level<2>, g, b, st, P, lvl, F, Fc, WV, R, Out, reach);
+      with_int<0, 1, 2>(rhs_mode, [&](auto rh) {
+        LAUNCH(k_utsolve_level<CV(rh)>, g, b, st, P, lvl, F, Fc, WV, R, Out, reach);
+      });
       break;
     default:  // L^T solve
       LAUNCH(k_ltsolve_level, g, b, st, P, lvl, F, Fc, WV, Yin, Out, reach);
@@ -3754,9 +3702,9 @@ void launch_solve(int which, int rhs_mode, bool sym, const DevPattern& P, const 
 }
 
 void launch_lsolve_multi(int rhs_mode, const DevPattern& P, int nslices, const int* const* lvl, const int* nf, int W,
-                         int ngroups, const double2* F, int64_t Fc, double2* const* WV, const RhsDesc* rd,
-                         double2* const* Y, const int* const* reach, hipStream_t st, int split, bool nar,
-                         int maxns, int maxf, bool rl) {
+                         int ngroups, const double2* F, int64_t Fc, double2* const* WV, const RhsArgs* rd,
+                         const PopArgs& pop, double2* const* Y, const int* const* reach, hipStream_t st, int split,
+                         bool nar, int maxns, int maxf, bool rl) {
   LSlices S{};
   int nmax = 0;
   for (int z = 0; z < nslices; ++z) {
@@ -3765,49 +3713,36 @@ void launch_lsolve_multi(int rhs_mode, const DevPattern& P, int nslices, const i
     S.WV[z] = WV[z];
     S.Y[z] = Y[z];
     S.reach[z] = reach[z];
-    S.R[z] = make_rhs(rd[z]);
+    S.R[z] = rd[z];
     nmax = std::max(nmax, nf[z]);
   }
   if (nmax <= 0) return;
   const dim3 g(nmax, ngroups, nslices), b(64 * W);
   const int rs = split > 1;
-  // a population sweep (slice 0's rhs carries the group table): RHS 4 / 5, the forms of 0 / 3 with the member's beta
-  const bool pop = rd[0].pop.member != nullptr;
   if (rl && maxns > 16 * RL_WMAX) rl = false;   // k_lsolve_rl_z: at most 4 rows per lane slot
-  if (rs && nar && rl) {
-    const int rpl = rl_rpl(maxns);
-    const dim3 gq(nmax, (unsigned)(Fc / RL_Q), nslices), bq(64 * rl_waves(maxns));
-#define LRL(RH, RP) LAUNCH((k_lsolve_rl_z<RH, RP>), gq, bq, st, P, S, F, Fc, rd[0].pop)
-    if (pop && rhs_mode == 0) {
-      if (rpl == 1) LRL(4, 1); else if (rpl == 2) LRL(4, 2); else LRL(4, 4);
-    } else if (pop) {
-      if (rpl == 1) LRL(5, 1); else if (rpl == 2) LRL(5, 2); else LRL(5, 4);
-    } else if (rhs_mode == 0) {
-      if (rpl == 1) LRL(0, 1); else if (rpl == 2) LRL(0, 2); else LRL(0, 4);
+  if (rs && nar && !rl) {
+    const auto raise = [](auto* k, const char* name) {
+      return dyn_lds(reinterpret_cast<const void*>(k), (int)LS_NAR_DYN_MAX, name);
+    };
+    static const bool attr = raise(&k_lsolve_level_z<0, true, false>, "k_lsolve_level_z<0,NAR>") &&
+                             raise(&k_lsolve_level_z<3, true, false>, "k_lsolve_level_z<3,NAR>") &&
+                             raise(&k_lsolve_level_z<0, true, true>, "k_lsolve_level_z<0,NAR,POP>") &&
+                             raise(&k_lsolve_level_z<3, true, true>, "k_lsolve_level_z<3,NAR,POP>");
+    if (!dyn_ok(attr, "k_lsolve_level_z<NAR>")) return;
+  }
+  // a population sweep (pop, the group table): the POP forms, slice 0's rhs with the member's beta
+  dispatch([&](auto rh, auto pp) {
+    if (rs && nar && rl) {
+      with_int<1, 2, 4>(rl_rpl(maxns), [&](auto rp) {
+        LAUNCH((k_lsolve_rl_z<CV(rh), CV(rp), CV(pp)>), dim3(nmax, (unsigned)(Fc / RL_Q), nslices),
+               dim3(64 * rl_waves(maxns)), st, P, S, F, Fc, pop);
+      });
+    } else if (rs && nar) {
+      LAUNCH_DYN((k_lsolve_level_z<CV(rh), true, CV(pp)>), g, b, (size_t)maxns * 64 * 16, st, P, S, F, Fc, rs, pop);
     } else {
-      if (rpl == 1) LRL(3, 1); else if (rpl == 2) LRL(3, 2); else LRL(3, 4);
+      LAUNCH((k_lsolve_level_z<CV(rh), false, CV(pp)>), g, b, st, P, S, F, Fc, rs, pop);
     }
-#undef LRL
-  } else if (rs && nar) {
-    static const bool attr =
-        dyn_lds(reinterpret_cast<const void*>(&k_lsolve_level_z<0, true>), (int)LS_NAR_DYN_MAX, "k_lsolve_level_z<0,NAR>") &&
-        dyn_lds(reinterpret_cast<const void*>(&k_lsolve_level_z<3, true>), (int)LS_NAR_DYN_MAX, "k_lsolve_level_z<3,NAR>") &&
-        dyn_lds(reinterpret_cast<const void*>(&k_lsolve_level_z<4, true>), (int)LS_NAR_DYN_MAX, "k_lsolve_level_z<4,NAR>") &&
-        dyn_lds(reinterpret_cast<const void*>(&k_lsolve_level_z<5, true>), (int)LS_NAR_DYN_MAX, "k_lsolve_level_z<5,NAR>");
-    if (!attr) {
-      const char* none = nullptr;
-      g_refused.compare_exchange_strong(none, "k_lsolve_level_z<NAR>");
-      return;
-    }
-    const size_t lds = (size_t)maxns * 64 * 16;
-    if (pop && rhs_mode == 0) LAUNCH_DYN((k_lsolve_level_z<4, true>), g, b, lds, st, P, S, F, Fc, rs, rd[0].pop);
-    else if (pop) LAUNCH_DYN((k_lsolve_level_z<5, true>), g, b, lds, st, P, S, F, Fc, rs, rd[0].pop);
-    else if (rhs_mode == 0) LAUNCH_DYN((k_lsolve_level_z<0, true>), g, b, lds, st, P, S, F, Fc, rs, rd[0].pop);
-    else LAUNCH_DYN((k_lsolve_level_z<3, true>), g, b, lds, st, P, S, F, Fc, rs, rd[0].pop);
-  } else if (pop && rhs_mode == 0) LAUNCH(k_lsolve_level_z<4>, g, b, st, P, S, F, Fc, rs, rd[0].pop);
-  else if (pop) LAUNCH(k_lsolve_level_z<5>, g, b, st, P, S, F, Fc, rs, rd[0].pop);
-  else if (rhs_mode == 0) LAUNCH(k_lsolve_level_z<0>, g, b, st, P, S, F, Fc, rs, rd[0].pop);
-  else LAUNCH(k_lsolve_level_z<3>, g, b, st, P, S, F, Fc, rs, rd[0].pop);
+  }, pick<0, 3>(rhs_mode), flag(pop.member != nullptr));
   if (rs && nar) {
     const int RB = (std::max(1, maxf - 1) + LRC_SR - 1) / LRC_SR;
     LAUNCH(k_lsolve_rows_zc, dim3(nmax * RB, ngroups, nslices), dim3(64 * LRC_W), st, P, S, F, Fc, RB);
@@ -3843,9 +3778,10 @@ void launch_usolve2(const DevPattern& P, const int* lvl, int nfronts, int W, boo
   UPair a{Y0, X0, reach0, skip0}, b{Y1, X1, reach1, nullptr};
   if (tiny > 0 && split <= 1) {
     // every pivot block of the level <= tiny (4 or 8): one wave per (front, group)
-    dim3 gt((unsigned)((nfronts + 3) / 4), ngroups), bt(256);
-    if (tiny <= 4) LAUNCH((k_usolve2_tiny<4>), gt, bt, st, P, lvl, nfronts, F, Fc, a, b);
-    else LAUNCH((k_usolve2_tiny<8>), gt, bt, st, P, lvl, nfronts, F, Fc, a, b);
+    with_int<4, 8>(tiny <= 4 ? 4 : 8, [&](auto t) {
+      LAUNCH((k_usolve2_tiny<CV(t)>), dim3((unsigned)((nfronts + 3) / 4), ngroups), dim3(256), st, P, lvl, nfronts, F, Fc,
+             a, b);
+    });
     return;
   }
   dim3 g(nfronts, ngroups), bl(64 * W);
@@ -3862,13 +3798,16 @@ void launch_usolve2(const DevPattern& P, const int* lvl, int nfronts, int W, boo
   // 8 pivot rows per pass share each gathered update-row value, 2 values per chunk, 3 waves/SIMD (18 % less traffic
   // than 2 rows x 4 values at 4 waves/SIMD, the same time: profiles/r04/solve_traffic/)
   if (rs && nar && rl) {
-    const int rpl = rl_rpl(maxns);
-    const dim3 gq(nfronts, (unsigned)(Fc / RL_Q)), bq(64 * rl_waves(maxns));
-    if (rpl == 1) LAUNCH((k_usolve2_rl<1>), gq, bq, st, P, lvl, F, Fc, a, b);
-    else if (rpl == 2) LAUNCH((k_usolve2_rl<2>), gq, bq, st, P, lvl, F, Fc, a, b);
-    else LAUNCH((k_usolve2_rl<4>), gq, bq, st, P, lvl, F, Fc, a, b);
-  } else if (small) LAUNCH((k_usolve2_level<true, 8, 2, 3>), g, bl, st, P, lvl, F, Fc, a, b, rs);
-  else LAUNCH((k_usolve2_level<true, 4, 8, 2>), g, bl, st, P, lvl, F, Fc, a, b, rs);
+    with_int<1, 2, 4>(rl_rpl(maxns), [&](auto rp) {
+      LAUNCH((k_usolve2_rl<CV(rp)>), dim3(nfronts, (unsigned)(Fc / RL_Q)), dim3(64 * rl_waves(maxns)), st, P, lvl, F, Fc,
+             a, b);
+    });
+  } else {
+    with_bool(small, [&](auto sm) {
+      constexpr bool S = CV(sm);
+      LAUNCH((k_usolve2_level<true, S ? 8 : 4, S ? 2 : 8, S ? 3 : 2>), g, bl, st, P, lvl, F, Fc, a, b, rs);
+    });
+  }
 }
 
 void launch_tangent_spmv(const int* ptr, const int* idx, const int* nzs, int nrows, const double2* Kd,
@@ -3879,59 +3818,42 @@ void launch_tangent_spmv(const int* ptr, const int* idx, const int* nzs, int nro
 }
 
 
-void launch_residual(int mode, int rhs, const ResidDesc& d, const double2* X, int64_t Fc, double2* R, double* acc,
-                     hipStream_t st, const double2* Mu, double2* cpart) {
-  ResidArgs a;
-  a.ptr = d.ptr; a.idx = d.idx; a.nzs = d.nzs; a.n = d.n;
-  a.K = d.K; a.M = d.M; a.freqs = d.freqs; a.data = d.data; a.data_stride = d.data_stride; a.nvalid = d.nvalid;
-  a.rhsP = d.rhsP; a.beta_re = d.beta_re; a.beta_im = d.beta_im; a.mass_sum = d.mass_sum;
-  a.B = d.B; a.b_stride = d.b_stride; a.perm = d.perm; a.G = d.G; a.walk = d.walk;
-  a.se = d.se; a.kpart = d.kpart; a.glist = d.glist;
-  const dim3 g((unsigned)residual_parts(d.n), (unsigned)(d.glist ? REFINE_CAP : Fc / 64)), b(256);
-  if (d.pop.member) {
-    // the population sweep: the POP twins of the operator-form instantiations below, chosen the same way
-#define RP(RH, DT, NK, CM, RU) LAUNCH((k_residual<0, RH, DT, NK, CM, RU, true>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop)
-    if (mode != 0) return;                               // explicit batches have no population form
-    if (rhs == 0 && Mu && d.kpart && d.n_stiff == 12) RP(0, true, 12, true, 4);
-    else if (rhs == 0 && Mu && d.kpart && d.n_stiff == 18) RP(0, true, 18, true, 4);
-    else if (rhs == 0 && Mu) RP(0, true, 0, true, 4);
-    else if (R && rhs == 0) RP(0, false, 0, true, 4);
-    else if (R) RP(2, false, 0, true, 4);
-    else if (rhs == 0) RP(0, false, 0, false, 4);
-    else if (d.unroll == 8) RP(2, false, 0, false, 8);
-    else RP(2, false, 0, false, 4);
-#undef RP
-    return;
-  }
+void launch_residual(int mode, int rhs, const ResidArgs& a, int n_stiff, int unroll, const PopArgs& pop, const double2* X,
+                     int64_t Fc, double2* R, double* acc, hipStream_t st, const double2* Mu, double2* cpart) {
+  if (pop.member && mode != 0) return;                   // explicit batches have no population form
+  // the variant: mode 0 walks rhs 0 or 2, mode 1 rhs 1 or 2
+  const int rh = mode == 0 ? (rhs == 0 ? 0 : 2) : (rhs == 1 ? 1 : 2);
+  const bool dot = mode == 0 && rhs == 0 && Mu;          // the correction walk; with kpart: + the contraction
   // unroll 8 on the forward walk with the contraction: 1.87 -> 1.94 ms per 2,048-frequency chunk (not taken)
-  if (mode == 0 && rhs == 0 && Mu && d.kpart && d.n_stiff == 12)
-    LAUNCH((k_residual<0, 0, true, 12>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
-  else if (mode == 0 && rhs == 0 && Mu && d.kpart && d.n_stiff == 18)
-    LAUNCH((k_residual<0, 0, true, 18>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
-  else if (mode == 0 && rhs == 0 && Mu) LAUNCH((k_residual<0, 0, true>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
-  else if (R) {   // the refinement's residual: compensated
-    if (mode == 0 && rhs == 0) LAUNCH((k_residual<0, 0, false, 0, true>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
-    else if (mode == 0) LAUNCH((k_residual<0, 2, false, 0, true>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
-    else if (rhs == 1) LAUNCH((k_residual<1, 1, false, 0, true>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
-    else LAUNCH((k_residual<1, 2, false, 0, true>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
-  } else if (mode == 0 && rhs == 0) LAUNCH((k_residual<0, 0>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
+  const int nsk = dot && a.kpart && (n_stiff == 12 || n_stiff == 18) ? n_stiff : 0;
+  const bool cmp = dot || R;                             // the refinement's residual: compensated
   // the adjoint's check walk with 8 entries per gather batch: 757 -> 638 us per 2,048-frequency chunk
   // (gpurun_out/ru2_*)
-  else if (mode == 0 && d.unroll == 8) LAUNCH((k_residual<0, 2, false, 0, false, 8>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
-  else if (mode == 0) LAUNCH((k_residual<0, 2>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
-  else if (rhs == 1) LAUNCH((k_residual<1, 1>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
-  else LAUNCH((k_residual<1, 2>), g, b, st, a, X, Fc, R, acc, Mu, cpart, d.pop);
+  const int ru = mode == 0 && rh == 2 && !cmp && unroll == 8 ? 8 : 4;
+  // a population sweep: the POP twins of the operator-form instantiations, chosen the same way
+  dispatch([&](auto md, auto rhc, auto dt, auto nk, auto cm, auto un, auto pp) {
+    constexpr int MD = CV(md), RH = CV(rhc), NK = CV(nk), RU = CV(un);
+    constexpr bool DT = CV(dt), CM = CV(cm), PP = CV(pp);
+    if constexpr ((RH == 2 || RH == MD) && (!DT || (MD == 0 && RH == 0 && CM)) && (NK == 0 || DT) &&
+                  (RU == 4 || (MD == 0 && RH == 2 && !CM)) && (!PP || MD == 0))
+      LAUNCH((k_residual<MD, RH, DT, NK, CM, RU, PP>), dim3((unsigned)residual_parts(a.n), (unsigned)(a.glist ? REFINE_CAP : Fc / 64)),
+             dim3(256), st, a, X, Fc, R, acc, Mu, cpart, pop);
+  }, pick<0, 1>(mode), pick<0, 1, 2>(rh), flag(dot), pick<0, 12, 18>(nsk), flag(cmp), pick<4, 8>(ru),
+     flag(pop.member != nullptr));
 }
 
 void launch_correct_finish(const FunctionalArgs& A, const double* fr0, const double2* cpart, int nparts, int64_t Fc,
                            int nvalid, int64_t q0, double* fr_out, double* loss_terms, double2* mscale,
-                           hipStream_t st, double* gind, double2* tq, const RhsScale& bsc, const PopArgs* pop) {
-  if (pop)
-    LAUNCH(k_correct_finish<true>, dim3((unsigned)(Fc / 64)), dim3(256), st, A, fr0, cpart, nparts, Fc, nvalid, q0,
-           fr_out, loss_terms, mscale, gind, tq, bsc, *pop);
-  else
-    LAUNCH(k_correct_finish<false>, dim3((unsigned)(Fc / 64)), dim3(256), st, A, fr0, cpart, nparts, Fc, nvalid, q0,
-           fr_out, loss_terms, mscale, gind, tq, bsc, PopArgs());
+                           const ChunkOp& op, hipStream_t st, double* gind, double2* tq) {
+  RhsScale bsc;
+  bsc.freqs = op.freqs;
+  bsc.mass_sum = op.mass_sum;
+  bsc.beta_re = op.beta_re;
+  bsc.beta_im = op.beta_im;
+  with_bool(op.pop.member != nullptr, [&](auto pp) {
+    LAUNCH(k_correct_finish<CV(pp)>, dim3((unsigned)(Fc / 64)), dim3(256), st, A, fr0, cpart, nparts, Fc, nvalid, q0,
+           fr_out, loss_terms, mscale, gind, tq, bsc, op.pop);
+  });
 }
 
 void launch_berr_finish(double* acc, int64_t Fc, int nvalid, double tol, int flag, int* flags, double* berr_out,
@@ -3972,11 +3894,10 @@ void launch_gather_entries(const int4* ent, int nent, const double* stiff, int n
 
 void launch_contract_eg(const int4* ent, int nent, const double* se, int n_stiff, const double2* Lam, const double2* X,
                         int64_t Fc, int nvalid, double2* partial, hipStream_t st, const double2* msc) {
-  const dim3 g(contract_eg_parts(nent)), b(256);
-  if (n_stiff == 12 && msc) LAUNCH((k_contract_eg<12, CEG_EW, true>), g, b, st, ent, nent, se, Lam, X, Fc, nvalid, msc, partial);
-  else if (n_stiff == 12) LAUNCH((k_contract_eg<12, CEG_EW, false>), g, b, st, ent, nent, se, Lam, X, Fc, nvalid, msc, partial);
-  else if (msc) LAUNCH((k_contract_eg<18, CEG_EW, true>), g, b, st, ent, nent, se, Lam, X, Fc, nvalid, msc, partial);
-  else LAUNCH((k_contract_eg<18, CEG_EW, false>), g, b, st, ent, nent, se, Lam, X, Fc, nvalid, msc, partial);
+  dispatch([&](auto ns, auto ms) {
+    LAUNCH((k_contract_eg<CV(ns), CEG_EW, CV(ms)>), dim3(contract_eg_parts(nent)), dim3(256), st, ent, nent, se, Lam, X, Fc,
+           nvalid, msc, partial);
+  }, pick<12, 18>(n_stiff), flag(msc != nullptr));
 }
 
 void launch_rhs_dot(const int* sup, const double* val, int n_sup, const double2* Lam, int64_t Fc, double2* t_out,
@@ -3991,16 +3912,17 @@ void launch_reduce_q(const double2* kpart, int nparts, int n_stiff, const double
 
 void launch_contract_q(const int4* ent, int nent, const double* se, int n_stiff, const double2* Lam, const double2* X,
                        int n, int64_t Fc, double2* kpart, hipStream_t st) {
-  const dim3 g(contract_q_parts(n, nent), (unsigned)(Fc / 64)), b(256);
-  if (n_stiff == 12) LAUNCH(k_contract_q<12>, g, b, st, ent, nent, se, Lam, X, Fc, kpart);
-  else LAUNCH(k_contract_q<18>, g, b, st, ent, nent, se, Lam, X, Fc, kpart);
+  with_int<12, 18>(n_stiff, [&](auto ns) {
+    LAUNCH(k_contract_q<CV(ns)>, dim3(contract_q_parts(n, nent), (unsigned)(Fc / 64)), dim3(256), st, ent, nent, se, Lam, X,
+           Fc, kpart);
+  });
 }
 
 void launch_jac_finish(const double2* kpart, int nparts, int n_stiff, const double2* msc, const double2* t_q,
                        const CoefPack& e, int nvalid, int64_t Fc, double2* jc, hipStream_t st) {
-  const dim3 g((unsigned)(Fc / 64)), b(1024);
-  if (n_stiff == 12) LAUNCH(k_jac_finish<12>, g, b, st, kpart, nparts, msc, t_q, e, nvalid, Fc, jc);
-  else LAUNCH(k_jac_finish<18>, g, b, st, kpart, nparts, msc, t_q, e, nvalid, Fc, jc);
+  with_int<12, 18>(n_stiff, [&](auto ns) {
+    LAUNCH(k_jac_finish<CV(ns)>, dim3((unsigned)(Fc / 64)), dim3(1024), st, kpart, nparts, msc, t_q, e, nvalid, Fc, jc);
+  });
 }
 
 void launch_reduce(const double2* partial, int nparts, int n_stiff, const double2* t_q, const CoefPack& e,
@@ -4020,28 +3942,21 @@ void launch_matvec(const int* colptr, const int* rowind, int n, const double2* d
          batch);
 }
 
-static DirArgs make_dir(const DirDesc& d) {
-  DirArgs a;
-  a.dir = d.dir; a.crow = d.crow; a.cptr = d.cptr; a.ce = d.ce; a.dptr = d.dptr; a.de = d.de;
-  a.K = d.K; a.M = d.M; a.freqs = d.freqs;
-  return a;
-}
-
-void launch_dirichlet_rhs(int src, const DirDesc& d, int n_crow, const RhsDesc& rd, double2* G, double2* Bc,
-                          int64_t Fc, hipStream_t st) {
+void launch_dirichlet_rhs(int src, const DirArgs& d, const PopArgs& pop, int n_crow, const RhsArgs& r, double2* G,
+                          double2* Bc, int64_t Fc, hipStream_t st) {
   if (n_crow <= 0) return;
-  dim3 g(n_crow, (unsigned)(Fc / 64)), b(64);
-  if (d.pop.member && src == 0) LAUNCH((k_dirichlet_rhs<0, true>), g, b, st, make_dir(d), make_rhs(rd), G, Bc, Fc, d.pop);
-  else if (d.pop.member) LAUNCH((k_dirichlet_rhs<2, true>), g, b, st, make_dir(d), make_rhs(rd), G, Bc, Fc, d.pop);
-  else if (src == 0) LAUNCH(k_dirichlet_rhs<0>, g, b, st, make_dir(d), make_rhs(rd), G, Bc, Fc, d.pop);
-  else LAUNCH(k_dirichlet_rhs<2>, g, b, st, make_dir(d), make_rhs(rd), G, Bc, Fc, d.pop);
+  dispatch([&](auto sr, auto pp) {
+    LAUNCH((k_dirichlet_rhs<CV(sr), CV(pp)>), dim3(n_crow, (unsigned)(Fc / 64)), dim3(64), st, d, r, G, Bc, Fc, pop);
+  }, pick<0, 2>(src), flag(pop.member != nullptr));
 }
 
-void launch_dirichlet_post(const DirDesc& d, int n_dir, double2* X, int64_t Fc, hipStream_t st, const int* glist) {
+void launch_dirichlet_post(const DirArgs& d, const PopArgs& pop, int n_dir, double2* X, int64_t Fc, hipStream_t st,
+                           const int* glist) {
   if (n_dir <= 0) return;
-  const dim3 g(n_dir, (unsigned)(glist ? REFINE_CAP : Fc / 64));
-  if (d.pop.member) LAUNCH(k_dirichlet_post<true>, g, dim3(64), st, make_dir(d), X, Fc, glist, d.pop);
-  else LAUNCH(k_dirichlet_post<false>, g, dim3(64), st, make_dir(d), X, Fc, glist, d.pop);
+  with_bool(pop.member != nullptr, [&](auto pp) {
+    LAUNCH(k_dirichlet_post<CV(pp)>, dim3(n_dir, (unsigned)(glist ? REFINE_CAP : Fc / 64)), dim3(64), st, d, X, Fc, glist,
+           pop);
+  });
 }
 
 // fill padded frequency slots with the last valid frequency (keeps padded lanes well-posed)

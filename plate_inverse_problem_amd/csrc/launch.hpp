@@ -5,31 +5,17 @@
 
 namespace pfr {
 
-struct RhsDesc {
-  const double* rhsP = nullptr;   // RHS 0: permuted Dirichlet vector (device)
-  double beta_re = 0, beta_im = 0, mass_sum = 0;
-  const double* freqs = nullptr;  // chunk frequencies (device, padded)
-  const double2* B = nullptr;     // RHS 1: explicit batch (device, batch-major, caller numbering)
-  int64_t b_stride = 0;
-  const double2* G = nullptr;     // RHS 2: permuted frequency-minor vector (device)
-  int nvalid = 1;                 // RHS 1: valid batch items of the chunk
-  const int* cslot = nullptr;     // RHS 3: coupled-row slot per permuted row (symmetric mode)
-  const double2* Bc = nullptr;    // RHS 3: Dirichlet corrections (slot-major)
-  PopArgs pop;                    // member != NULL (population sweep): RHS 0 / 3 with the group's member's beta
-};
-
-// Dirichlet decoupling lists of a symmetric-mode solver (device pointers) + operator
-struct DirDesc {
-  const int2* dir = nullptr;
-  const int* crow = nullptr;
-  const int* cptr = nullptr;
-  const int2* ce = nullptr;
-  const int* dptr = nullptr;
-  const int2* de = nullptr;
+// The operator A = K - omega^2 M and the operator right-hand side b = rhsP (beta - omega^2 mass_sum) of the current
+// chunk (device pointers; api.cpp builds one per chunk and passes it down).  pop.member != NULL (population sweep): K
+// holds the members' operators (stride pop.nnz) and every 64-lane group takes K and beta of its member -- the
+// launchers then pick the kernels' POP instantiations.  Explicit-matrix solves read none of K, rhsP and beta.
+struct ChunkOp {
   const double2* K = nullptr;
   const double* M = nullptr;
-  const double* freqs = nullptr;
-  PopArgs pop;                    // member != NULL (population sweep): K and the rhs scale of the group's member
+  const double* freqs = nullptr;  // chunk frequencies (padded)
+  const double* rhsP = nullptr;   // permuted Dirichlet vector
+  double beta_re = 0, beta_im = 0, mass_sum = 0;
+  PopArgs pop;
 };
 
 // the first launch configuration refused since the last call (a kernel's dynamic LDS size), NULL: none; the
@@ -41,11 +27,10 @@ void launch_combine(const double* stiff, int n_stiff, int64_t nnz, const CoefPac
 // bitwise launch_combine's K
 void launch_combine_batch(const double* stiff, int n_stiff, int64_t nnz, const double2* coef, int n_members,
                           double2* K, hipStream_t st);
-// pop != NULL (operator form, here and in launch_front0 / launch_offdiag): the population sweep, K = the members'
-// operators and every 64-lane group assembled from its member's
+// mode 0: the operator op (a population sweep's: every 64-lane group assembled from its member's K; so too in
+// launch_front0 / launch_offdiag); mode 1: the explicit batch (data, ds, nvalid)
 void launch_assemble(int mode, const int4* recs, int nrec, const int* xptr, const int2* xl, int ngroups, double2* F,
-                     int64_t Fc, const double* freqs, const double2* K, const double* M, const double2* data,
-                     int64_t ds, int nvalid, hipStream_t st, const PopArgs* pop = nullptr);
+                     int64_t Fc, const ChunkOp& op, const double2* data, int64_t ds, int nvalid, hipStream_t st);
 // G: lane groups per wave of the symmetric kernel (FAC_G, 4 or 8)
 void launch_factor(bool sym, const DevPattern& P, const int* lvl, int nfronts, int W, int ngroups, double2* F, int64_t Fc,
                    int* flags, hipStream_t st, int G = FAC_G);
@@ -57,12 +42,10 @@ void launch_factor_lds(const DevPattern& P, const int* lvl, int nfronts, int max
 // (symmetric, operator-form launches with few waves)
 // the bottom level fused (k_front0, Plan::fused0): fl = level-0 fronts, the first nsmall with <= 2 pivots
 void launch_front0(const DevPattern& P, const int* fl, int nfronts, int nsmall, const int* fptr, const int* fnz,
-                   int ngroups, double2* F, int64_t Fc, const double* freqs, const double2* K, const double* M,
-                   int* flags, hipStream_t st, const PopArgs* pop = nullptr);
+                   int ngroups, double2* F, int64_t Fc, const ChunkOp& op, int* flags, hipStream_t st);
 void launch_offdiag(int mode, const DevPattern& P, const int4* items, int nitems, const int2* orec, const int* oxp,
-                    const int2* ox, int ngroups, double2* F, int64_t Fc, const double* freqs, const double2* K,
-                    const double* M, const double2* data, int64_t ds, int nvalid, int maxns, hipStream_t st,
-                    bool pipelined = false, const PopArgs* pop = nullptr);
+                    const int2* ox, int ngroups, double2* F, int64_t Fc, const ChunkOp& op, const double2* data, int64_t ds,
+                    int nvalid, int maxns, hipStream_t st, bool pipelined = false);
 // Schur complement A22 -= L21 U12 for a level's tile list (TM x TN = 4 x 4 tiles)
 void launch_schur(bool sym, const DevPattern& P, const int4* tiles, int ntiles, const int* g1, const int* gxp,
                   const int2* gx, int ngroups, double2* F, int64_t Fc, hipStream_t st);
@@ -75,14 +58,17 @@ void launch_schur_blk(const DevPattern& P, const int4* blocks, int nblocks, cons
 // (front, frequency group) -- the top levels' few fronts otherwise pull their L21 blocks through one CU each
 // glist (may be NULL): the groups to solve, REFINE_CAP of them (-1: none), indexed by grid row (pass
 // ngroups = REFINE_CAP); the selective adjoint refinement's solves
+// pop (the chunk operator's): a population sweep's L solve of the operator rhs (rhs_mode 0 / 3) takes its POP form
 void launch_solve(int which, int rhs_mode, bool sym, const DevPattern& P, const int* lvl, int nfronts, int W, int ngroups,
-                  const double2* F, int64_t Fc, double2* WV, const RhsDesc& rd, const double2* Yin, double2* Out,
-                  const int* reach, hipStream_t st, int split = 1, const int* glist = nullptr);
+                  const double2* F, int64_t Fc, double2* WV, const RhsArgs& rd, const PopArgs& pop, const double2* Yin,
+                  double2* Out, const int* reach, hipStream_t st, int split = 1, const int* glist = nullptr);
 // nslices (<= 4) bottom-up L solves as one chain of launches (blockIdx.z = slice; slice z: the fronts
-// lvl[z][0 .. nf[z]), its work vectors WV[z], rhs rd[z] (rhs_mode 0 or 3 for every slice), solution Y[z])
+// lvl[z][0 .. nf[z]), its work vectors WV[z], rhs rd[z] (rhs_mode 0 or 3 for every slice), solution Y[z]);
+// pop (population sweep): slice 0's rhs with the member's beta
 void launch_lsolve_multi(int rhs_mode, const DevPattern& P, int nslices, const int* const* lvl, const int* nf, int W,
-                         int ngroups, const double2* F, int64_t Fc, double2* const* WV, const RhsDesc* rd,
-                         double2* const* Y, const int* const* reach, hipStream_t st, int split, bool nar = false,
+                         int ngroups, const double2* F, int64_t Fc, double2* const* WV, const RhsArgs* rd,
+                         const PopArgs& pop, double2* const* Y, const int* const* reach, hipStream_t st, int split,
+                         bool nar = false,
                          int maxns = 0, int maxf = 0,    // nar (split > 1): pivot blocks in LDS, update rows
                                                          // column-split (k_lsolve_level_z<., true>, k_lsolve_rows_zc)
                          bool rl = true);                // nar + rl: pivot blocks right-looking (k_lsolve_rl_z)
@@ -131,57 +117,35 @@ void launch_contract_q(const int4* ent, int nent, const double* se, int n_stiff,
 void launch_jac_finish(const double2* kpart, int nparts, int n_stiff, const double2* msc, const double2* t_q,
                        const CoefPack& e, int nvalid, int64_t Fc, double2* jc, hipStream_t st);
 // symmetric mode: forward right-hand-side corrections (src 0: operator rhs -> Bc; src 2: G in
-// place) and the adjoint's Dirichlet rows (X in place)
-void launch_dirichlet_rhs(int src, const DirDesc& d, int n_crow, const RhsDesc& rd, double2* G, double2* Bc,
-                          int64_t Fc, hipStream_t st);
-void launch_dirichlet_post(const DirDesc& d, int n_dir, double2* X, int64_t Fc, hipStream_t st, const int* glist = nullptr);
+// place) and the adjoint's Dirichlet rows (X in place); pop (population sweep): K and the rhs scale of the
+// group's member
+void launch_dirichlet_rhs(int src, const DirArgs& d, const PopArgs& pop, int n_crow, const RhsArgs& rd, double2* G,
+                          double2* Bc, int64_t Fc, hipStream_t st);
+void launch_dirichlet_post(const DirArgs& d, const PopArgs& pop, int n_dir, double2* X, int64_t Fc, hipStream_t st,
+                           const int* glist = nullptr);
 // Backward-error check: the original system's rows (forward) or columns (adjoint) in the permuted
 // numbering, A = K - omega^2 M (mode 0) or the explicit batch (mode 1); rhs 0 operator, 1 explicit
 // B, 2 vector G.  The per-frequency componentwise backward error accumulates in acc (max, zero on
 // entry); acc == NULL: only the residual is written to R.
-struct ResidDesc {
-  const int* ptr = nullptr;
-  const int* idx = nullptr;
-  const int* nzs = nullptr;
-  int n = 0;
-  const double2* K = nullptr;
-  const double* M = nullptr;
-  const double* freqs = nullptr;
-  const double2* data = nullptr;
-  int64_t data_stride = 0;
-  int nvalid = 1;
-  const double* rhsP = nullptr;
-  double beta_re = 0, beta_im = 0, mass_sum = 0;
-  const double2* B = nullptr;
-  int64_t b_stride = 0;
-  const int* perm = nullptr;
-  const double2* G = nullptr;
-  const int* walk = nullptr;   // the n rows (permuted numbering) in walk order
-  // the gradient contraction fused into the forward walk (mode 0, rhs 0, Mu != NULL): stiffness values
-  // nz-major (n_stiff 12 or 18 per nz) and the per (workgroup, k, frequency) output
-  const double* se = nullptr;
-  int n_stiff = 0;
-  double2* kpart = nullptr;
-  const int* glist = nullptr;  // the groups to walk (REFINE_CAP, -1: none; NULL: every group)
-  int unroll = 4;              // entries per gather batch of the adjoint check walk (4 or 8; the same bits)
-  PopArgs pop;                 // member != NULL (population sweep, mode 0): K and beta of the group's member
-};
+// n_stiff (12 or 18, with a.se / a.kpart; else 0): the gradient contraction fused into the forward walk (mode 0,
+// rhs 0, Mu != NULL).  unroll: entries per gather batch of the adjoint check walk (4 or 8; the same bits).
+// pop (population sweep, mode 0): K and beta of the group's member.
 // Mu != NULL (mode 0, rhs 0): also the functional-correction dot products sum_p Mu_p r_p, one partial
 // per workgroup and frequency in cpart (residual_parts(n) x Fc), summed by launch_correct_finish
+void launch_residual(int mode, int rhs, const ResidArgs& a, int n_stiff, int unroll, const PopArgs& pop, const double2* X,
+                     int64_t Fc, double2* R, double* acc, hipStream_t st, const double2* Mu = nullptr,
+                     double2* cpart = nullptr);
 // partial[t * n_stiff + k] = sum_{q in tile t} msc[q] sum_b kpart[b][k][q] (msc NULL: 1; tiles of 64
 // frequencies): the fused walk's contraction as Fc / 64 parts
 void launch_reduce_q(const double2* kpart, int nparts, int n_stiff, const double2* msc, int nvalid, int64_t Fc,
                      double2* partial, hipStream_t st);
-void launch_residual(int mode, int rhs, const ResidDesc& d, const double2* X, int64_t Fc, double2* R, double* acc,
-                     hipStream_t st, const double2* Mu = nullptr, double2* cpart = nullptr);
 // corrected fr (fr_out, global index; may be NULL), loss terms and cotangent scales of a chunk
 // gind != NULL: per 64-frequency group its largest |correction| / |fr| (launch_select_groups picks from them)
-// tq != NULL: t_q = mu^T rhsP in, m_q t_q out, and the solve-error scale in m_q (k_correct_finish)
+// tq != NULL: t_q = mu^T rhsP in, m_q t_q out, and the solve-error scale in m_q (k_correct_finish) from op's
+// rhs scale (population sweep: with the beta of the group's member)
 void launch_correct_finish(const FunctionalArgs& A, const double* fr0, const double2* cpart, int nparts, int64_t Fc,
                            int nvalid, int64_t q0, double* fr_out, double* loss_terms, double2* mscale,
-                           hipStream_t st, double* gind = nullptr, double2* tq = nullptr,
-                           const RhsScale& bsc = RhsScale(),
-                           const PopArgs* pop = nullptr);   // population sweep: bsc's beta from the group's member
+                           const ChunkOp& op, hipStream_t st, double* gind = nullptr, double2* tq = nullptr);
 // glist[0 .. REFINE_CAP): the groups with the largest indicators above tol, largest first, -1 past them
 void launch_select_groups(const double* gind, int ngroups, double tol, int* glist, hipStream_t st);
 // flags |= flag where acc[q] > tol (or not finite); acc cleared
@@ -193,5 +157,12 @@ void launch_scale_vec(double2* X, const double2* m, int n, int64_t Fc, hipStream
 void launch_unpermute(const int* perm, int n, const double2* X, int64_t Fc, int nvalid, double2* out, hipStream_t st);
 void launch_matvec(const int* colptr, const int* rowind, int n, const double2* data, int64_t ds, const double2* x,
                    int64_t xs, double2* y, int transpose, int batch, hipStream_t st);
+// a chunk's frequencies (padded with the last) and its flags cleared, one kernel
+void launch_chunk_start(double* freqs, const double* src, int nvalid, int64_t Fc, int* flags, hipStream_t st,
+                        double* loss = nullptr, double* w = nullptr, int nw = 0, int* out_flags = nullptr,
+                        double* berr = nullptr, int nfreq = 0);
+// p[0 .. n) = 0 (complex entries)
+void launch_zero(double2* p, int64_t n, hipStream_t st);
+void launch_flags_merge(const int* chunk, int nvalid, int* out, hipStream_t st);
 
 }  // namespace pfr
