@@ -152,6 +152,33 @@ PFR_API void pfr_solver_destroy(pfr_solver* s);
 PFR_API int64_t pfr_solver_workspace_bytes(const pfr_symbolic* sym, int32_t max_batch);
 PFR_API int32_t pfr_solver_max_batch(const pfr_solver* s);
 
+/* The launch schedule: which kernel form every tree level launches in every pass, and with what shape.  The library
+ * decides it once per solver, from the launch-shape environment knobs (PFR_SOLVE_WMAX, PFR_US2_NAR, ...) read at
+ * pfr_solver_create, the level geometry and the right-hand-side reaches; its level loops launch exactly these records.
+ * pfr_symbolic_schedule: the schedule a solver created now for max_batch would start with, every front reached (host
+ * only, no device).  pfr_solver_schedule: the live schedule of a solver, with its current reaches.
+ * dst receives n_levels x PFR_SCHED_COLS int32 (capacity in bytes): the six tables below one after the other, each
+ * n_levels rows (level 0 first) of its column count.  In the paired, chain and unpaired tables nf = 0 (nmax = 0) means
+ * the level launches nothing in that pass.
+ *   factor (13): nf, maxns, fused0 (level through k_front0 in operator-form sweeps), f0_small (its fronts of <= 2
+ *                pivots), lds (A11 by k_factor_sym_lds), G (lane groups per wave of k_factor_sym), waves (A11 panel),
+ *                off_small, off_pu (L21: SMALL form; 3 = pipelined prefix, 2 = plain), nasm, nitems, nblocks, ntiles
+ *   pair (9):    paired top-down pass.  nf, form (0 tiny4, 1 tiny8, 2 rl, 3 level_small, 4 level_big), upd (0 none,
+ *                1 k_usolve2_upd, 2 k_usolve2_updc), split, waves (of the pivot-block kernel), rpl (rl), RB (updc),
+ *                tiny, small (the level's classes under PFR_US2_TINY / PFR_US2_SMALL, whichever form runs)
+ *   chain (11):  bottom-up chain of the loss sweeps.  nf0, nf1 (fronts of reach 0 / 1), nmax, nsum, form (0 plain,
+ *                1 NAR, 2 RL), rows (0 none, 1 k_lsolve_rows_z, 2 k_lsolve_rows_zc), split, waves, rpl (RL), RB (zc),
+ *                lds_bytes (NAR: dynamic LDS)
+ *   solve_all, solve_reach0, solve_reach1 (5 each): the unpaired passes over all fronts / the fronts of reach 0 / 1.
+ *                nf, level_w (the level's size-based wave count), waves (the launch's), split_L, split_U */
+#define PFR_SCHED_FACTOR_COLS 13
+#define PFR_SCHED_PAIR_COLS 9
+#define PFR_SCHED_CHAIN_COLS 11
+#define PFR_SCHED_SOLVE_COLS 5
+#define PFR_SCHED_COLS (PFR_SCHED_FACTOR_COLS + PFR_SCHED_PAIR_COLS + PFR_SCHED_CHAIN_COLS + 3 * PFR_SCHED_SOLVE_COLS)
+PFR_API int pfr_symbolic_schedule(const pfr_symbolic* sym, int32_t max_batch, int32_t* dst, int64_t capacity_bytes);
+PFR_API int pfr_solver_schedule(const pfr_solver* s, int32_t* dst, int64_t capacity_bytes);
+
 /* ---------------------------------------------------------------- InnerState-compatible entry points
  * pfr_solve: x[q] = A_q^{-1} b[q]  (transpose != 0: A_q^{-T} b[q], NON-conjugate, = UMFPACK_Aat,
  * InnerState.h:183-185).  A_q values on the CSC pattern: data_dev + q * data_stride (complex, nnz);

@@ -31,6 +31,20 @@ LOSS_IDS = {"MSE": LOSS_MSE, "RMSE": LOSS_RMSE, "MSE_AFC": LOSS_MSE_AFC, "MSE_LO
 EXPORT = dict(PERM=0, IPERM=1, FRONTS=2, IDX=3, RELPOS=4, ASM_PTR=5, ASM_COL=6, ASM_NZ=7, EA_PTR=8,
               EA_SRC=9, LEVEL_PTR=10, LEVEL_FRONTS=11, DIRICHLET=12, COUPLING=13)
 
+# the tables of pfr_symbolic_schedule / pfr_solver_schedule and their int32 columns (include/pfr.h), in order
+_SOLVE_COLS = ("nf", "level_w", "waves", "split_L", "split_U")
+SCHEDULE = (
+    ("factor", ("nf", "maxns", "fused0", "f0_small", "lds", "G", "waves", "off_small", "off_pu", "nasm", "nitems",
+                "nblocks", "ntiles")),
+    ("pair", ("nf", "form", "upd", "split", "waves", "rpl", "RB", "tiny", "small")),
+    ("chain", ("nf0", "nf1", "nmax", "nsum", "form", "rows", "split", "waves", "rpl", "RB", "lds_bytes")),
+    ("solve_all", _SOLVE_COLS), ("solve_reach0", _SOLVE_COLS), ("solve_reach1", _SOLVE_COLS),
+)
+PAIR_FORMS = ("tiny4", "tiny8", "rl", "level_small", "level_big")    # pair["form"]
+PAIR_UPD = ("none", "upd", "updc")                                   # pair["upd"]
+CHAIN_FORMS = ("plain", "nar", "rl")                                 # chain["form"]
+CHAIN_ROWS = ("none", "rows_z", "rows_zc")                           # chain["rows"]
+
 
 class NativeError(RuntimeError):
     pass
@@ -66,6 +80,8 @@ _PROTOS = {
     "pfr_solver_destroy": (None, [_P]),
     "pfr_solver_workspace_bytes": (C.c_int64, [_P, C.c_int32]),
     "pfr_solver_max_batch": (C.c_int32, [_P]),
+    "pfr_symbolic_schedule": (C.c_int, [_P, C.c_int32, _I32P, C.c_int64]),
+    "pfr_solver_schedule": (C.c_int, [_P, _I32P, C.c_int64]),
     "pfr_solve": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32, _P, _P]),
     "pfr_matvec": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32, _P]),
     "pfr_set_stiffness": (C.c_int, [_P, C.c_int32, _P, _DP]),
@@ -146,6 +162,18 @@ def _ptr(t) -> int:
     return t.data_ptr()
 
 
+def _schedule(n_levels: int, fill) -> dict:
+    """The launch schedule ``fill(dst, capacity_bytes)`` writes: {pass name: structured array, one row per level}."""
+    flat = np.zeros(n_levels * sum(len(cols) for _, cols in SCHEDULE), dtype=np.int32)
+    fill(flat.ctypes.data_as(_I32P), flat.nbytes)
+    out, at = {}, 0
+    for name, cols in SCHEDULE:
+        size = n_levels * len(cols)
+        out[name] = flat[at:at + size].copy().view(np.dtype([(c, np.int32) for c in cols]))
+        at += size
+    return out
+
+
 def stream_order(waiter: int, signaller: int):
     """pfr_stream_order: work enqueued on HIP stream ``waiter`` from now on runs after the work enqueued on
     ``signaller`` so far (stream handles, e.g. torch.cuda.Stream.cuda_stream)."""
@@ -224,6 +252,12 @@ class Symbolic:
     def workspace_bytes(self, max_batch: int) -> int:
         return int(lib().pfr_solver_workspace_bytes(self._h, int(max_batch)))
 
+    def schedule(self, max_batch: int) -> dict:
+        """pfr_symbolic_schedule: the launch schedule a solver created now (the PFR_* launch-shape knobs of the
+        environment) for ``max_batch`` would start with, every front reached.  Needs no device."""
+        return _schedule(self.stats()["n_levels"], lambda dst, cap: check(
+            lib().pfr_symbolic_schedule(self._h, int(max_batch), dst, cap), "pfr_symbolic_schedule"))
+
     def __del__(self):
         h = getattr(self, "_h", None)
         if h is not None and _lib is not None:
@@ -252,6 +286,11 @@ class Solver:
         if h is not None and _lib is not None:
             _lib.pfr_solver_destroy(h)
             self._h = None
+
+    def schedule(self) -> dict:
+        """pfr_solver_schedule: the records this solver's level loops launch, with its current reaches."""
+        return _schedule(self.sym.stats()["n_levels"], lambda dst, cap: check(
+            lib().pfr_solver_schedule(self._h, dst, cap), "pfr_solver_schedule"))
 
     @staticmethod
     def _stream(t):

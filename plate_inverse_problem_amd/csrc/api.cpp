@@ -61,7 +61,7 @@ struct pfr_solver {
   int n = 0;
   int64_t nnz = 0;
   int64_t Fc = 0;  // frequencies per chunk (multiple of 64)
-  std::vector<int32_t> level_ptr, level_maxf, level_maxns, level_W, perm, iperm;
+  std::vector<int32_t> level_ptr, perm, iperm;
   std::vector<int32_t> tile_ptr, blk_ptr, asm_ptr, item_ptr;   // per level: first Schur tile / block, A11 record, L21 item
   DevPattern P{};
   // owned device arrays
@@ -70,8 +70,6 @@ struct pfr_solver {
   int4* d_tiles = nullptr;              // Schur tiles (front, i0, j0, 0), grouped by level
   int4* d_items = nullptr;              // off-diagonal panel items (front, first row/col, kind, record offset)
   int2* d_orec = nullptr;               // per item x lane group x pivot: (nz, first child source) of the entry
-  bool fused0 = false;                  // level 0 through k_front0 (Plan::fused0)
-  int n_f0 = 0, f0_small = 0;
   int32_t *d_f0_front = nullptr, *d_f0_ptr = nullptr, *d_f0_nz = nullptr;
   int32_t* d_oxp = nullptr;             // per item: range of further child sources in d_ox
   int2* d_ox = nullptr;                 // (pivot * OFF_G OFF_RPL + row slot, element id)
@@ -151,8 +149,6 @@ struct pfr_solver {
   double* fr0 = nullptr;
   double2 *mscale = nullptr, *cpart = nullptr;     // mscale complex: the solve-error scale (k_correct_finish)
   int scale_corr = 1;                   // PFR_SCALE_CORR: the solve-error scale of the loss sweeps' cotangent
-  int us2_tiny = 8;                     // PFR_US2_TINY (0 / 4 / 8): levels whose pivot blocks are <= this, one wave per front
-  int off_pu_waves = 0;                 // PFR_OFF_PU_WAVES: L21 launches with fewer waves run the pipelined prefix
   int32_t* flags = nullptr;
   // operator / rhs / functional / stiffness state
   const double2* K = nullptr;
@@ -186,31 +182,11 @@ struct pfr_solver {
   // loaded or stored; index data is shared by all frequencies and not counted)
   std::vector<std::array<int64_t, pfr::NKC>> lev_bytes;
   pfr::Workspace ws;                    // element counts of the chunk buffers (plan.cpp; what is allocated)
-  // launch-shape tuning knobs, read from the environment when the solver is created (so that a
-  // process can build solvers with different settings, e.g. tests forcing each kernel variant):
-  // PFR_SOLVE_WMAX (waves per solve workgroup, at most), PFR_FAC_WMAX (waves per A11 LU
-  // workgroup, at most), PFR_US2_SMALL (largest front of a level the paired top-down solve treats
-  // with its low-register small-front variant)
-  int solve_wmax = 8, fac_wmax = 16, us2_small = 110;
-  int fac_lds = -1;                     // PFR_FAC_LDS: which levels factor A11 in LDS (k_factor_sym_lds): n > 0
-                                        // those whose largest pivot block has at least n pivots, 0 none, -1 auto
-                                        // (default since round 3: 512-frequency sweeps +2.6 %, 4,096 unchanged)
-  int fac_lds_wg = 160;                 // PFR_FAC_LDS_WG: auto mode threshold (workgroups of k_factor_sym)
+  // which kernel form every level launches in every pass, with what shape (plan.hpp): built when the solver is
+  // created from the launch-shape knobs (sched.knobs, read from the environment then), its reach-dependent records
+  // again whenever a reach changes (set_reach)
+  pfr::Schedule sched;
   int res_unroll = 8;                   // PFR_RES_UNROLL: entries per gather batch of the adjoint check walk (4 / 8)
-  int fac_g_wg = 0;                     // PFR_FAC_G_WG: k_factor_sym launches below this many workgroups take G = 4 / 8
-  int fac_gbig = 4, fac_g_ns = 64;      // PFR_FAC_GBIG / PFR_FAC_G_NS: k_factor_sym's lane groups per wave on the
-                                        // levels whose largest pivot block exceeds PFR_FAC_G_NS pivots
-  int us2_nar = 256;                    // PFR_US2_NAR: solve launches (paired top-down, bottom-up chain) with fewer
-                                        // (front, group) workgroups than this take the narrow-level forms -- pivot
-                                        // blocks in LDS, left-looking, the update parts with their columns split
-                                        // over the waves (k_usolve2_updc + k_usolve2_rl, k_lsolve_level_z<., true>
-                                        // + k_lsolve_rows_zc); 0: never.  Measured best at 256 for both passes
-                                        // (1,024 / 4,096: no gain at 512 frequencies, slower at 4,096)
-  int us2_rl = 1;                       // PFR_US2_RL: k_usolve2_rl for the narrow levels' paired pivot blocks
-  int ls_rl = 1;                        // PFR_LS_RL: k_lsolve_rl_z for the bottom-up chain's narrow pivot blocks
-  int split_target = 256;               // PFR_SOLVE_SPLIT: solve launches with fewer (front, group) workgroups
-                                        // than this (one per CU) split their update parts up to about this
-                                        // many workgroups (0: off)
   // backward-error checks (pfr_set_check): PFR_CHECK_* bits, tolerance, optional per-item output;
   // per-frequency maxima scratch, forward and adjoint (kept zero between checks)
   int check_mode = 0;
@@ -330,27 +306,6 @@ int finish_timing(pfr_solver* s, const bool* used) {
 
 void reset_timing(pfr_solver* s) { s->n_tev = 0; }
 
-// Waves per workgroup of a solve launch over nf fronts of level l: the level's size-based count,
-// raised (up to 8) when the launch has too few workgroups to fill the chip -- the sparse passes
-// and the top levels, which are latency-bound: every wave more takes rows off each wave's chain.
-int solve_W(const pfr_solver* s, int l, int nf) { return pfr::solve_waves(s->level_W[l], nf, s->Fc, s->solve_wmax); }
-
-// Workgroups per (front, frequency group) for the update part of a solve launch over nf fronts: 1 when the
-// launch already has split_target workgroups, else enough to reach it (at most 16).
-int solve_split(const pfr_solver* s, int nf) { return pfr::solve_split(nf, s->Fc, s->split_target); }
-
-// A11 of level l factored in LDS (k_factor_sym_lds): PFR_FAC_LDS = n > 0: levels whose largest pivot block has
-// >= n pivots; -1: levels on which the global-memory kernel would get fewer than PFR_FAC_LDS_WG workgroups (the
-// top of the tree in small chunks: 512 frequencies levels 10-16, 2,048 level 16 -- faster per level there, slower
-// elsewhere; the default since the MMD ordering: 512-frequency sweeps 31.8k -> 32.6k freq-solves/s, 4,096
-// unchanged)
-bool level_lds(const pfr_solver* s, int l) {
-  const int64_t wgs = (int64_t)(s->level_ptr[l + 1] - s->level_ptr[l]) * (s->Fc / 64) * pfr::FAC_G;
-  return s->sym && s->level_maxns[l] <= 64 &&
-         (s->fac_lds > 0 ? s->level_maxns[l] >= s->fac_lds
-                         : s->fac_lds < 0 && s->level_maxns[l] >= 16 && wgs < s->fac_lds_wg);
-}
-
 // The operator and the operator right-hand side of the chunk starting at q0 (pfr::ChunkOp), built once per chunk and
 // passed to everything that launches on it: the solver's K and rhs scale, or in a population sweep (pop != NULL: the
 // sweep's group table, a device table padded to whole chunks; chunks start at multiples of Fc) the members'
@@ -424,52 +379,32 @@ int factor_all(pfr_solver* s, const pfr::ChunkOp& op, int mode, const double2* d
   };
   if (kt) s->tev[s->n_tev].f0 = false;
   for (int l = 0; l < L; ++l) {
-    int nf = s->level_ptr[l + 1] - s->level_ptr[l];
+    const pfr::FactorLevel& r = s->sched.factor[l];
+    const int32_t* lvl = s->d_level_fronts + s->level_ptr[l];
     mark(l, 0);
-    if (l == 0 && s->fused0 && mode == 0) {
+    if (r.fused0 && mode == 0) {
       if (kt) s->tev[s->n_tev].f0 = true;
       // the bottom level's leaf fronts in one pass (k_front0): A11, L21 and update block per frequency in registers
-      pfr::launch_front0(s->P, s->d_f0_front, s->n_f0, s->f0_small, s->d_f0_ptr, s->d_f0_nz, ngroups, s->F, s->Fc, op,
-                         s->flags, st);
+      pfr::launch_front0(s->P, s->d_f0_front, r, s->d_f0_ptr, s->d_f0_nz, ngroups, s->F, s->Fc, op, s->flags, st);
       for (int c = 1; c <= 5; ++c) mark(l, c);
       continue;
     }
-    // panel: enough workgroups (front x 16 frequencies) to fill the chip -> one wave
-    // each (no idle waves at the block barriers); few large fronts -> more waves
-    // (symmetric kernel: up to 16 waves -- the top levels' few fronts are latency-bound, every
-    // wave more takes rows off each wave's serial chain)
-    const int fac_wmax = s->fac_wmax;
-    // lane groups per wave of the symmetric A11 kernel: FAC_G; fac_gbig on the levels with a pivot block of more
-    // than fac_g_ns pivots, whose long chains gain from more row slots per wave (the deep tree's level 25 with its
-    // 76-pivot separator at 2,048 frequencies: 0.61 -> 0.41 ms with 4; the levels of 2-3 fronts of <= 35 pivots
-    // below it were slower with 4, gpurun_out/fg2_t2048_*); raised to 4 / 8 while the launch has fewer than
-    // fac_g_wg workgroups (default off)
-    int G = (s->sym && s->level_maxns[l] > s->fac_g_ns) ? s->fac_gbig : pfr::FAC_G;
-    while (s->sym && G < 8 && (int64_t)nf * ngroups * G < s->fac_g_wg) G *= 2;
-    const int64_t wgs = (int64_t)nf * ngroups * G;
-    const int64_t wfill = (4096 + wgs - 1) / wgs;
-    const int Wp = (int)std::max<int64_t>(
-        1, s->sym ? std::min<int64_t>(fac_wmax, wfill) : std::min<int64_t>(s->level_W[l], wfill));
-    pfr::launch_assemble(mode, s->d_asm + s->asm_ptr[l], s->asm_ptr[l + 1] - s->asm_ptr[l],
-                         s->d_asm_xp + s->asm_ptr[l] / 8, s->d_asm_x, ngroups, s->F, s->Fc, op, data, ds, nvalid, st);
+    pfr::launch_assemble(mode, s->d_asm + s->asm_ptr[l], r.nasm, s->d_asm_xp + s->asm_ptr[l] / 8, s->d_asm_x, ngroups,
+                         s->F, s->Fc, op, data, ds, nvalid, st);
     mark(l, 1);
-    if (level_lds(s, l))
-      pfr::launch_factor_lds(s->P, s->d_level_fronts + s->level_ptr[l], nf, s->level_maxns[l], s->F, s->Fc, s->flags, st);
+    if (r.lds)
+      pfr::launch_factor_lds(s->P, lvl, r, s->F, s->Fc, s->flags, st);
     else
-      pfr::launch_factor(s->sym, s->P, s->d_level_fronts + s->level_ptr[l], nf, Wp, ngroups, s->F, s->Fc, s->flags, st,
-                         G);
+      pfr::launch_factor(s->sym, s->P, lvl, r, ngroups, s->F, s->Fc, s->flags, st);
     mark(l, 2);
-    // the software-pipelined L21 prefix on the launches with few waves (symmetric analyses, operator form)
-    const int64_t owaves = (int64_t)(s->item_ptr[l + 1] - s->item_ptr[l]) * ngroups;
-    pfr::launch_offdiag(mode, s->P, s->d_items + s->item_ptr[l], s->item_ptr[l + 1] - s->item_ptr[l], s->d_orec,
-                        s->d_oxp + s->item_ptr[l], s->d_ox, ngroups, s->F, s->Fc, op, data, ds, nvalid,
-                        s->level_maxns[l], st, s->sym && owaves < s->off_pu_waves);
+    pfr::launch_offdiag(mode, s->P, s->d_items + s->item_ptr[l], r, s->d_orec, s->d_oxp + s->item_ptr[l], s->d_ox,
+                        ngroups, s->F, s->Fc, op, data, ds, nvalid, st);
     mark(l, 3);
-    pfr::launch_schur_blk(s->P, s->d_blocks + s->blk_ptr[l], s->blk_ptr[l + 1] - s->blk_ptr[l],
+    pfr::launch_schur_blk(s->P, s->d_blocks + s->blk_ptr[l], r.nblocks,
                           s->d_bg1 + (int64_t)s->blk_ptr[l] * 16 * 16, s->d_bgxp + s->blk_ptr[l], s->d_bgx, ngroups, s->F,
                           s->Fc, st);
     mark(l, 4);
-    pfr::launch_schur(s->sym, s->P, s->d_tiles + s->tile_ptr[l], s->tile_ptr[l + 1] - s->tile_ptr[l],
+    pfr::launch_schur(s->sym, s->P, s->d_tiles + s->tile_ptr[l], r.ntiles,
                       s->d_g1 + (int64_t)s->tile_ptr[l] * pfr::SCHUR_TM * pfr::SCHUR_TN * pfr::SCHUR_SR * pfr::SCHUR_SC,
                       s->d_gxp + s->tile_ptr[l], s->d_gx, ngroups, s->F, s->Fc, st);
     mark(l, 5);
@@ -489,16 +424,12 @@ int solve_all(pfr_solver* s, const pfr::ChunkOp& op, int which, int rhs_mode, co
   const int* reach = subset >= 0 ? s->d_reach[subset] : nullptr;
   for (int t = 0; t < L; ++t) {
     int l = up ? t : L - 1 - t;
-    const int32_t* lvl = s->d_level_fronts + s->level_ptr[l];
-    int nf = s->level_ptr[l + 1] - s->level_ptr[l];
-    if (up && subset >= 0) {
-      lvl = s->d_reach_fronts[subset] + s->reach_ptr[subset][l];
-      nf = s->reach_ptr[subset][l + 1] - s->reach_ptr[subset][l];
-    }
-    // the update parts split over several workgroups: L solves, and U solves in symmetric mode
-    const int split = (which == 0 || (which == 1 && s->sym)) ? solve_split(s, nf) : 1;
-    pfr::launch_solve(which, rhs_mode, s->sym, s->P, lvl, nf, solve_W(s, l, nf), ngroups, s->F, s->Fc, s->WV, rd, op.pop,
-                      Yin, Out, reach, st, split, glist);
+    // bottom-up over the subset's fronts only, top-down over the whole level
+    const bool part = up && subset >= 0;
+    const int32_t* lvl = part ? s->d_reach_fronts[subset] + s->reach_ptr[subset][l] : s->d_level_fronts + s->level_ptr[l];
+    const pfr::SolveLevel& r = s->sched.solve[part ? pfr::SUBSET_REACH0 + subset : pfr::SUBSET_ALL][l];
+    pfr::launch_solve(which, rhs_mode, s->sym, s->P, lvl, r, ngroups, s->F, s->Fc, s->WV, rd, op.pop, Yin, Out, reach, st,
+                      glist);
   }
   LAUNCH_TRY();
   return PFR_OK;
@@ -608,20 +539,9 @@ int fn_bottom_up(pfr_solver* s, const pfr::ChunkOp& op, int rhs_mode, const pfr:
     rd[k].cslot = s->d_noslot;
   }
   for (int l = 0; l < L; ++l) {
-    const int* lvl[4];
-    int nf[4];
-    lvl[0] = s->d_reach_fronts[0] + s->reach_ptr[0][l];
-    nf[0] = s->reach_ptr[0][l + 1] - s->reach_ptr[0][l];
-    for (int k = 1; k < 4; ++k) {
-      lvl[k] = s->d_reach_fronts[1] + s->reach_ptr[1][l];
-      nf[k] = s->reach_ptr[1][l + 1] - s->reach_ptr[1][l];
-    }
-    const int nmax = std::max(nf[0], nf[1]);
-    if (nmax == 0) continue;
-    const int nsum = nf[0] + 3 * nf[1];
-    const bool nar = (int64_t)nsum * ngroups < s->us2_nar && pfr::ls_nar_fits(s->level_maxns[l]);
-    pfr::launch_lsolve_multi(rhs_mode, s->P, 4, lvl, nf, solve_W(s, l, nmax), ngroups, s->F, s->Fc, WV, rd, op.pop, Y,
-                             reach, st, solve_split(s, nsum), nar, s->level_maxns[l], s->level_maxf[l], s->ls_rl != 0);
+    const int32_t* sup = s->d_reach_fronts[1] + s->reach_ptr[1][l];
+    const int* lvl[4] = {s->d_reach_fronts[0] + s->reach_ptr[0][l], sup, sup, sup};
+    pfr::launch_lsolve_multi(rhs_mode, s->P, 4, lvl, s->sched.chain[l], ngroups, s->F, s->Fc, WV, rd, op.pop, Y, reach, st);
   }
   LAUNCH_TRY();
   return PFR_OK;
@@ -635,9 +555,8 @@ int sym_top_down_support(pfr_solver* s, hipStream_t st) {
   const int L = (int)s->level_ptr.size() - 1;
   const int ngroups = (int)(s->Fc / 64);
   for (int l = L - 1; l >= 0; --l) {
-    const int nf = s->reach_ptr[1][l + 1] - s->reach_ptr[1][l];
-    pfr::launch_solve(1, 0, true, s->P, s->d_reach_fronts[1] + s->reach_ptr[1][l], nf, solve_W(s, l, nf), ngroups, s->F,
-                      s->Fc, s->WV, pfr::RhsArgs(), pfr::PopArgs(), s->Y, s->X, s->d_reach[0], st, solve_split(s, nf));
+    pfr::launch_solve(1, 0, true, s->P, s->d_reach_fronts[1] + s->reach_ptr[1][l], s->sched.solve[pfr::SUBSET_REACH1][l],
+                      ngroups, s->F, s->Fc, s->WV, pfr::RhsArgs(), pfr::PopArgs(), s->Y, s->X, s->d_reach[0], st);
   }
   LAUNCH_TRY();
   return PFR_OK;
@@ -647,14 +566,8 @@ int sym_top_down_pair(pfr_solver* s, hipStream_t st, bool fwd_all = false) {
   const int L = (int)s->level_ptr.size() - 1;
   const int ngroups = (int)(s->Fc / 64);
   for (int l = L - 1; l >= 0; --l) {
-    const int nf = s->level_ptr[l + 1] - s->level_ptr[l];
-    const bool small = s->level_maxf[l] <= s->us2_small;
-    const int tiny = s->us2_tiny > 0 && s->level_maxns[l] <= s->us2_tiny ? (s->level_maxns[l] <= 4 ? 4 : 8) : 0;
-    const bool nar = (int64_t)nf * ngroups < s->us2_nar;
-    pfr::launch_usolve2(s->P, s->d_level_fronts + s->level_ptr[l], nf, solve_W(s, l, nf), small, ngroups, s->F, s->Fc,
-                        s->Y, s->X, s->d_reach[0], fwd_all ? nullptr : s->d_reach[1], s->Y2, s->XA, s->d_reach[1], st,
-                        nar ? std::max(2, solve_split(s, nf)) : solve_split(s, nf), nar ? 0 : tiny, nar,
-                        s->level_maxns[l], s->us2_rl != 0);
+    pfr::launch_usolve2(s->P, s->d_level_fronts + s->level_ptr[l], s->sched.pair[l], ngroups, s->F, s->Fc, s->Y, s->X,
+                        s->d_reach[0], fwd_all ? nullptr : s->d_reach[1], s->Y2, s->XA, s->d_reach[1], st);
   }
   LAUNCH_TRY();
   return PFR_OK;
@@ -668,6 +581,7 @@ int set_reach(pfr_solver* s, int which, const std::vector<int32_t>& prows) {
                    s->reach_ptr[which]);
   s->reach_host[which].assign(mark.begin(), mark.end());
   s->fn_ready = false;
+  pfr::schedule_reach(s->sched, s->reach_ptr);
   HIP_TRY(hipMemcpy(s->d_reach[which], mark.data(), mark.size() * 4, hipMemcpyHostToDevice));
   if (!list.empty()) HIP_TRY(hipMemcpy(s->d_reach_fronts[which], list.data(), list.size() * 4, hipMemcpyHostToDevice));
   return PFR_OK;
@@ -867,70 +781,36 @@ int pfr_solver_create(const pfr_symbolic* sym, const int32_t* colptr, const int3
     const char* e = getenv(name);
     return e ? std::max(lo, std::min(hi, atoi(e))) : def;
   };
-  // launch-shape and path knobs (the measured-slower variants of rounds 1-4 are in git history, DESIGN.md
-  // section 8): waves per solve / A11 LU workgroup, the small-front paired top-down variant's front limit,
-  // the solve update-part split target, the A11 LU in LDS, the functional from the bottom-up passes, the
-  // contraction in the forward walk, the cotangent's solve-error scale, the one-wave top-down pass, the
-  // Schur block-kernel threshold and the pipelined L21 prefix
-  // (tests/synthetic.py restates the defaults of us2_small, fac_g_ns, us2_nar, fac_lds_wg and blk_min)
-  s->solve_wmax = knob("PFR_SOLVE_WMAX", 8, 1, 8);
-  s->fac_wmax = knob("PFR_FAC_WMAX", 16, 1, 16);
-  s->fac_g_wg = knob("PFR_FAC_G_WG", 0, 0, 1 << 20);
+  // path knobs: the functional from the bottom-up passes, the contraction in the forward walk, the cotangent's
+  // solve-error scale, the check walk's gather batch, sweep graphs (the launch-shape knobs: pfr::knobs_from_env)
   s->res_unroll = knob("PFR_RES_UNROLL", 8, 4, 8) == 8 ? 8 : 4;
-  s->fac_gbig = knob("PFR_FAC_GBIG", 4, 2, 8);
-  if (s->fac_gbig != 2 && s->fac_gbig != 8) s->fac_gbig = 4;
-  s->fac_g_ns = knob("PFR_FAC_G_NS", 64, 0, 1 << 20);
-  s->us2_small = knob("PFR_US2_SMALL", 110, 0, pfr::MAX_FRONT);
-  s->split_target = knob("PFR_SOLVE_SPLIT", 256, 0, 1 << 20);
-  s->us2_nar = knob("PFR_US2_NAR", 256, 0, 1 << 30);
-  s->fac_lds = knob("PFR_FAC_LDS", -1, -1, 64);
   s->fn_dot = knob("PFR_FN_DOT", 1, 0, 1);
   s->contract_walk = knob("PFR_CONTRACT_WALK", 1, 0, 1);
   s->scale_corr = knob("PFR_SCALE_CORR", 1, 0, 1);
-  // 8: the bottom two levels at 2,048 frequencies 685 / 612 -> 509 / 489 us (profiles/r04/experiments/us2_tiny_*)
-  s->us2_tiny = knob("PFR_US2_TINY", 8, 0, 8);
-  // the narrow levels' paired top-down pivot blocks right-looking with prefetched factor entries (k_usolve2_rl)
-  s->us2_rl = knob("PFR_US2_RL", 1, 0, 1);
-  const int blk_min = knob("PFR_SCHUR_BLK_MIN", 24, 0, pfr::MAX_FRONT);   // update blocks of >= this many rows: block kernel
-  pfr::PlanOptions po;
-  po.blk_min = blk_min;
+  // PFR_GRAPH=1: repeated sweeps captured into and replayed from a hipGraph (off by default: bitwise the same
+  // results and the host's enqueue of a 512-frequency sweep 427 -> 75 us, but 512 frequencies within the spread
+  // and 4,096 frequencies 1 % slower on the device, 67.0-67.6k -> 66.5-66.8k, gpurun_out/r6r_e4096)
+  s->graph_mode = knob("PFR_GRAPH", 0, 0, 1);
   s->n = S.n;
   s->nnz = S.nnz;
   s->Fc = round64(max_batch);
-  // the same for the bottom-up chain's pivot blocks (k_lsolve_rl_z), on chunks of up to 1,024 frequencies: 512-
-  // frequency sweeps forward solves 1.65 -> 1.33 ms per step, 41.6k against 38.9-39.7k freq-solves/s; on 2,048-
-  // frequency chunks 0.37 -> 0.50 ms per sweep (four slices x 128 groups of 16 frequencies each stage the frontal
-  // index chains: profiles/EXPERIMENTS.md, round 6)
-  s->ls_rl = knob("PFR_LS_RL", s->Fc <= 1024 ? 1 : 0, 0, 1);
-  // the pipelined L21 prefix on launches of fewer than 8,000 waves in chunks of <= 1,024 frequencies (the narrow
-  // levels of C4's per-rank sweeps: 512 frequencies 35.3-35.7k -> 36.2-36.6k freq-solves/s; 2,048-frequency
-  // chunks unchanged, profiles/r04/offdiag_layout/pu3_*)
-  s->off_pu_waves = knob("PFR_OFF_PU_WAVES", s->Fc <= 1024 ? 8000 : 0, 0, 1 << 30);
   s->level_ptr = S.level_ptr;
-  s->level_maxf = S.level_maxf;
   s->perm = S.perm;
   s->iperm = S.iperm;
-  for (int m : S.level_maxf) s->level_W.push_back(pfr::waves_for(m));
-  // the launch plan (host, plan.cpp): every record array the kernels gather through, level by level
+  // the launch plan (host, plan.cpp): every record array the kernels gather through, level by level, and the
+  // launch schedule of every level (no front reached yet: set_reach below)
+  const pfr::Knobs knobs = pfr::knobs_from_env(s->Fc);
   pfr::Plan pl;
   std::string perr;
-  if (pfr::build_plan(S, po, pl, perr)) return bail(fail(PFR_ERR_ARG, perr));
+  if (pfr::build_plan(S, knobs.blk_min, pl, perr)) return bail(fail(PFR_ERR_ARG, perr));
   s->sym = pl.sym;
-  s->level_maxns = pl.level_maxns;
   s->tile_ptr = pl.tile_ptr;
   s->blk_ptr = pl.blk_ptr;
   s->asm_ptr = pl.asm_ptr;
   s->item_ptr = pl.item_ptr;
   s->lev_bytes = pl.lev_bytes;
-  // PFR_FRONT0=0: level 0 through the four class kernels instead of the fused k_front0 (tests/test_gpu_bitwise.py
-  // checks the two give the same factors bit for bit)
-  s->fused0 = pl.fused0 && knob("PFR_FRONT0", 1, 0, 1);
-  // PFR_GRAPH=1: repeated sweeps captured into and replayed from a hipGraph (off by default: bitwise the same
-  // results and the host's enqueue of a 512-frequency sweep 427 -> 75 us, but 512 frequencies within the spread
-  // and 4,096 frequencies 1 % slower on the device, 67.0-67.6k -> 66.5-66.8k, gpurun_out/r6r_e4096)
-  s->graph_mode = knob("PFR_GRAPH", 0, 0, 1);
-  s->n_f0 = (int)pl.f0_front.size();
-  s->f0_small = pl.f0_small;
+  s->sched = pfr::level_schedule(S, pl, s->Fc, knobs, s->reach_ptr);
+  const bool fused0 = s->sched.factor[0].fused0;
   Front* d_fronts = nullptr;
   int rc = PFR_OK;
   std::vector<Front> fv(S.fronts);
@@ -950,7 +830,7 @@ int pfr_solver_create(const pfr_symbolic* sym, const int32_t* colptr, const int3
       (rc = s->up_rec(&s->d_asm_x, pl.asm_x, z2)) || (rc = s->up_rec(&s->d_items, pl.items, z4)) ||
       (rc = s->up_rec(&s->d_orec, pl.orec, n2)) || (rc = s->up(&s->d_oxp, pl.oxp)) || (rc = s->up_rec(&s->d_ox, pl.ox, z2)))
     return bail(rc);
-  if (s->fused0 && ((rc = s->up(&s->d_f0_front, pl.f0_front)) || (rc = s->up(&s->d_f0_ptr, pl.f0_ptr)) ||
+  if (fused0 && ((rc = s->up(&s->d_f0_front, pl.f0_front)) || (rc = s->up(&s->d_f0_ptr, pl.f0_ptr)) ||
                     (rc = s->up(&s->d_f0_nz, pl.f0_nz))))
     return bail(rc);
   std::vector<int32_t> cp(colptr, colptr + S.n + 1), ri(rowind, rowind + S.nnz);
@@ -1013,6 +893,44 @@ void pfr_solver_destroy(pfr_solver* s) {
 }
 
 int32_t pfr_solver_max_batch(const pfr_solver* s) { return s ? (int32_t)s->Fc : 0; }
+
+namespace {
+// the six tables of a schedule, one after the other (include/pfr.h)
+int schedule_out(const pfr::Schedule& sc, int32_t* dst, int64_t cap) {
+  static_assert(pfr::schedule_cols<pfr::FactorLevel>() == PFR_SCHED_FACTOR_COLS &&
+                    pfr::schedule_cols<pfr::PairLevel>() == PFR_SCHED_PAIR_COLS &&
+                    pfr::schedule_cols<pfr::ChainLevel>() == PFR_SCHED_CHAIN_COLS &&
+                    pfr::schedule_cols<pfr::SolveLevel>() == PFR_SCHED_SOLVE_COLS,
+                "include/pfr.h documents the records' columns");
+  if (!dst || cap < (int64_t)sc.factor.size() * PFR_SCHED_COLS * 4) return fail(PFR_ERR_ARG, "destination too small");
+  auto put = [&](const auto& v) {
+    const size_t bytes = v.size() * sizeof(v[0]);
+    if (bytes) std::memcpy(dst, v.data(), bytes);
+    dst += bytes / 4;
+  };
+  put(sc.factor);
+  put(sc.pair);
+  put(sc.chain);
+  for (const auto& v : sc.solve) put(v);
+  return PFR_OK;
+}
+}  // namespace
+
+int pfr_symbolic_schedule(const pfr_symbolic* sym, int32_t max_batch, int32_t* dst, int64_t cap) {
+  if (!sym || max_batch <= 0) return fail(PFR_ERR_ARG, "bad arguments");
+  const int64_t Fc = round64(max_batch);
+  const pfr::Knobs knobs = pfr::knobs_from_env(Fc);
+  pfr::Plan pl;
+  std::string perr;
+  if (pfr::build_plan(sym->S, knobs.blk_min, pl, perr)) return fail(PFR_ERR_ARG, perr);
+  const std::vector<int32_t> all[2] = {sym->S.level_ptr, sym->S.level_ptr};   // every front reached
+  return schedule_out(pfr::level_schedule(sym->S, pl, Fc, knobs, all), dst, cap);
+}
+
+int pfr_solver_schedule(const pfr_solver* s, int32_t* dst, int64_t cap) {
+  if (!s) return fail(PFR_ERR_ARG, "null solver");
+  return schedule_out(s->sched, dst, cap);
+}
 
 int pfr_set_timing(pfr_solver* s, int32_t enable) {
   if (!s) return fail(PFR_ERR_ARG, "null solver");
@@ -1077,11 +995,10 @@ int pfr_last_kernel_timings(const pfr_solver* s, double* ms, int64_t* launches) 
   for (int c = 0; c < s->n_tev; ++c) {
     if (!s->tev[c].used[0]) continue;
     for (int l = 0; l < L; ++l) {
-      int work[pfr::NKC] = {s->asm_ptr[l + 1] - s->asm_ptr[l], s->level_ptr[l + 1] - s->level_ptr[l],
-                            s->item_ptr[l + 1] - s->item_ptr[l], s->blk_ptr[l + 1] - s->blk_ptr[l],
-                            s->tile_ptr[l + 1] - s->tile_ptr[l]};
+      const pfr::FactorLevel& r = s->sched.factor[l];
+      int work[pfr::NKC] = {r.nasm, r.nf, r.nitems, r.nblocks, r.ntiles};
       if (l == 0 && s->tev[c].f0) {   // the fused bottom level: one or two k_front0 launches, all in class 0
-        work[0] = (s->f0_small > 0) + (s->n_f0 > s->f0_small);
+        work[0] = (r.f0_small > 0) + (r.nf > r.f0_small);
         for (int k = 1; k < pfr::NKC; ++k) work[k] = 0;
       }
       for (int k = 0; k < pfr::NKC; ++k) {

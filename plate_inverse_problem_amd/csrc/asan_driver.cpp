@@ -3,7 +3,9 @@
 // and pfr_solver_create this pfr::build_plan (api.cpp); tests/test_asan_host.py feeds it the plate patterns with
 // every ordering option the engine uses, compares the statistics with libpfr's, and has every plan checked
 // (pfr::check_plan) for every engine shape: chunks of 64 .. 4,096 frequencies (one or two lanes split a sweep
-// into such chunks), Schur block thresholds and solve split targets.
+// into such chunks), Schur block thresholds and solve split targets.  For each shape it also builds the launch
+// schedule (pfr::level_schedule, the records the level loops launch) under the environment's knobs, once with every
+// front reached and once with the reach of a single leaf row, and has every record checked (pfr::check_schedule).
 //
 // Input file (little-endian): int32 n, int64 nnz, int32 colptr[n + 1], int32 rowind[nnz],
 // int32 n_last, int32 last[n_last].  Each further argument is one option set
@@ -64,20 +66,31 @@ int main(int argc, char** argv) {
     // launch plans of every engine shape
     int checked = 0;
     std::string err;
+    std::vector<int32_t> foc(S.n, -1), par, rows, mark, list, ptr;   // reach lists: front of each pivot column, parents
+    for (size_t t = 0; t < S.fronts.size(); ++t) {
+      par.push_back(S.fronts[t].parent);
+      for (int a = 0; a < S.fronts[t].ns; ++a) foc[S.fronts[t].col0 + a] = (int32_t)t;
+    }
+    // the reaches the schedules are built for: every front, and the ancestors of one leaf row
+    pfr::reach_lists(foc, par, S.level_ptr, S.level_fronts, {S.fronts[S.level_fronts[0]].col0}, mark, list, ptr);
+    const std::vector<int32_t> reach_all[2] = {S.level_ptr, S.level_ptr}, reach_leaf[2] = {ptr, ptr};
     const int blk_mins[] = {24, 0, 4};
     const int splits[] = {256, 0, 1000000};
     const int64_t chunks[] = {64, 512, 1024, 2048, 4096};
     for (int bm : blk_mins) {
-      pfr::PlanOptions po;
-      po.blk_min = bm;
       pfr::Plan P;
-      if (pfr::build_plan(S, po, P, err)) {
+      if (pfr::build_plan(S, bm, P, err)) {
         printf("plan error blk_min=%d: %s\n", bm, err.c_str());
         goto next;
       }
       for (int64_t Fc : chunks)
         for (int sp : splits) {
-          const std::string e = pfr::check_plan(S, P, Fc, sp);
+          pfr::Knobs k = pfr::knobs_from_env(Fc);
+          k.blk_min = bm;
+          k.split_target = sp;
+          std::string e = pfr::check_plan(S, P, Fc);
+          for (const auto& reach : {&reach_all, &reach_leaf})
+            if (e.empty()) e = pfr::check_schedule(S, P, pfr::level_schedule(S, P, Fc, k, *reach));
           if (!e.empty()) {
             printf("plan error blk_min=%d Fc=%lld split=%d: %s\n", bm, (long long)Fc, sp, e.c_str());
             goto next;
@@ -87,11 +100,6 @@ int main(int argc, char** argv) {
     }
     {
       // reach lists of the loss support (the last nodes, when given) and of every 97th row
-      std::vector<int32_t> foc(S.n, -1), par, rows, mark, list, ptr;
-      for (size_t t = 0; t < S.fronts.size(); ++t) {
-        par.push_back(S.fronts[t].parent);
-        for (int a = 0; a < S.fronts[t].ns; ++a) foc[S.fronts[t].col0 + a] = (int32_t)t;
-      }
       for (int32_t v : last) rows.push_back(S.iperm[v]);
       for (int i = 0; i < S.n; i += 97) rows.push_back(i);
       pfr::reach_lists(foc, par, S.level_ptr, S.level_fronts, rows, mark, list, ptr);

@@ -1461,7 +1461,7 @@ __device__ __forceinline__ void gather_frontal(const DevPattern& P, const Front&
 // diagonal block solved by wave 0 in registers (its loads independent of the chain), the
 // later pivot rows updated by all waves.  Update rows: V(i) -= L21(i, :) y in ONE
 // read-modify-write per row, SRB rows per wave, y in chunks of SKC.
-constexpr int SRB = 4, SKC = 8;
+constexpr int SKC = 8;   // SRB: plan.hpp
 
 // Pivot blocks of the solves: every load unconditional (indices clamped into the block) and the
 // entries past the block masked arithmetically.  A load under a runtime condition -- even a
@@ -1698,7 +1698,7 @@ __global__ __launch_bounds__(256) void k_lsolve_rows_z(DevPattern P, LSlices S, 
 // workgroup = LRC_SR update rows of one front x one frequency group x one slice, its LRC_W waves each summing every
 // LRC_W-th chunk of LRC_SK pivot columns, the partial sums added in wave order through LDS (k_lsolve_rows_z: each
 // wave's rows walk all ns columns, a dependent load round per 8 columns).
-constexpr int LRC_SR = 4, LRC_SK = 8, LRC_W = 4;
+constexpr int LRC_SK = 8;   // LRC_SR, LRC_W: plan.hpp
 __global__ __launch_bounds__(64 * LRC_W) void k_lsolve_rows_zc(DevPattern P, LSlices S, const cplx* __restrict__ F,
                                                               int64_t Fc, int RB) {
   int bx;
@@ -2091,11 +2091,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(WPE))) void
 // trips per block: the paired pass's 28 narrow levels 1.06 -> 0.67 ms per 2,048-frequency chunk.  The 16-frequency workgroups also give the narrow levels 4x the workgroups.
 // dst[v] (and dst2 for vector 0 when not NULL): the solution's pivot rows (already offset by the first pivot row and the lane's
 // frequency).
-constexpr int RL_Q = 16, RL_WMAX = 8, RL_RING = 16;   // ring entries per lane: PF = RL_RING / RPL pivots ahead
-// rows per lane slot for a level whose largest pivot block is maxns (1, 2 or 4: maxns <= 128), and the waves
-// (RL_WMAX and rl_rpl are restated in tests/synthetic.py dispatch_classes)
-inline int rl_rpl(int maxns) { return maxns <= 4 * RL_WMAX ? 1 : maxns <= 8 * RL_WMAX ? 2 : 4; }
-inline int rl_waves(int maxns) { return std::min(RL_WMAX, (maxns + 4 * rl_rpl(maxns) - 1) / (4 * rl_rpl(maxns))); }
+// (RL_Q, RL_WMAX, the rows per lane slot rl_rpl and the waves rl_waves of a level: plan.hpp)
+constexpr int RL_RING = 16;   // ring entries per lane: PF = RL_RING / RPL pivots ahead
 template <bool UP, int NV, int RPL, int PF>
 __device__ __forceinline__ void tri_rl16(const cplx* __restrict__ base, int f, int ns, int64_t Fc, int w, int W,
                                          int lane, const bool (&act)[NV], cplx (&acc)[NV][RPL],
@@ -2383,7 +2380,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NSM <= 4 ? 
 // UPC_W-th chunk of UPC_SK update columns for those rows (each chunk's gathers and L21 loads independent of the
 // others), the partial sums added in wave order through LDS.  k_usolve2_upd gives each wave a row pair and the
 // whole column range: r / 4 dependent load rounds per wave (16-18 on the narrow levels of C3, 22-64 us per level).
-constexpr int UPC_SR = 2, UPC_SK = 8, UPC_W = 8;
+constexpr int UPC_SK = 8;   // UPC_SR, UPC_W: plan.hpp
 __global__ __launch_bounds__(64 * UPC_W) void k_usolve2_updc(DevPattern P, const int* __restrict__ lvl,
                                                             const cplx* __restrict__ F, int64_t Fc, UPair A, UPair B,
                                                             int RB) {
@@ -3616,28 +3613,28 @@ void launch_assemble(int mode, const int4* recs, int nrec, const int* xptr, cons
   }, pick<0, 1>(mode), flag(mode == 0 && op.pop.member));
 }
 
-void launch_factor_lds(const DevPattern& P, const int* lvl, int nfronts, int maxns, double2* F, int64_t Fc, int* flags,
+void launch_factor_lds(const DevPattern& P, const int* lvl, const FactorLevel& r, double2* F, int64_t Fc, int* flags,
                        hipStream_t st) {
-  const size_t lds = (size_t)fac_lds_bytes(maxns);
+  const size_t lds = (size_t)fac_lds_bytes(r.maxns);
   static_assert(FAC_LB == 8, "fac_lds_bytes: 8 W columns per row");
   // dynamic LDS beyond the default 64 KiB (up to 64 pivots: 37 KiB; headroom)
   static const bool attr = dyn_lds(reinterpret_cast<const void*>(&k_factor_sym_lds), 160 * 1024, "k_factor_sym_lds");
   if (!dyn_ok(attr, "k_factor_sym_lds")) return;
-  LAUNCH_DYN(k_factor_sym_lds, dim3((unsigned)(nfronts * Fc)), dim3(256), lds, st, P, lvl, F, Fc, flags, maxns);
+  LAUNCH_DYN(k_factor_sym_lds, dim3((unsigned)(r.nf * Fc)), dim3(256), lds, st, P, lvl, F, Fc, flags, r.maxns);
 }
 
-void launch_factor(bool sym, const DevPattern& P, const int* lvl, int nfronts, int W, int ngroups, double2* F,
-                   int64_t Fc, int* flags, hipStream_t st, int G) {
+void launch_factor(bool sym, const DevPattern& P, const int* lvl, const FactorLevel& r, int ngroups, double2* F,
+                   int64_t Fc, int* flags, hipStream_t st) {
   if (!sym) {
-    LAUNCH(k_factor_level<true>, dim3(nfronts, ngroups * FAC_G), dim3(64 * W), st, P, lvl, F, Fc, flags);
+    LAUNCH(k_factor_level<true>, dim3(r.nf, ngroups * FAC_G), dim3(64 * r.waves), st, P, lvl, F, Fc, flags);
     return;
   }
-  with_int<8, 4, FAC_G>(G, [&](auto g) {
-    LAUNCH(k_factor_sym<CV(g)>, dim3(nfronts, ngroups * CV(g)), dim3(64 * W), st, P, lvl, F, Fc, flags);
+  with_int<8, 4, FAC_G>(r.G, [&](auto g) {
+    LAUNCH(k_factor_sym<CV(g)>, dim3(r.nf, ngroups * CV(g)), dim3(64 * r.waves), st, P, lvl, F, Fc, flags);
   });
 }
 
-void launch_front0(const DevPattern& P, const int* fl, int nfronts, int nsmall, const int* fptr, const int* fnz,
+void launch_front0(const DevPattern& P, const int* fl, const FactorLevel& r, const int* fptr, const int* fnz,
                    int ngroups, double2* F, int64_t Fc, const ChunkOp& op, int* flags, hipStream_t st) {
   // the fronts [n0, n0 + cnt) of the list with NS pivot columns in registers
   auto part = [&](auto ns, int n0, int cnt) {
@@ -3647,31 +3644,31 @@ void launch_front0(const DevPattern& P, const int* fl, int nfronts, int nsmall, 
              Fc, op.freqs, op.K, op.M, flags, op.pop);
     });
   };
-  part(std::integral_constant<int, 2>{}, 0, nsmall);
-  part(std::integral_constant<int, F0_NS>{}, nsmall, nfronts - nsmall);
+  part(std::integral_constant<int, 2>{}, 0, r.f0_small);
+  part(std::integral_constant<int, F0_NS>{}, r.f0_small, r.nf - r.f0_small);
 }
 
-void launch_offdiag(int mode, const DevPattern& P, const int4* items, int nitems, const int2* orec, const int* oxp,
-                    const int2* ox, int ngroups, double2* F, int64_t Fc, const ChunkOp& op, const double2* data, int64_t ds,
-                    int nvalid, int maxns, hipStream_t st, bool pipelined) {
+void launch_offdiag(int mode, const DevPattern& P, const int4* items, const FactorLevel& r, const int2* orec,
+                    const int* oxp, const int2* ox, int ngroups, double2* F, int64_t Fc, const ChunkOp& op,
+                    const double2* data, int64_t ds, int nvalid, hipStream_t st) {
+  const int nitems = r.nitems;
   if (nitems <= 0) return;
-  const bool small = maxns <= 8;
   static_assert(OB >= 8, "the SMALL variant covers pivot blocks of up to 8");
-  // pipelined: the prefix loop with the next pivot's loads issued before the current pivot's products (the
-  // narrow levels, where few waves are resident)
+  // off_pu 3: the prefix loop with the next pivot's loads issued before the current pivot's products (the
+  // narrow levels, where few waves are resident; operator form only)
   dispatch([&](auto md, auto sm, auto pu, auto pop) {
     if constexpr ((CV(pu) == 2 || (CV(md) == 0 && !CV(sm))) && (CV(md) == 0 || !CV(pop)))
       LAUNCH((k_offdiag_level<CV(md), CV(sm), CV(pu), CV(pop)>), dim3((nitems + 3) / 4, ngroups * OFF_G), dim3(256), st, P,
              items, nitems, orec, oxp, ox, F, Fc, op.freqs, op.K, op.M, data, ds, nvalid, op.pop);
-  }, pick<0, 1>(mode), flag(small), pick<2, 3>(mode == 0 && !small && pipelined ? 3 : 2),
-     flag(mode == 0 && op.pop.member));
+  }, pick<0, 1>(mode), flag(r.off_small), pick<2, 3>(mode == 0 ? r.off_pu : 2), flag(mode == 0 && op.pop.member));
 }
 
-void launch_solve(int which, int rhs_mode, bool sym, const DevPattern& P, const int* lvl, int nfronts, int W, int ngroups,
+void launch_solve(int which, int rhs_mode, bool sym, const DevPattern& P, const int* lvl, const SolveLevel& r, int ngroups,
                   const double2* F, int64_t Fc, double2* WV, const RhsArgs& R, const PopArgs& pop, const double2* Yin,
-                  double2* Out, const int* reach, hipStream_t st, int split, const int* glist) {
+                  double2* Out, const int* reach, hipStream_t st, const int* glist) {
+  const int nfronts = r.nf, split = which == 0 ? r.split_L : which == 1 ? r.split_U : 1;
   if (nfronts <= 0) return;
-  dim3 g(nfronts, ngroups), b(64 * W);
+  dim3 g(nfronts, ngroups), b(64 * r.waves);
   const dim3 gs(nfronts * split, ngroups), bs(64 * SPLIT_W);
   const int rs = split > 1;
   switch (which) {
@@ -3701,26 +3698,23 @@ void launch_solve(int which, int rhs_mode, bool sym, const DevPattern& P, const 
   }
 }
 
-void launch_lsolve_multi(int rhs_mode, const DevPattern& P, int nslices, const int* const* lvl, const int* nf, int W,
+void launch_lsolve_multi(int rhs_mode, const DevPattern& P, int nslices, const int* const* lvl, const ChainLevel& r,
                          int ngroups, const double2* F, int64_t Fc, double2* const* WV, const RhsArgs* rd,
-                         const PopArgs& pop, double2* const* Y, const int* const* reach, hipStream_t st, int split,
-                         bool nar, int maxns, int maxf, bool rl) {
+                         const PopArgs& pop, double2* const* Y, const int* const* reach, hipStream_t st) {
   LSlices S{};
-  int nmax = 0;
   for (int z = 0; z < nslices; ++z) {
     S.lvl[z] = lvl[z];
-    S.nf[z] = nf[z];
+    S.nf[z] = z == 0 ? r.nf0 : r.nf1;
     S.WV[z] = WV[z];
     S.Y[z] = Y[z];
     S.reach[z] = reach[z];
     S.R[z] = rd[z];
-    nmax = std::max(nmax, nf[z]);
   }
+  const int nmax = r.nmax;
   if (nmax <= 0) return;
-  const dim3 g(nmax, ngroups, nslices), b(64 * W);
-  const int rs = split > 1;
-  if (rl && maxns > 16 * RL_WMAX) rl = false;   // k_lsolve_rl_z: at most 4 rows per lane slot
-  if (rs && nar && !rl) {
+  const dim3 g(nmax, ngroups, nslices), b(64 * r.waves);
+  const int rs = r.rows != ROWS_NONE;
+  if (r.form == CHAIN_NAR) {
     const auto raise = [](auto* k, const char* name) {
       return dyn_lds(reinterpret_cast<const void*>(k), (int)LS_NAR_DYN_MAX, name);
     };
@@ -3732,23 +3726,21 @@ void launch_lsolve_multi(int rhs_mode, const DevPattern& P, int nslices, const i
   }
   // a population sweep (pop, the group table): the POP forms, slice 0's rhs with the member's beta
   dispatch([&](auto rh, auto pp) {
-    if (rs && nar && rl) {
-      with_int<1, 2, 4>(rl_rpl(maxns), [&](auto rp) {
-        LAUNCH((k_lsolve_rl_z<CV(rh), CV(rp), CV(pp)>), dim3(nmax, (unsigned)(Fc / RL_Q), nslices),
-               dim3(64 * rl_waves(maxns)), st, P, S, F, Fc, pop);
+    if (r.form == CHAIN_RL) {
+      with_int<1, 2, 4>(r.rpl, [&](auto rp) {
+        LAUNCH((k_lsolve_rl_z<CV(rh), CV(rp), CV(pp)>), dim3(nmax, (unsigned)(Fc / RL_Q), nslices), b, st, P, S, F, Fc,
+               pop);
       });
-    } else if (rs && nar) {
-      LAUNCH_DYN((k_lsolve_level_z<CV(rh), true, CV(pp)>), g, b, (size_t)maxns * 64 * 16, st, P, S, F, Fc, rs, pop);
+    } else if (r.form == CHAIN_NAR) {
+      LAUNCH_DYN((k_lsolve_level_z<CV(rh), true, CV(pp)>), g, b, (size_t)r.lds_bytes, st, P, S, F, Fc, rs, pop);
     } else {
       LAUNCH((k_lsolve_level_z<CV(rh), false, CV(pp)>), g, b, st, P, S, F, Fc, rs, pop);
     }
   }, pick<0, 3>(rhs_mode), flag(pop.member != nullptr));
-  if (rs && nar) {
-    const int RB = (std::max(1, maxf - 1) + LRC_SR - 1) / LRC_SR;
-    LAUNCH(k_lsolve_rows_zc, dim3(nmax * RB, ngroups, nslices), dim3(64 * LRC_W), st, P, S, F, Fc, RB);
-  } else if (rs) {
-    LAUNCH(k_lsolve_rows_z, dim3(nmax * split, ngroups, nslices), dim3(64 * SPLIT_W), st, P, S, F, Fc, split);
-  }
+  if (r.rows == ROWS_ZC)
+    LAUNCH(k_lsolve_rows_zc, dim3(nmax * r.RB, ngroups, nslices), dim3(64 * LRC_W), st, P, S, F, Fc, r.RB);
+  else if (r.rows == ROWS_Z)
+    LAUNCH(k_lsolve_rows_z, dim3(nmax * r.split, ngroups, nslices), dim3(64 * SPLIT_W), st, P, S, F, Fc, r.split);
 }
 
 void launch_fn_dot(const int2* rows, int nrows, const double2* F, const double2* Yb, const double2* const* Yk, int64_t Fc,
@@ -3768,42 +3760,38 @@ void launch_fn_combine(const int* rows, int nrows, const double2* fcoef, double2
   LAUNCH(k_fn_combine, dim3(nb, (unsigned)(Fc / 64)), dim3(256), st, rows, nrows, fcoef, Yk[0], Yk[1], Yk[2], Fc);
 }
 
-void launch_usolve2(const DevPattern& P, const int* lvl, int nfronts, int W, bool small, int ngroups,
-                    const double2* F, int64_t Fc, const double2* Y0, double2* X0, const int* reach0, const int* skip0,
-                    const double2* Y1, double2* X1, const int* reach1, hipStream_t st, int split, int tiny,
-                    bool nar, int maxns, bool rl) {
+void launch_usolve2(const DevPattern& P, const int* lvl, const PairLevel& r, int ngroups, const double2* F, int64_t Fc,
+                    const double2* Y0, double2* X0, const int* reach0, const int* skip0, const double2* Y1, double2* X1,
+                    const int* reach1, hipStream_t st) {
+  const int nfronts = r.nf;
   if (nfronts <= 0) return;
-  if (rl && maxns > 16 * RL_WMAX) rl = false;   // k_usolve2_rl: at most 4 rows per lane slot
-  // nar && !rl: the column-split update part (k_usolve2_updc), then k_usolve2_level's pivot block
   UPair a{Y0, X0, reach0, skip0}, b{Y1, X1, reach1, nullptr};
-  if (tiny > 0 && split <= 1) {
-    // every pivot block of the level <= tiny (4 or 8): one wave per (front, group)
-    with_int<4, 8>(tiny <= 4 ? 4 : 8, [&](auto t) {
-      LAUNCH((k_usolve2_tiny<CV(t)>), dim3((unsigned)((nfronts + 3) / 4), ngroups), dim3(256), st, P, lvl, nfronts, F, Fc,
-             a, b);
+  if (r.form == PAIR_TINY4 || r.form == PAIR_TINY8) {
+    // every pivot block of the level <= 4 or 8: one wave per (front, group)
+    with_int<4, 8>(r.form == PAIR_TINY4 ? 4 : 8, [&](auto t) {
+      LAUNCH((k_usolve2_tiny<CV(t)>), dim3((unsigned)((nfronts + 3) / 4), ngroups), dim3(64 * r.waves), st, P, lvl, nfronts,
+             F, Fc, a, b);
     });
     return;
   }
-  dim3 g(nfronts, ngroups), bl(64 * W);
-  const int rs = split > 1;
-  // split > 1: the pivot rows' update part over `split` workgroups per front first (the small-front
-  // register shape: many short waves)
-  if (rs && nar) {
-    const int RB = (maxns + UPC_SR - 1) / UPC_SR;
-    LAUNCH(k_usolve2_updc, dim3(nfronts * RB, ngroups), dim3(64 * UPC_W), st, P, lvl, F, Fc, a, b, RB);
-  } else if (rs) {
-    LAUNCH((k_usolve2_upd<true, 2, 4>), dim3(nfronts * split, ngroups), dim3(64 * SPLIT_W), st, P, lvl, F, Fc, a, b, split);
-  }
+  const dim3 g(nfronts, ngroups), bl(64 * r.waves);
+  const int rs = r.upd != UPD_NONE;
+  // the pivot rows' update part first: column-split (the narrow levels), or over `split` workgroups per front (the
+  // small-front register shape: many short waves)
+  if (r.upd == UPD_COLS)
+    LAUNCH(k_usolve2_updc, dim3(nfronts * r.RB, ngroups), dim3(64 * UPC_W), st, P, lvl, F, Fc, a, b, r.RB);
+  else if (r.upd == UPD_ROWS)
+    LAUNCH((k_usolve2_upd<true, US2_UPD_SR, 4>), dim3(nfronts * r.split, ngroups), dim3(64 * SPLIT_W), st, P, lvl, F, Fc, a,
+           b, r.split);
   // symmetric mode only (the paired top-down pass serves the symmetric loss + gradient sweep).  Small-front levels:
   // 8 pivot rows per pass share each gathered update-row value, 2 values per chunk, 3 waves/SIMD (18 % less traffic
   // than 2 rows x 4 values at 4 waves/SIMD, the same time: profiles/r04/solve_traffic/)
-  if (rs && nar && rl) {
-    with_int<1, 2, 4>(rl_rpl(maxns), [&](auto rp) {
-      LAUNCH((k_usolve2_rl<CV(rp)>), dim3(nfronts, (unsigned)(Fc / RL_Q)), dim3(64 * rl_waves(maxns)), st, P, lvl, F, Fc,
-             a, b);
+  if (r.form == PAIR_RL) {
+    with_int<1, 2, 4>(r.rpl, [&](auto rp) {
+      LAUNCH((k_usolve2_rl<CV(rp)>), dim3(nfronts, (unsigned)(Fc / RL_Q)), bl, st, P, lvl, F, Fc, a, b);
     });
   } else {
-    with_bool(small, [&](auto sm) {
+    with_bool(r.form == PAIR_SMALL, [&](auto sm) {
       constexpr bool S = CV(sm);
       LAUNCH((k_usolve2_level<true, S ? 8 : 4, S ? 2 : 8, S ? 3 : 2>), g, bl, st, P, lvl, F, Fc, a, b, rs);
     });

@@ -31,21 +31,23 @@ void launch_combine_batch(const double* stiff, int n_stiff, int64_t nnz, const d
 // launch_front0 / launch_offdiag); mode 1: the explicit batch (data, ds, nvalid)
 void launch_assemble(int mode, const int4* recs, int nrec, const int* xptr, const int2* xl, int ngroups, double2* F,
                      int64_t Fc, const ChunkOp& op, const double2* data, int64_t ds, int nvalid, hipStream_t st);
-// G: lane groups per wave of the symmetric kernel (FAC_G, 4 or 8)
-void launch_factor(bool sym, const DevPattern& P, const int* lvl, int nfronts, int W, int ngroups, double2* F, int64_t Fc,
-                   int* flags, hipStream_t st, int G = FAC_G);
-// symmetric A11 LU with the pivot block in LDS (one front x one frequency per workgroup); maxns = the level's
-// largest pivot block (sizes the dynamic LDS: (maxns (maxns + 1) / 2 + 4 maxns) x 16 B)
-void launch_factor_lds(const DevPattern& P, const int* lvl, int nfronts, int maxns, double2* F, int64_t Fc, int* flags,
+// The launchers of a tree level take the level's record of the solver's schedule (plan.hpp: FactorLevel, PairLevel,
+// ChainLevel, SolveLevel) and only map it to a kernel instantiation, grid and block.
+// A11 LU of a level: r.G lane groups per wave of the symmetric kernel, r.waves waves
+void launch_factor(bool sym, const DevPattern& P, const int* lvl, const FactorLevel& r, int ngroups, double2* F, int64_t Fc,
+                   int* flags, hipStream_t st);
+// symmetric A11 LU with the pivot block in LDS (one front x one frequency per workgroup); r.maxns, the level's
+// largest pivot block, sizes the dynamic LDS (fac_lds_bytes)
+void launch_factor_lds(const DevPattern& P, const int* lvl, const FactorLevel& r, double2* F, int64_t Fc, int* flags,
                        hipStream_t st);
-// L21 rows (and U12 columns in general mode) of a level's items; pipelined: the software-pipelined prefix
-// (symmetric, operator-form launches with few waves)
-// the bottom level fused (k_front0, Plan::fused0): fl = level-0 fronts, the first nsmall with <= 2 pivots
-void launch_front0(const DevPattern& P, const int* fl, int nfronts, int nsmall, const int* fptr, const int* fnz,
+// the bottom level fused (k_front0, Plan::fused0): fl = level-0 fronts, the first r.f0_small with <= 2 pivots
+void launch_front0(const DevPattern& P, const int* fl, const FactorLevel& r, const int* fptr, const int* fnz,
                    int ngroups, double2* F, int64_t Fc, const ChunkOp& op, int* flags, hipStream_t st);
-void launch_offdiag(int mode, const DevPattern& P, const int4* items, int nitems, const int2* orec, const int* oxp,
-                    const int2* ox, int ngroups, double2* F, int64_t Fc, const ChunkOp& op, const double2* data, int64_t ds,
-                    int nvalid, int maxns, hipStream_t st, bool pipelined = false);
+// L21 rows (and U12 columns in general mode) of a level's items; r.off_pu 3: the software-pipelined prefix
+// (operator-form launches)
+void launch_offdiag(int mode, const DevPattern& P, const int4* items, const FactorLevel& r, const int2* orec,
+                    const int* oxp, const int2* ox, int ngroups, double2* F, int64_t Fc, const ChunkOp& op,
+                    const double2* data, int64_t ds, int nvalid, hipStream_t st);
 // Schur complement A22 -= L21 U12 for a level's tile list (TM x TN = 4 x 4 tiles)
 void launch_schur(bool sym, const DevPattern& P, const int4* tiles, int ntiles, const int* g1, const int* gxp,
                   const int2* gx, int ngroups, double2* F, int64_t Fc, hipStream_t st);
@@ -53,25 +55,21 @@ void launch_schur(bool sym, const DevPattern& P, const int4* tiles, int ntiles, 
 void launch_schur_blk(const DevPattern& P, const int4* blocks, int nblocks, const int* bg1, const int* bgxp,
                       const int2* bgx, int ngroups, double2* F, int64_t Fc, hipStream_t st);
 // which: 0 = L (bottom-up), 1 = U (top-down), 2 = U^T (bottom-up), 3 = L^T (top-down)
-// split > 1 (L and U solves): the update part of every front (L: the update rows; U: the pivot rows'
-// products with the update-row solution) runs first / last over `split` workgroups of SPLIT_W waves per
+// r.split_L / r.split_U > 1 (L and U solves): the update part of every front (L: the update rows; U: the pivot rows'
+// products with the update-row solution) runs first / last over that many workgroups of SPLIT_W waves per
 // (front, frequency group) -- the top levels' few fronts otherwise pull their L21 blocks through one CU each
 // glist (may be NULL): the groups to solve, REFINE_CAP of them (-1: none), indexed by grid row (pass
 // ngroups = REFINE_CAP); the selective adjoint refinement's solves
 // pop (the chunk operator's): a population sweep's L solve of the operator rhs (rhs_mode 0 / 3) takes its POP form
-void launch_solve(int which, int rhs_mode, bool sym, const DevPattern& P, const int* lvl, int nfronts, int W, int ngroups,
+void launch_solve(int which, int rhs_mode, bool sym, const DevPattern& P, const int* lvl, const SolveLevel& r, int ngroups,
                   const double2* F, int64_t Fc, double2* WV, const RhsArgs& rd, const PopArgs& pop, const double2* Yin,
-                  double2* Out, const int* reach, hipStream_t st, int split = 1, const int* glist = nullptr);
+                  double2* Out, const int* reach, hipStream_t st, const int* glist = nullptr);
 // nslices (<= 4) bottom-up L solves as one chain of launches (blockIdx.z = slice; slice z: the fronts
-// lvl[z][0 .. nf[z]), its work vectors WV[z], rhs rd[z] (rhs_mode 0 or 3 for every slice), solution Y[z]);
+// lvl[z][0 .. r.nf0 or r.nf1), its work vectors WV[z], rhs rd[z] (rhs_mode 0 or 3 for every slice), solution Y[z]);
 // pop (population sweep): slice 0's rhs with the member's beta
-void launch_lsolve_multi(int rhs_mode, const DevPattern& P, int nslices, const int* const* lvl, const int* nf, int W,
+void launch_lsolve_multi(int rhs_mode, const DevPattern& P, int nslices, const int* const* lvl, const ChainLevel& r,
                          int ngroups, const double2* F, int64_t Fc, double2* const* WV, const RhsArgs* rd,
-                         const PopArgs& pop, double2* const* Y, const int* const* reach, hipStream_t st, int split,
-                         bool nar = false,
-                         int maxns = 0, int maxf = 0,    // nar (split > 1): pivot blocks in LDS, update rows
-                                                         // column-split (k_lsolve_level_z<., true>, k_lsolve_rows_zc)
-                         bool rl = true);                // nar + rl: pivot blocks right-looking (k_lsolve_rl_z)
+                         const PopArgs& pop, double2* const* Y, const int* const* reach, hipStream_t st);
 // functional from the bottom-up passes: partial dot products (FN_PARTS x 3 x Fc), the functional / loss
 // / cotangent from them (fcoef: 3 x Fc, G at the support rows), and L^-1 g = sum_k c_k L^-1 a_k in Yk[0]
 void launch_fn_dot(const int2* rows, int nrows, const double2* F, const double2* Yb, const double2* const* Yk, int64_t Fc,
@@ -79,14 +77,10 @@ void launch_fn_dot(const int2* rows, int nrows, const double2* F, const double2*
 void launch_functional_fn(const FunctionalArgs& A, const double2* parts, int64_t Fc, int nvalid, int64_t q0,
                           double* fr_out, double* loss_terms, double2* G, double2* fcoef, hipStream_t st);
 void launch_fn_combine(const int* rows, int nrows, const double2* fcoef, double2* const* Yk, int64_t Fc, hipStream_t st);
-// two top-down U solves in one pass (vector 0 skipped on the fronts flagged in skip0), symmetric
-// mode; small: the low-register variant for levels of small fronts
-void launch_usolve2(const DevPattern& P, const int* lvl, int nfronts, int W, bool small, int ngroups,
-                    const double2* F, int64_t Fc, const double2* Y0, double2* X0, const int* reach0, const int* skip0,
-                    const double2* Y1, double2* X1, const int* reach1, hipStream_t st, int split = 1,
-                    int tiny = 0,     // tiny 4 / 8: the level's pivot blocks all <= tiny (k_usolve2_tiny)
-                    bool nar = false, int maxns = 0,    // nar (split > 1): the update part column-split (k_usolve2_updc)
-                    bool rl = true);                    // nar + rl: pivot blocks right-looking, prefetched (k_usolve2_rl)
+// two top-down U solves in one pass (vector 0 skipped on the fronts flagged in skip0), symmetric mode
+void launch_usolve2(const DevPattern& P, const int* lvl, const PairLevel& r, int ngroups, const double2* F, int64_t Fc,
+                    const double2* Y0, double2* X0, const int* reach0, const int* skip0, const double2* Y1, double2* X1,
+                    const int* reach1, hipStream_t st);
 // Hessian sweep: tangent right-hand sides (rows of the permuted matrix, or of its
 // transpose with accumulate = 1) and the directional derivative of the loss cotangent
 void launch_tangent_spmv(const int* ptr, const int* idx, const int* nzs, int nrows, const double2* Kd,

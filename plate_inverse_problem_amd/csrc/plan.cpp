@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <climits>
 #include <cstdio>
+#include <cstdlib>
 #include <utility>
 
 namespace pfr {
@@ -72,7 +73,7 @@ void each_more(const std::vector<std::pair<int32_t, int32_t>>& more, int32_t key
 
 }  // namespace
 
-int build_plan(const Symbolic& S, const PlanOptions& o, Plan& P, std::string& err) {
+int build_plan(const Symbolic& S, int blk_min, Plan& P, std::string& err) {
   P = Plan();
   if (S.max_front > MAX_FRONT) {
     err = "front larger than MAX_FRONT (plan.hpp)";
@@ -108,7 +109,7 @@ int build_plan(const Symbolic& S, const PlanOptions& o, Plan& P, std::string& er
       const Front& F = S.fronts[t];
       const int r = F.f - F.ns;
       a22_sources(S, kids, t, sym, first, more);
-      if (sym && o.blk_min > 0 && r >= o.blk_min) {
+      if (sym && blk_min > 0 && r >= blk_min) {
         // blocks touching the lower triangle; wave w owns the 4 x 4 tile (w / 4, w % 4)
         constexpr int B = SCHUR_BLK, BC = SCHUR_BLK, tcw = BC / 4;
         for (int i0 = 0; i0 < r; i0 += B)
@@ -385,7 +386,7 @@ void reach_lists(const std::vector<int32_t>& front_of_col, const std::vector<int
   }
 }
 
-std::string check_plan(const Symbolic& S, const Plan& P, int64_t Fc, int split_target) {
+std::string check_plan(const Symbolic& S, const Plan& P, int64_t Fc) {
   char buf[256];
   auto bad = [&](const char* what, int64_t at, int64_t v, int64_t lim) {
     snprintf(buf, sizeof buf, "%s: entry %lld = %lld outside [0, %lld)", what, (long long)at, (long long)v, (long long)lim);
@@ -485,9 +486,6 @@ std::string check_plan(const Symbolic& S, const Plan& P, int64_t Fc, int split_t
     if (P.tile_ptr[l] > P.tile_ptr[l + 1] || P.blk_ptr[l] > P.blk_ptr[l + 1] || P.item_ptr[l] > P.item_ptr[l + 1] ||
         P.asm_ptr[l] > P.asm_ptr[l + 1])
       return bad("level range order", l, P.tile_ptr[l], P.tile_ptr[l + 1]);
-  // A11 in LDS (k_factor_sym_lds) on the levels whose pivot blocks reach at most 64
-  for (int l = 0; l < L; ++l)
-    if (P.level_maxns[l] <= 64 && fac_lds_bytes(P.level_maxns[l]) > LDS_BYTES) return bad("A11 LDS", l, P.level_maxns[l], 64);
   // Dirichlet lists
   const Workspace W = workspace(S, Fc, P.n_crow);
   for (size_t d = 0; d < P.dir.size(); ++d)
@@ -518,25 +516,238 @@ std::string check_plan(const Symbolic& S, const Plan& P, int64_t Fc, int split_t
     const int64_t partial = (int64_t)std::max<int64_t>(contract_eg_parts(P.n_uent), Fc / 64) * 18;   // api.cpp's size
     if ((int64_t)contract_eg_parts(P.n_uent) * 18 > partial || (Fc / 64) * 18 > partial) return "gradient partials";
   }
-  // split solve update parts: the rows every (part, wave) walks cover the update rows (L solve) / pivot rows (U
-  // solve) exactly once for every split the launches use
+  return "";
+}
+
+// ---- the launch schedule
+Knobs knobs_from_env(int64_t Fc) {
+  auto knob = [](const char* name, int def, int lo, int hi) {
+    const char* e = getenv(name);
+    return e ? std::max(lo, std::min(hi, atoi(e))) : def;
+  };
+  Knobs k;
+  k.solve_wmax = knob("PFR_SOLVE_WMAX", k.solve_wmax, 1, 8);
+  k.fac_wmax = knob("PFR_FAC_WMAX", k.fac_wmax, 1, 16);
+  k.fac_g_wg = knob("PFR_FAC_G_WG", k.fac_g_wg, 0, 1 << 20);
+  k.fac_gbig = knob("PFR_FAC_GBIG", k.fac_gbig, 2, 8);
+  if (k.fac_gbig != 2 && k.fac_gbig != 8) k.fac_gbig = 4;
+  k.fac_g_ns = knob("PFR_FAC_G_NS", k.fac_g_ns, 0, 1 << 20);
+  k.us2_small = knob("PFR_US2_SMALL", k.us2_small, 0, MAX_FRONT);
+  k.split_target = knob("PFR_SOLVE_SPLIT", k.split_target, 0, 1 << 20);
+  k.us2_nar = knob("PFR_US2_NAR", k.us2_nar, 0, 1 << 30);
+  k.fac_lds = knob("PFR_FAC_LDS", k.fac_lds, -1, 64);
+  k.us2_tiny = knob("PFR_US2_TINY", k.us2_tiny, 0, 8);
+  k.us2_rl = knob("PFR_US2_RL", k.us2_rl, 0, 1);
+  k.ls_rl = knob("PFR_LS_RL", Fc <= 1024 ? 1 : 0, 0, 1);
+  k.off_pu_waves = knob("PFR_OFF_PU_WAVES", Fc <= 1024 ? 8000 : 0, 0, 1 << 30);
+  k.front0 = knob("PFR_FRONT0", k.front0, 0, 1);
+  k.blk_min = knob("PFR_SCHUR_BLK_MIN", k.blk_min, 0, MAX_FRONT);
+  return k;
+}
+
+namespace {
+
+int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+SolveLevel solve_level(const Schedule& sc, int l, int nf) {
+  SolveLevel r{};
+  r.nf = nf;
+  r.level_w = waves_for(sc.level_maxf[l]);
+  // raised (up to solve_wmax) when the launch has too few workgroups to fill the chip -- the sparse passes and the
+  // top levels, which are latency-bound: every wave more takes rows off each wave's chain
+  r.waves = solve_waves(r.level_w, nf, sc.Fc, sc.knobs.solve_wmax);
+  // the update parts split over several workgroups: L solves, and U solves in symmetric mode
+  r.split_L = solve_split(nf, sc.Fc, sc.knobs.split_target);
+  r.split_U = sc.sym ? r.split_L : 1;
+  return r;
+}
+
+}  // namespace
+
+void schedule_reach(Schedule& sc, const std::vector<int32_t> (&reach_ptr)[2]) {
+  const Knobs& k = sc.knobs;
+  const int L = (int)sc.level_nf.size();
+  const int64_t ng = sc.Fc / 64;
+  auto count = [&](int w, int l) { return reach_ptr[w].empty() ? 0 : reach_ptr[w][l + 1] - reach_ptr[w][l]; };
+  sc.chain.assign(L, ChainLevel{});
+  for (int w = 0; w < 2; ++w) sc.solve[SUBSET_REACH0 + w].resize(L);
   for (int l = 0; l < L; ++l) {
-    const int64_t nf = S.level_ptr[l + 1] - S.level_ptr[l];
-    const int split = solve_split(nf, Fc, split_target);
-    if (split < 1 || split > 16) return bad("solve split", l, split, 17);
-    constexpr int SRB = 4, SR = 2;   // rows per step: k_lsolve_rows (SRB), k_usolve2_upd (SR)
-    for (int e = S.level_ptr[l]; e < S.level_ptr[l + 1]; ++e) {
-      const Front& F = S.fronts[S.level_fronts[e]];
-      std::vector<int> seen(F.f, 0);
+    for (int w = 0; w < 2; ++w) sc.solve[SUBSET_REACH0 + w][l] = solve_level(sc, l, count(w, l));
+    ChainLevel& c = sc.chain[l];
+    const int maxns = sc.level_maxns[l];
+    c.nf0 = count(0, l);
+    c.nf1 = count(1, l);
+    c.nmax = std::max(c.nf0, c.nf1);
+    if (c.nmax == 0) continue;
+    c.nsum = c.nf0 + 3 * c.nf1;
+    c.split = solve_split(c.nsum, sc.Fc, k.split_target);
+    c.waves = solve_waves(waves_for(sc.level_maxf[l]), c.nmax, sc.Fc, k.solve_wmax);
+    // the narrow forms need the update rows apart (split > 1) and the largest pivot block in LDS
+    const bool nar = c.split > 1 && c.nsum * ng < k.us2_nar && ls_nar_fits(maxns);
+    c.rows = nar ? ROWS_ZC : c.split > 1 ? ROWS_Z : ROWS_NONE;
+    if (nar) c.RB = ceil_div(std::max(1, sc.level_maxf[l] - 1), LRC_SR);
+    if (nar && k.ls_rl && maxns <= 16 * RL_WMAX) {   // k_lsolve_rl_z: at most 4 rows per lane slot
+      c.form = CHAIN_RL;
+      c.rpl = rl_rpl(maxns);
+      c.waves = rl_waves(maxns);
+    } else if (nar) {
+      c.form = CHAIN_NAR;
+      c.lds_bytes = maxns * 64 * 16;
+    }
+  }
+}
+
+Schedule level_schedule(const Symbolic& S, const Plan& P, int64_t Fc, const Knobs& k,
+                        const std::vector<int32_t> (&reach_ptr)[2]) {
+  Schedule sc;
+  sc.Fc = Fc;
+  sc.knobs = k;
+  sc.sym = P.sym;
+  sc.level_maxns = P.level_maxns;
+  sc.level_maxf = S.level_maxf;
+  const int L = P.L;
+  const int64_t ng = Fc / 64;
+  for (int l = 0; l < L; ++l) sc.level_nf.push_back(S.level_ptr[l + 1] - S.level_ptr[l]);
+  sc.factor.assign(L, FactorLevel{});
+  sc.pair.assign(L, PairLevel{});
+  sc.solve[SUBSET_ALL].resize(L);
+  for (int l = 0; l < L; ++l) {
+    const int nf = sc.level_nf[l], maxns = sc.level_maxns[l];
+    const SolveLevel all = sc.solve[SUBSET_ALL][l] = solve_level(sc, l, nf);
+    FactorLevel& f = sc.factor[l];
+    f.nf = nf;
+    f.maxns = maxns;
+    f.fused0 = l == 0 && P.fused0 && k.front0;
+    f.f0_small = f.fused0 ? P.f0_small : 0;
+    f.lds = P.sym && maxns <= 64 &&
+            (k.fac_lds > 0 ? maxns >= k.fac_lds : k.fac_lds < 0 && maxns >= 16 && nf * ng * FAC_G < k.fac_lds_wg);
+    // lane groups per wave of the symmetric A11 kernel: FAC_G; fac_gbig on the levels with a pivot block of more
+    // than fac_g_ns pivots, whose long chains gain from more row slots per wave (the deep tree's level 25 with its
+    // 76-pivot separator at 2,048 frequencies: 0.61 -> 0.41 ms with 4; the levels of 2-3 fronts of <= 35 pivots
+    // below it were slower with 4); raised to 4 / 8 while the launch has fewer than fac_g_wg workgroups (default off)
+    f.G = (P.sym && maxns > k.fac_g_ns) ? k.fac_gbig : FAC_G;
+    while (P.sym && f.G < 8 && nf * ng * f.G < k.fac_g_wg) f.G *= 2;
+    // panel: enough workgroups (front x 16 frequencies) to fill the chip -> one wave each (no idle waves at the
+    // block barriers); few large fronts -> more waves (symmetric kernel: up to 16 waves -- the top levels' few
+    // fronts are latency-bound, every wave more takes rows off each wave's serial chain)
+    const int64_t wgs = nf * ng * f.G, wfill = (4096 + wgs - 1) / wgs;
+    f.waves = (int)std::max<int64_t>(1, std::min<int64_t>(P.sym ? k.fac_wmax : all.level_w, wfill));
+    f.nasm = P.asm_ptr[l + 1] - P.asm_ptr[l];
+    f.nitems = P.item_ptr[l + 1] - P.item_ptr[l];
+    f.nblocks = P.blk_ptr[l + 1] - P.blk_ptr[l];
+    f.ntiles = P.tile_ptr[l + 1] - P.tile_ptr[l];
+    f.off_small = maxns <= 8;
+    // the software-pipelined L21 prefix on the launches with few waves (symmetric analyses, not the SMALL form)
+    f.off_pu = P.sym && !f.off_small && f.nitems * ng < k.off_pu_waves ? 3 : 2;
+
+    PairLevel& p = sc.pair[l];
+    p.nf = nf;
+    p.small = sc.level_maxf[l] <= k.us2_small;
+    p.tiny = k.us2_tiny > 0 && maxns <= k.us2_tiny ? (maxns <= 4 ? 4 : 8) : 0;
+    const bool nar = nf * ng < k.us2_nar;
+    p.split = nar ? std::max(2, all.split_L) : all.split_L;
+    if (p.tiny > 0 && p.split <= 1) {   // every pivot block of the level <= tiny: one wave per (front, group)
+      p.form = p.tiny == 4 ? PAIR_TINY4 : PAIR_TINY8;
+      p.waves = 4;
+      continue;
+    }
+    p.upd = p.split <= 1 ? UPD_NONE : nar ? UPD_COLS : UPD_ROWS;
+    if (nar) p.RB = ceil_div(maxns, UPC_SR);
+    if (nar && k.us2_rl && maxns <= 16 * RL_WMAX) {   // k_usolve2_rl: at most 4 rows per lane slot
+      p.form = PAIR_RL;
+      p.rpl = rl_rpl(maxns);
+      p.waves = rl_waves(maxns);
+    } else {
+      p.form = p.small ? PAIR_SMALL : PAIR_BIG;
+      p.waves = all.waves;
+    }
+  }
+  schedule_reach(sc, reach_ptr);
+  return sc;
+}
+
+std::string check_schedule(const Symbolic& S, const Plan& P, const Schedule& sc) {
+  char buf[256];
+  auto bad = [&](const char* what, int l, int64_t v, int64_t lim) {
+    snprintf(buf, sizeof buf, "schedule, level %d: %s %lld against %lld", l, what, (long long)v, (long long)lim);
+    return std::string(buf);
+  };
+  const int L = P.L;
+  if ((int)sc.factor.size() != L || (int)sc.pair.size() != L || (int)sc.chain.size() != L) return "schedule levels";
+  for (const auto& v : sc.solve)
+    if ((int)v.size() != L) return "schedule levels";
+  auto waves_ok = [](int w, int hi) { return w >= 1 && w <= hi; };
+  for (int l = 0; l < L; ++l) {
+    const int nf = S.level_ptr[l + 1] - S.level_ptr[l], maxns = P.level_maxns[l], maxf = S.level_maxf[l];
+    const FactorLevel& f = sc.factor[l];
+    const PairLevel& p = sc.pair[l];
+    const ChainLevel& c = sc.chain[l];
+    if (f.nf != nf || p.nf != nf || sc.solve[SUBSET_ALL][l].nf != nf) return bad("fronts", l, f.nf, nf);
+    if (f.maxns != maxns) return bad("largest pivot block", l, f.maxns, maxns);
+    if (f.lds && (maxns > 64 || fac_lds_bytes(maxns) > LDS_BYTES)) return bad("A11 LDS", l, maxns, 64);
+    if (f.fused0 && (l != 0 || !P.fused0 || f.f0_small != P.f0_small)) return bad("fused level", l, f.fused0, 0);
+    if (f.G != 2 && f.G != 4 && f.G != 8) return bad("lane groups", l, f.G, 8);
+    if (!waves_ok(f.waves, 16)) return bad("panel waves", l, f.waves, 16);
+    if (f.off_pu == 3 ? f.off_small != 0 : f.off_pu != 2) return bad("L21 prefix", l, f.off_pu, 3);
+    // the split parts' strides: the rows [lo, hi) of a front, `rows` per step, every one exactly once
+    std::vector<int> seen;
+    auto covered = [&](int lo, int hi, int rows, int split) {
+      seen.assign(std::max(hi, 0), 0);
       for (int part = 0; part < split; ++part)
-        for (int w = 0; w < SPLIT_W; ++w) {
-          for (int i0 = F.ns + SRB * (part * SPLIT_W + w); i0 < F.f; i0 += SRB * SPLIT_W * split)
-            for (int r = 0; r < SRB && i0 + r < F.f; ++r) ++seen[i0 + r];
-          for (int a0 = SR * (part * SPLIT_W + w); a0 < F.ns; a0 += SR * SPLIT_W * split)
-            for (int r = 0; r < SR && a0 + r < F.ns; ++r) ++seen[a0 + r];
-        }
-      for (int a = 0; a < F.f; ++a)
-        if (seen[a] != 1) return bad("split coverage", a, seen[a], 2);
+        for (int w = 0; w < SPLIT_W; ++w)
+          for (int i0 = lo + rows * (part * SPLIT_W + w); i0 < hi; i0 += rows * SPLIT_W * split)
+            for (int r = 0; r < rows && i0 + r < hi; ++r) ++seen[i0 + r];
+      for (int a = lo; a < hi; ++a)
+        if (seen[a] != 1) return false;
+      return true;
+    };
+    auto split_ok = [&](int split, bool pivots, int rows) {   // over every front of the level
+      if (split < 1 || split > 16) return false;
+      for (int e = S.level_ptr[l]; e < S.level_ptr[l + 1]; ++e) {
+        const Front& F = S.fronts[S.level_fronts[e]];
+        if (!(pivots ? covered(0, F.ns, rows, split) : covered(F.ns, F.f, rows, split))) return false;
+      }
+      return true;
+    };
+    // paired top-down
+    if (p.form == PAIR_TINY4 || p.form == PAIR_TINY8) {
+      const int t = p.form == PAIR_TINY4 ? 4 : 8;
+      if (maxns > t || p.tiny != t || p.split > 1 || p.upd != UPD_NONE) return bad("tiny level", l, maxns, t);
+    } else {
+      if ((p.upd == UPD_NONE) != (p.split <= 1)) return bad("paired update part", l, p.upd, p.split);
+      if (p.upd == UPD_ROWS && !split_ok(p.split, true, US2_UPD_SR)) return bad("paired split coverage", l, p.split, 16);
+      if (p.upd == UPD_COLS && p.RB * UPC_SR < maxns) return bad("paired row blocks", l, p.RB * UPC_SR, maxns);
+      if (p.form == PAIR_RL) {
+        if (p.upd != UPD_COLS || maxns > 16 * RL_WMAX || 4 * p.rpl * p.waves < maxns || p.waves > RL_WMAX ||
+            (p.rpl != 1 && p.rpl != 2 && p.rpl != 4))
+          return bad("right-looking paired level", l, 4 * p.rpl * p.waves, maxns);
+      } else if (p.form != (p.small ? PAIR_SMALL : PAIR_BIG)) {
+        return bad("paired form", l, p.form, p.small);
+      }
+    }
+    if (!waves_ok(p.waves, 8)) return bad("paired waves", l, p.waves, 8);
+    // bottom-up chain
+    if (c.nf0 < 0 || c.nf0 > nf || c.nf1 < 0 || c.nf1 > nf || c.nmax != std::max(c.nf0, c.nf1))
+      return bad("chain fronts", l, c.nmax, nf);
+    if (c.nmax > 0) {
+      if (c.nsum != c.nf0 + 3 * c.nf1) return bad("chain slices", l, c.nsum, c.nf0 + 3 * c.nf1);
+      if ((c.rows == ROWS_NONE) != (c.split <= 1)) return bad("chain update rows", l, c.rows, c.split);
+      if ((c.form != CHAIN_PLAIN) != (c.rows == ROWS_ZC)) return bad("chain form", l, c.form, c.rows);
+      if (c.rows == ROWS_Z && !split_ok(c.split, false, SRB)) return bad("chain split coverage", l, c.split, 16);
+      if (c.rows == ROWS_ZC && c.RB * LRC_SR < maxf - 1) return bad("chain row blocks", l, c.RB * LRC_SR, maxf - 1);
+      if (c.form == CHAIN_NAR && (!ls_nar_fits(maxns) || c.lds_bytes != (int64_t)maxns * 64 * 16))
+        return bad("chain LDS", l, c.lds_bytes, LS_NAR_DYN_MAX);
+      if (c.form == CHAIN_RL && (maxns > 16 * RL_WMAX || 4 * c.rpl * c.waves < maxns || c.waves > RL_WMAX ||
+                                 (c.rpl != 1 && c.rpl != 2 && c.rpl != 4)))
+        return bad("right-looking chain level", l, 4 * c.rpl * c.waves, maxns);
+      if (!waves_ok(c.waves, 8)) return bad("chain waves", l, c.waves, 8);
+    }
+    // unpaired passes
+    for (const auto& v : sc.solve) {
+      const SolveLevel& r = v[l];
+      if (r.nf < 0 || r.nf > nf) return bad("solve fronts", l, r.nf, nf);
+      if (!waves_ok(r.waves, 8) || r.level_w > r.waves) return bad("solve waves", l, r.waves, 8);
+      if (!split_ok(r.split_L, false, SRB) || !split_ok(r.split_U, true, SRB)) return bad("solve split coverage", l, r.split_L, 16);
     }
   }
   return "";

@@ -4,8 +4,12 @@
 // device buffer a solver allocates.  HIP-free (plain C++17): pfr_solver_create (api.cpp) uploads a Plan,
 // and the sanitizer driver (asan_driver.cpp, tests/test_asan_host.py) builds plans for every engine shape
 // under -fsanitize=address,undefined and checks each index a launch will use against the buffer it addresses
-// (check_plan).  The launch-geometry functions below are the ones the launchers use (kernels.hip), so the
-// checks and the launches cannot drift apart.
+// (check_plan).  Which kernel form every tree level launches, with what grid, block and LDS size, is decided here
+// too, once per solver: level_schedule turns the launch-shape knobs (Knobs) and the level geometry into one record
+// per pass and level (Schedule).  The level loops of api.cpp walk those records, the launchers (kernels.hip) map
+// a record to a kernel instantiation, check_schedule checks every record, and pfr_symbolic_schedule /
+// pfr_solver_schedule hand the same records to the tests -- so the checks, the tests and the launches cannot drift
+// apart.
 #pragma once
 
 #include <algorithm>
@@ -47,12 +51,19 @@ constexpr int NKC = 5;                        // factorisation kernel classes: a
 constexpr int FN_PARTS_HOST = 16;             // k_fn_dot partials per frequency group (kernels.hip: FN_PARTS)
 constexpr int REFINE_CAP = 4;                 // groups of the selective adjoint refinement per chunk
 constexpr int SPLIT_W = 4;                    // waves per workgroup of the split solve update parts
+constexpr int SRB = 4;                        // rows per step of lsolve_rows / usolve_upd (the split parts' stride)
+constexpr int US2_UPD_SR = 2;                 // pivot rows per step of k_usolve2_upd
+// right-looking pivot-block solves (k_usolve2_rl / k_lsolve_rl_z): RL_Q frequencies per workgroup, at most RL_WMAX
+// waves of 4 row slots, 1 / 2 / 4 rows per lane slot
+constexpr int RL_Q = 16, RL_WMAX = 8;
+inline int rl_rpl(int maxns) { return maxns <= 4 * RL_WMAX ? 1 : maxns <= 8 * RL_WMAX ? 2 : 4; }
+inline int rl_waves(int maxns) { return std::min(RL_WMAX, (maxns + 4 * rl_rpl(maxns) - 1) / (4 * rl_rpl(maxns))); }
+constexpr int UPC_SR = 2, UPC_W = 8;          // k_usolve2_updc: pivot rows per workgroup, waves
+constexpr int LRC_SR = 4, LRC_W = 4;          // k_lsolve_rows_zc: update rows per workgroup, waves
 constexpr int CEG_EW = 8;                     // entries per wave of k_contract_eg
 constexpr int64_t LDS_BYTES = 160 * 1024;
 
 // ---- launch geometry shared by the launchers and the checks
-// (tests/synthetic.py restates FAC_G, LS_NAR_DYN_MAX, waves_for, solve_waves, F0_NS / F0_RM and the knob defaults of
-// api.cpp to prove which launch class each synthetic shape reaches: change them there too)
 inline int residual_parts(int n) { return (int)std::min<int64_t>((n + 3) / 4, 256); }   // k_residual grid.x
 inline int contract_eg_parts(int nent) { return ((nent + CEG_EW - 1) / CEG_EW + 3) / 4; }   // k_contract_eg grid
 // k_contract_q grid.x: at least 16 entries per wave, never more workgroups than k_residual's (kpart holds them)
@@ -85,10 +96,6 @@ inline int solve_waves(int level_w, int64_t nf, int64_t Fc, int wmax) {
 // The bottom level fused (k_front0): symmetric analyses whose level-0 fronts (leaves) all have at most F0_NS pivots
 // and F0_RM update rows -- per (front, frequency) A11, L21 and the update block formed in registers, one pass
 constexpr int F0_NS = 4, F0_RM = 10;
-
-struct PlanOptions {
-  int blk_min = 24;      // PFR_SCHUR_BLK_MIN: update blocks of at least this many rows through the block kernel
-};
 
 struct Plan {
   int L = 0;                             // levels
@@ -140,8 +147,9 @@ struct Workspace {
 };
 Workspace workspace(const Symbolic& S, int64_t Fc, int n_crow);
 
-// Builds the plan; returns 0, or non-zero with err set (a front too large for the kernels, int32 overflow)
-int build_plan(const Symbolic& S, const PlanOptions& o, Plan& P, std::string& err);
+// Builds the plan (blk_min: Knobs::blk_min); returns 0, or non-zero with err set (a front too large for the kernels,
+// int32 overflow)
+int build_plan(const Symbolic& S, int blk_min, Plan& P, std::string& err);
 
 // The fronts holding the given permuted rows and all their ancestors: per-front flags and the marked fronts
 // level by level (level order kept; ptr per level).  front_of_col: the front of each pivot column (permuted).
@@ -151,9 +159,110 @@ void reach_lists(const std::vector<int32_t>& front_of_col, const std::vector<int
                  std::vector<int32_t>& ptr);
 
 // Every index each launch of a solver with chunk Fc takes from the plan, against the buffer it addresses
-// (element ids < factor entries, nz < nnz, record offsets and overflow ranges inside their arrays, LDS sizes,
-// the per-workgroup partial buffers against the grids that write them, the split solve parts covering every
-// row once).  Returns "" or the first violation.
-std::string check_plan(const Symbolic& S, const Plan& P, int64_t Fc, int split_target);
+// (element ids < factor entries, nz < nnz, record offsets and overflow ranges inside their arrays, the
+// per-workgroup partial buffers against the grids that write them).  Returns "" or the first violation.
+std::string check_plan(const Symbolic& S, const Plan& P, int64_t Fc);
+
+// ---- the launch schedule
+// Launch-shape knobs, read from the environment when a solver is created (so that a process can build solvers
+// with different settings, e.g. tests forcing each kernel variant).  The measured-slower variants of rounds 1-4
+// are in git history.
+struct Knobs {
+  int solve_wmax = 8;     // PFR_SOLVE_WMAX: waves per solve workgroup, at most
+  int fac_wmax = 16;      // PFR_FAC_WMAX: waves per A11 LU workgroup, at most
+  int fac_g_wg = 0;       // PFR_FAC_G_WG: k_factor_sym launches below this many workgroups take G = 4 / 8
+  int fac_gbig = 4;       // PFR_FAC_GBIG / PFR_FAC_G_NS: k_factor_sym's lane groups per wave on the levels whose
+  int fac_g_ns = 64;      // largest pivot block exceeds PFR_FAC_G_NS pivots
+  int us2_small = 110;    // PFR_US2_SMALL: largest front of a level the paired top-down solve treats with its
+                          // low-register small-front variant
+  int split_target = 256; // PFR_SOLVE_SPLIT: solve launches with fewer (front, group) workgroups than this (one per
+                          // CU) split their update parts up to about this many workgroups (0: off)
+  int us2_nar = 256;      // PFR_US2_NAR: solve launches (paired top-down, bottom-up chain) with fewer (front, group)
+                          // workgroups than this take the narrow-level forms -- pivot blocks in LDS, left-looking,
+                          // the update parts with their columns split over the waves (k_usolve2_updc + k_usolve2_rl,
+                          // k_lsolve_level_z<., true> + k_lsolve_rows_zc); 0: never.  Measured best at 256 for both
+                          // passes (1,024 / 4,096: no gain at 512 frequencies, slower at 4,096)
+  int fac_lds = -1;       // PFR_FAC_LDS: which levels factor A11 in LDS (k_factor_sym_lds): n > 0 those whose largest
+                          // pivot block has at least n pivots, 0 none, -1 auto: the levels on which the global-memory
+                          // kernel would get fewer than fac_lds_wg workgroups (the top of the tree in small chunks:
+                          // 512 frequencies levels 10-16, 2,048 level 16 -- faster per level there, slower elsewhere;
+                          // 512-frequency sweeps 31.8k -> 32.6k freq-solves/s, 4,096 unchanged)
+  int fac_lds_wg = 160;   // auto mode threshold (workgroups of k_factor_sym)
+  int us2_tiny = 8;       // PFR_US2_TINY (0 / 4 / 8): levels whose pivot blocks are <= this, one wave per front (8: the
+                          // bottom two levels at 2,048 frequencies 685 / 612 -> 509 / 489 us)
+  int us2_rl = 1;         // PFR_US2_RL: k_usolve2_rl for the narrow levels' paired pivot blocks
+  int ls_rl = 1;          // PFR_LS_RL: k_lsolve_rl_z for the bottom-up chain's narrow pivot blocks; on by default on
+                          // chunks of up to 1,024 frequencies (512-frequency sweeps forward solves 1.65 -> 1.33 ms per
+                          // step; on 2,048-frequency chunks 0.37 -> 0.50 ms per sweep: four slices x 128 groups of 16
+                          // frequencies each stage the frontal index chains, profiles/EXPERIMENTS.md, round 6)
+  int off_pu_waves = 0;   // PFR_OFF_PU_WAVES: L21 launches with fewer waves run the pipelined prefix; 8,000 by default
+                          // on chunks of up to 1,024 frequencies (the narrow levels of C4's per-rank sweeps: 512
+                          // frequencies 35.3-35.7k -> 36.2-36.6k freq-solves/s; 2,048-frequency chunks unchanged)
+  int front0 = 1;         // PFR_FRONT0=0: level 0 through the four class kernels instead of the fused k_front0
+                          // (tests/test_gpu_bitwise.py checks the two give the same factors bit for bit)
+  int blk_min = 24;       // PFR_SCHUR_BLK_MIN: update blocks of at least this many rows through the block kernel
+};
+// The knobs of a solver with chunk Fc from the environment, clamped
+Knobs knobs_from_env(int64_t Fc);
+
+// One record per pass and level: everything a launch of that level needs beyond pointers.  Plain int32 columns, in
+// this order the rows of pfr_symbolic_schedule / pfr_solver_schedule (include/pfr.h).  nf = 0: the level launches
+// nothing in that pass.
+struct FactorLevel {
+  int32_t nf, maxns;
+  int32_t fused0;          // operator-form sweeps run the level through k_front0 (level 0 only)
+  int32_t f0_small;        // ... whose first f0_small listed fronts have <= 2 pivots
+  int32_t lds;             // A11 by k_factor_sym_lds (else k_factor_sym<G> / k_factor_level)
+  int32_t G, waves;        // lane groups per wave and panel waves of the global-memory A11 kernel
+  int32_t off_small;       // L21: the SMALL form (pivot blocks <= 8)
+  int32_t off_pu;          // L21: 3 = the pipelined prefix (operator-form sweeps), 2 = plain
+  int32_t nasm, nitems, nblocks, ntiles;   // assembly records, L21 items, Schur blocks and tiles
+};
+enum PairForm { PAIR_TINY4, PAIR_TINY8, PAIR_RL, PAIR_SMALL, PAIR_BIG };   // the pivot-block kernel
+enum UpdForm { UPD_NONE, UPD_ROWS, UPD_COLS };   // update part: in the level kernel, k_usolve2_upd, k_usolve2_updc
+struct PairLevel {         // paired top-down pass (sym_top_down_pair), over all fronts of the level
+  int32_t nf, form, upd;
+  int32_t split;           // workgroups per (front, group) of UPD_ROWS; > 1 whenever the update part runs apart
+  int32_t waves;           // of the pivot-block kernel's workgroup
+  int32_t rpl;             // PAIR_RL: rows per lane slot (else 0)
+  int32_t RB;              // UPD_COLS: row blocks per front (else 0)
+  int32_t tiny, small;     // the level's classes under PFR_US2_TINY (0 / 4 / 8) and PFR_US2_SMALL, whichever form runs
+};
+enum ChainForm { CHAIN_PLAIN, CHAIN_NAR, CHAIN_RL };    // k_lsolve_level_z<., false | true>, k_lsolve_rl_z
+enum RowsForm { ROWS_NONE, ROWS_Z, ROWS_ZC };           // update rows: in the level kernel, k_lsolve_rows_z, ..._zc
+struct ChainLevel {        // bottom-up chain (fn_bottom_up): slice 0 over reach 0, slices 1-3 over reach 1
+  int32_t nf0, nf1, nmax, nsum;
+  int32_t form, rows, split, waves;
+  int32_t rpl;             // CHAIN_RL (else 0)
+  int32_t RB;              // ROWS_ZC (else 0)
+  int32_t lds_bytes;       // CHAIN_NAR: dynamic LDS (else 0)
+};
+struct SolveLevel {        // unpaired passes (solve_all, sym_top_down_support) over one subset of the level's fronts
+  int32_t nf;
+  int32_t level_w, waves;  // the level's size-based wave count; the launch's
+  int32_t split_L, split_U;
+};
+enum Subset { SUBSET_ALL, SUBSET_REACH0, SUBSET_REACH1 };
+struct Schedule {
+  // what the reach-dependent records are rebuilt from
+  int64_t Fc = 0;
+  Knobs knobs;
+  bool sym = false;
+  std::vector<int32_t> level_nf, level_maxns, level_maxf;
+  std::vector<FactorLevel> factor;
+  std::vector<PairLevel> pair;
+  std::vector<ChainLevel> chain;
+  std::vector<SolveLevel> solve[3];      // by Subset
+};
+template <class R> constexpr int schedule_cols() { return (int)(sizeof(R) / sizeof(int32_t)); }
+// Pure: the schedule of a solver with chunk Fc under the knobs k, for the reaches given by their per-level ranges
+// (reach_lists' ptr; an empty vector: no front reached)
+Schedule level_schedule(const Symbolic& S, const Plan& P, int64_t Fc, const Knobs& k,
+                        const std::vector<int32_t> (&reach_ptr)[2]);
+// The records that depend on the reaches (chain, solve[SUBSET_REACH*]) again, after a reach changed
+void schedule_reach(Schedule& sc, const std::vector<int32_t> (&reach_ptr)[2]);
+// Every record against the kernels' limits (LDS sizes, rows per lane slot, wave counts, the row blocks and the
+// split parts covering every row once).  Returns "" or the first violation.
+std::string check_schedule(const Symbolic& S, const Plan& P, const Schedule& sc);
 
 }  // namespace pfr

@@ -58,16 +58,8 @@ LD = np.longdouble
 CLD = np.clongdouble
 TREE_SPEC = ((65, -1), (20, 0), (33, 0), (3, 1), (4, 1), (9, 1), (16, 2), (17, 2), (31, 2), (5, 0))
 
-# launcher constants mirrored from csrc/kernels.hip / csrc/api.cpp / csrc/launch.hpp (dispatch_classes)
-RL_WMAX = 8
-FAC_G_NS = 64
-US2_SMALL = 110
-BLK_MIN = 24
-MAX_NS = 256
-LS_NAR_DYN_MAX = 112 * 1024    # csrc/plan.hpp: ls_nar_fits(maxns) = maxns * 64 * 16 <= LS_NAR_DYN_MAX (112 / 113)
-FAC_G, FAC_LDS_WG = 2, 160     # csrc/plan.hpp FAC_G; csrc/api.cpp fac_lds_wg (level_lds, auto mode)
-F0_NS, F0_RM = 4, 10           # csrc/plan.hpp: the fused bottom level (k_front0)
-US2_NAR = 256                  # csrc/api.cpp us2_nar: solve launches of fewer workgroups take the narrow forms
+BLK_MIN = 24           # PFR_SCHUR_BLK_MIN's default: update blocks of at least this many rows through the block kernel
+                       # (dispatch_classes lists them as ``blk``, checked against the schedule's block counts)
 
 
 # ----------------------------------------------------------------------------- patterns
@@ -158,52 +150,43 @@ def clique_tree(spec=TREE_SPEC, frac=0.5, n_dir=0, seed=0):
 
 
 # ----------------------------------------------------------------------------- dispatch classes
-def waves_for(maxf):
-    """csrc/plan.hpp waves_for: the size-based wave count of a level."""
-    return max(1, min(8, (maxf + 23) // 24))
-
-
-def solve_waves(level_w, nf, Fc, wmax):
-    """csrc/plan.hpp solve_waves: the waves per workgroup a solve launch over nf fronts really gets -- the level's
-    size-based count raised up to PFR_SOLVE_WMAX while the launch has fewer than 4,096 workgroups."""
-    wgs = max(1, nf * (Fc // 64))
-    return max(level_w, min(wmax, -(-4096 // wgs)))
-
-
-def dispatch_classes(sym, Fc=64, solve_wmax=8):
-    """Per-level launch classes of an analysis, from its exported fronts, as the launchers of csrc/kernels.hip and
-    csrc/api.cpp select them for chunks of ``Fc`` frequencies under PFR_SOLVE_WMAX = ``solve_wmax`` (the other
-    knobs at their defaults; constants mirrored above).  Returns a list of dicts, level 0 first."""
+def dispatch_classes(sym, Fc=64):
+    """Per-level launch classes of an analysis for chunks of ``Fc`` frequencies, level 0 first: the front geometry
+    from its exported fronts, every launch decision from the library's own schedule (``Symbolic.schedule``: the
+    records the level loops of csrc/api.cpp launch, every front reached) under the PFR_* knobs of the environment."""
+    from plate_inverse_problem_amd._native import CHAIN_FORMS, PAIR_FORMS, PAIR_UPD
     fr = sym.export("FRONTS")
     lp, lf = sym.export("LEVEL_PTR"), sym.export("LEVEL_FRONTS")
-    symmetric = bool(sym.stats()["symmetric"])
+    sc = sym.schedule(Fc)
     out = []
     for lv in range(lp.size - 1):
         t = lf[lp[lv]:lp[lv + 1]]
         ns, f = fr[t, 0], fr[t, 1]
         assert np.all(fr[t, 5] == lv)
-        maxns, maxf, nf = int(ns.max()), int(f.max()), int(t.size)
-        level_w = waves_for(maxf)
+        fac, pair, chain, sol = (sc[k][lv] for k in ("factor", "pair", "chain", "solve_all"))
+        assert fac["nf"] == pair["nf"] == sol["nf"] == t.size and fac["maxns"] == ns.max()
+        blk = [int(v) for v in f - ns if v >= BLK_MIN] if sym.stats()["symmetric"] else []
+        assert bool(blk) == (fac["nblocks"] > 0)
         out.append(dict(
             level=lv, ns=[int(v) for v in ns], f=[int(v) for v in f], upd=[int(v) for v in f - ns],
-            maxns=maxns, maxf=maxf, nf=nf,
-            rl=maxns <= 16 * RL_WMAX,                                   # right-looking solves allowed
-            rpl=1 if maxns <= 4 * RL_WMAX else 2 if maxns <= 8 * RL_WMAX else 4,   # rl_rpl
-            narrow=nf * (Fc // 64) < US2_NAR,                           # sym_top_down_pair: the narrow forms
-            ls_nar_fits=maxns * 64 * 16 <= LS_NAR_DYN_MAX,
-            tiny=4 if maxns <= 4 else 8 if maxns <= 8 else 0,           # k_usolve2_tiny / SMALL k_offdiag_level
-            # level_lds, auto mode: k_factor_sym_lds
-            fac_lds_auto=symmetric and 16 <= maxns <= 64 and nf * (Fc // 64) * FAC_G < FAC_LDS_WG,
-            fac_big=maxns > FAC_G_NS,                                   # k_factor_sym<4|8>
-            us2_small=maxf <= US2_SMALL,
-            level_w=level_w,                                            # waves_for(maxf)
-            # the waves of the level's solve launches over all its fronts (solve_W; the right-looking forms size
-            # their workgroups by rl_waves(maxns) instead)
-            solve_w=solve_waves(level_w, nf, Fc, solve_wmax),
-            # the general-mode panel factor: min(level_w, fill)
-            panel_w=max(1, min(level_w, -(-4096 // (nf * (Fc // 64) * FAC_G)))),
-            fused0=symmetric and lv == 0 and bool(np.all(ns <= F0_NS) and np.all(f - ns <= F0_RM)),   # k_front0
-            blk=[int(v) for v in f - ns if v >= BLK_MIN]))              # 16 x 16 LDS Schur blocks
+            maxns=int(ns.max()), maxf=int(f.max()), nf=int(t.size),
+            # the paired top-down pass: its form names, and what the tests pin of them
+            pair=PAIR_FORMS[pair["form"]], pair_upd=PAIR_UPD[pair["upd"]], chain=CHAIN_FORMS[chain["form"]],
+            rl=PAIR_FORMS[pair["form"]] == "rl",                        # k_usolve2_rl
+            rpl=int(pair["rpl"]),                                       # ... its rows per lane slot
+            narrow=PAIR_UPD[pair["upd"]] == "updc",                     # the narrow forms (k_usolve2_updc)
+            ls_nar_fits=CHAIN_FORMS[chain["form"]] != "plain",          # the chain's narrow forms (NAR / RL)
+            tiny=int(pair["tiny"]),                                     # the level's PFR_US2_TINY class (4 / 8 / 0)
+            us2_small=bool(pair["small"]),                              # ... and PFR_US2_SMALL class
+            fac_lds_auto=bool(fac["lds"]),                              # k_factor_sym_lds
+            fac_big=int(fac["G"]) > 2,                                  # k_factor_sym<4|8>
+            level_w=int(sol["level_w"]),                                # the level's size-based wave count
+            # the waves of the level's solve launches over all its fronts (the right-looking forms size their
+            # workgroups by the record's own wave count instead)
+            solve_w=int(sol["waves"]),
+            panel_w=int(fac["waves"]),                                  # the A11 panel factor
+            fused0=bool(fac["fused0"]),                                 # k_front0
+            blk=blk))                                                   # 16 x 16 LDS Schur blocks
     return out
 
 
@@ -892,35 +875,17 @@ def general_case(shape) -> GeneralCase:
 
 
 # ----------------------------------------------------------------------------- the unpaired solve passes
-SPLIT_TARGET = 256             # csrc/api.cpp split_target (PFR_SOLVE_SPLIT)
-
-
-def solve_split(nf, Fc, target):
-    """csrc/plan.hpp solve_split: the workgroups per (front, group) a solve launch's update part is split over."""
-    wgs = nf * (Fc // 64)
-    if target <= 0 or wgs <= 0 or wgs >= target:
-        return 1
-    return min(16, -(-target // wgs))
-
-
-def unpaired_classes(sym, Fc=64, solve_wmax=8, split_target=SPLIT_TARGET):
+def unpaired_classes(sym, Fc=64):
     """Per-level launch classes of the UNPAIRED passes (csrc/api.cpp forward_solve / adjoint_solve -> solve_all ->
-    csrc/kernels.hip launch_solve with subset = -1 or the reach lists, rhs_mode 0 / 2 / 3), level 0 first.  They
+    csrc/kernels.hip launch_solve with subset = -1 or the reach lists, rhs_mode 0 / 2 / 3), level 0 first, from the
+    schedule's records over all fronts (``Symbolic.schedule``, under the PFR_* knobs of the environment).  They
     differ from the paired passes' (dispatch_classes): launch_solve knows no narrow, right-looking or tiny form and
     does not look at us2_small -- PFR_US2_NAR, PFR_US2_RL, PFR_LS_RL and PFR_US2_TINY do not reach it.  What it
     selects on is
-      which = 0 (L):              k_lsolve_level<rhs_mode>, and with split > 1 the update rows by k_lsolve_rows
-      which = 1 (U), symmetric:   with split > 1 k_usolve_upd<true> first, then k_usolve_level<true>
+      which = 0 (L):              k_lsolve_level<rhs_mode>, and with split_L > 1 the update rows by k_lsolve_rows
+      which = 1 (U), symmetric:   with split_U > 1 k_usolve_upd<true> first, then k_usolve_level<true>
       which = 1 / 2 / 3, general: k_usolve_level<false> / k_utsolve_level<2> / k_ltsolve_level, never split
-    with split = solve_split(nf, Fc, PFR_SOLVE_SPLIT) and solve_waves(level_w, nf, Fc, PFR_SOLVE_WMAX) waves."""
-    fr = sym.export("FRONTS")
-    lp, lf = sym.export("LEVEL_PTR"), sym.export("LEVEL_FRONTS")
-    symmetric = bool(sym.stats()["symmetric"])
-    out = []
-    for lv in range(lp.size - 1):
-        t = lf[lp[lv]:lp[lv + 1]]
-        nf, level_w = int(t.size), waves_for(int(fr[t, 1].max()))
-        split = solve_split(nf, Fc, split_target)
-        out.append(dict(level=lv, nf=nf, split_L=split, split_U=split if symmetric else 1, level_w=level_w,
-                        solve_w=solve_waves(level_w, nf, Fc, solve_wmax)))
-    return out
+    and the record's waves."""
+    return [dict(level=lv, nf=int(r["nf"]), split_L=int(r["split_L"]), split_U=int(r["split_U"]),
+                 level_w=int(r["level_w"]), solve_w=int(r["waves"]))
+            for lv, r in enumerate(sym.schedule(Fc)["solve_all"])]

@@ -213,6 +213,30 @@ def test_solve_waves(shape, env, monkeypatch):
     _sweep_case(shape + "-" + ",".join(f"{k[4:]}={v}" for k, v in env.items()), shape, monkeypatch, env=env)
 
 
+@pytest.mark.parametrize("shape", ["A", "C", "F", "T", "F0"])
+def test_solver_schedule(shape):
+    """The live schedule of a solver with its right-hand side and functional set (nothing is launched) against the
+    analysis' schedule with every front reached: the reach-independent passes equal, the reach-dependent records
+    over at most the level's fronts and never empty at the root; on T the right-hand side (two leaf cliques and one
+    Dirichlet node) reaches only part of the bottom of its 5-level tree."""
+    _, op = sy.case(shape)
+    sym = sy.symbolic(shape)
+    sv, _ = make_solver(op, sym)
+    live, full = sv.schedule(), sym.schedule(64)
+    for name in ("factor", "pair", "solve_all"):
+        assert np.array_equal(live[name], full[name]), name
+    nf = full["solve_all"]["nf"]
+    assert nf.size == sym.stats()["n_levels"] and np.all(nf > 0)
+    for counts in (live["chain"]["nf0"], live["chain"]["nf1"], live["solve_reach0"]["nf"], live["solve_reach1"]["nf"]):
+        assert np.all(counts >= 0) and np.all(counts <= nf) and counts[-1] > 0
+    chain = live["chain"]
+    assert np.array_equal(chain["nf0"], live["solve_reach0"]["nf"])
+    assert np.array_equal(chain["nf1"], live["solve_reach1"]["nf"])
+    assert np.array_equal(chain["nmax"], np.maximum(chain["nf0"], chain["nf1"]))
+    if shape == "T":
+        assert nf.size == 5 and np.any(chain["nf0"] < nf)
+
+
 # ----------------------------------------------------------------------------- once, not per shape
 @pytest.mark.parametrize("nfreq", [1, 63, 64, 65])
 def test_batch_edges(nfreq, monkeypatch):

@@ -1,9 +1,10 @@
 """CPU: the synthetic shapes of tests/synthetic.py land in the launch classes tests/test_gpu_synthetic.py runs
 them for, and the fp64 multifrontal model (tests/mf_model.py) solves them to rounding level.
 
-The dispatch assertions read the exported fronts (FRONTS, LEVEL_PTR, LEVEL_FRONTS) and restate the launchers'
-thresholds (csrc/kernels.hip launch_usolve2 / launch_lsolve_multi, csrc/api.cpp sym_top_down_pair / factor_level,
-csrc/plan.hpp): if the analysis changes, the GPU tests cannot silently stop covering a branch.
+The dispatch assertions read the front geometry from the exported fronts (FRONTS, LEVEL_PTR, LEVEL_FRONTS) and every
+launch decision from the library's own schedule (``Symbolic.schedule``: the records csrc/plan.cpp level_schedule
+computes and the level loops of csrc/api.cpp launch), under the knobs of the environment: if the analysis, a threshold
+or a launcher's cut-off changes, the GPU tests cannot silently stop covering a branch.
 
 Which test reaches which dispatch point (ids of tests/test_gpu_synthetic.py; "narrow" = the launch has fewer than
 us2_nar = 256 workgroups, which every level of every shape at 64-frequency chunks has):
@@ -58,8 +59,11 @@ def _fronts(shape):
 
 BORDER_SHAPES = {"A": ((3, 4, 5, 8, 9, 16, 17), 33), "B": ((4, 8, 31, 32, 33), 65), "C": ((2, 7, 40), 129),
                  "D": ((5, 70), 161), "A4": ((2, 3, 4, 4), 33), "A8": ((5, 7, 8), 33), "F": ((6, 112), 113)}
-def _solve_w(shape, **kw):
-    return [d["solve_w"] for d in sy.dispatch_classes(sy.symbolic(shape), **kw)]
+
+
+
+def _solve_w(shape):
+    return [d["solve_w"] for d in sy.dispatch_classes(sy.symbolic(shape))]
 
 
 @pytest.mark.parametrize("shape", sorted(BORDER_SHAPES))
@@ -147,18 +151,19 @@ def test_dispatch_classes():
     assert not any(d[0]["fused0"] for d in (A, A4, A8, B, C, D, E, F, T))
 
 
-def test_solve_launch_waves():
+def test_solve_launch_waves(monkeypatch):
     """The waves a solve launch really gets (csrc/plan.hpp solve_waves): 8 on every level of every shape under the
     default knobs, since no launch here has 4,096 workgroups; the levels' size-based counts 1 .. 8 only under
     PFR_SOLVE_WMAX=1 (test_gpu_synthetic.py::test_solve_waves).  Every level is narrow at 64-frequency chunks; the
     2,048-lane chunk makes shape A's level 0 wide."""
+    want = {"F0": [1, 1], "A": [3, 2], "T": [4, 4, 4, 4, 3], "B": [5, 3], "C": [8, 6], "D": [8, 7]}
     for shape in sy.SHAPES:
         dc = sy.dispatch_classes(sy.symbolic(shape))
         assert all(d["solve_w"] == 8 and d["narrow"] for d in dc), shape
-        assert _solve_w(shape, solve_wmax=1) == [d["level_w"] for d in dc]
-    want = {"F0": [1, 1], "A": [3, 2], "T": [4, 4, 4, 4, 3], "B": [5, 3], "C": [8, 6], "D": [8, 7]}
-    for shape, w in want.items():
-        assert _solve_w(shape, solve_wmax=1) == w, shape
+        with monkeypatch.context() as m:
+            m.setenv("PFR_SOLVE_WMAX", "1")
+            assert _solve_w(shape) == [d["level_w"] for d in dc]
+            assert shape not in want or _solve_w(shape) == want[shape], shape
     assert set(sum(want.values(), [])) == {1, 2, 3, 4, 5, 6, 7, 8}
     wide = sy.dispatch_classes(sy.symbolic("A"), Fc=2048)
     assert [d["narrow"] for d in wide] == [False, True] and [d["solve_w"] for d in wide] == [8, 8]
@@ -166,6 +171,41 @@ def test_solve_launch_waves():
     panel = {s: [d["panel_w"] for d in sy.dispatch_classes(sy.symbolic(s, symmetric=False, general=True))]
              for s in sy.GENERAL_SHAPES}
     assert panel == {"A": [3, 2], "C": [8, 6], "E": [8, 8, 2], "T": [4, 4, 4, 4, 3]}
+
+
+def _forms(monkeypatch, shape, env, *keys):
+    """[tuple of the keys of sy.dispatch_classes per level] of a shape under the environment ``env``."""
+    with monkeypatch.context() as m:
+        for k, v in env.items():
+            m.setenv(k, v)
+        return [tuple(d[k] for k in keys) for d in sy.dispatch_classes(sy.symbolic(shape))]
+
+
+def test_knob_forms(monkeypatch):
+    """The knob lines of the module docstring: the form the schedule reports on the named level under the named
+    environment (tests/test_gpu_synthetic.py::test_knob runs these cases)."""
+    # [F-LS_RL=0]: the chain's pivot blocks in LDS where they fit (112), the plain form where they do not (113)
+    assert _forms(monkeypatch, "F", {}, "chain") == [("rl",), ("plain",)]
+    assert _forms(monkeypatch, "F", {"PFR_LS_RL": "0"}, "chain") == [("nar",), ("plain",)]
+    # [B-US2_RL=0]: the column-split update part, then the small-front level kernel; on C the large-front one
+    assert _forms(monkeypatch, "B", {}, "pair", "pair_upd") == [("rl", "updc")] * 2
+    assert _forms(monkeypatch, "B", {"PFR_US2_RL": "0"}, "pair", "pair_upd") == [("level_small", "updc")] * 2
+    assert _forms(monkeypatch, "C", {"PFR_US2_RL": "0"}, "pair", "pair_upd") == [("level_big", "updc")] * 2
+    # [A4|A8-US2_NAR=0,SOLVE_SPLIT=0]: wide unsplit launches take the tiny forms on the levels of small pivot blocks
+    wide = {"PFR_US2_NAR": "0", "PFR_SOLVE_SPLIT": "0"}
+    assert _forms(monkeypatch, "A4", wide, "pair", "pair_upd") == [("tiny4", "none"), ("level_small", "none")]
+    assert _forms(monkeypatch, "A8", wide, "pair", "pair_upd") == [("tiny8", "none"), ("level_small", "none")]
+    for shape in ("A4", "A8"):       # ... and the small-front level kernel with PFR_US2_TINY=0, or while narrow
+        assert _forms(monkeypatch, shape, dict(wide, PFR_US2_TINY="0"), "pair", "tiny") == [("level_small", 0)] * 2
+        assert _forms(monkeypatch, shape, {}, "pair", "pair_upd") == [("rl", "updc")] * 2
+    # [A|B-FAC_LDS=0|1]: A11 in LDS on no level / on every level of pivot blocks up to 64 (B's root has 65)
+    for shape, on in (("A", [True, True]), ("B", [True, False])):
+        assert _forms(monkeypatch, shape, {"PFR_FAC_LDS": "0"}, "fac_lds_auto") == [(False,), (False,)]
+        assert _forms(monkeypatch, shape, {"PFR_FAC_LDS": "1"}, "fac_lds_auto") == [(v,) for v in on]
+    assert _forms(monkeypatch, "A4", {"PFR_FAC_LDS": "1"}, "fac_lds_auto") == [(True,), (True,)]   # auto: 16 .. 64 only
+    # [F0-FRONT0=0]: the bottom level through the four class kernels
+    assert _forms(monkeypatch, "F0", {}, "fused0") == [(True,), (False,)]
+    assert _forms(monkeypatch, "F0", {"PFR_FRONT0": "0"}, "fused0") == [(False,), (False,)]
 
 
 @pytest.mark.parametrize("shape", sorted(sy.SHAPES))
@@ -317,7 +357,7 @@ def test_weak_variant_conditions(shape, symmetric):
 
 
 # ----------------------------------------------------------------------------- the unpaired passes' dispatch
-def test_unpaired_dispatch_classes():
+def test_unpaired_dispatch_classes(monkeypatch):
     """launch_solve as forward_solve / adjoint_solve call it selects differently from the paired passes (see
     sy.unpaired_classes): only the split of the update parts and the wave count.  Which shapes reach what, at
     64-frequency chunks (tests/test_gpu_synthetic_hessian.py::test_unpaired_knobs runs them):
@@ -332,14 +372,19 @@ def test_unpaired_dispatch_classes():
     assert [d["nf"] for d in A] == [9, 1] and [d["nf"] for d in B] == [7, 1]
     assert all(d["split_U"] == d["split_L"] for d in A + B + C + T)
     assert all(d["split_L"] == 16 for d in T[1:]) and T[0]["nf"] < 256
-    big = [sy.unpaired_classes(sy.symbolic(s), split_target=1000000) for s in "ABCT"]
+    def under(name, value, shape):
+        with monkeypatch.context() as m:
+            m.setenv(name, value)
+            return sy.unpaired_classes(sy.symbolic(shape))
+
+    big = [under("PFR_SOLVE_SPLIT", "1000000", s) for s in "ABCT"]
     assert all(d["split_L"] == 16 for dc in big for d in dc)
-    assert [d["split_L"] for d in sy.unpaired_classes(sy.symbolic("A"), split_target=64)] == [8, 16]
-    assert [d["split_L"] for d in sy.unpaired_classes(sy.symbolic("B"), split_target=64)] == [10, 16]
+    assert [d["split_L"] for d in under("PFR_SOLVE_SPLIT", "64", "A")] == [8, 16]
+    assert [d["split_L"] for d in under("PFR_SOLVE_SPLIT", "64", "B")] == [10, 16]
     for s in "ABCT":
-        off = sy.unpaired_classes(sy.symbolic(s), split_target=0)
+        off = under("PFR_SOLVE_SPLIT", "0", s)
         assert all(d["split_L"] == 1 and d["split_U"] == 1 for d in off)
-        assert [d["solve_w"] for d in sy.unpaired_classes(sy.symbolic(s), solve_wmax=1)] == \
+        assert [d["solve_w"] for d in under("PFR_SOLVE_WMAX", "1", s)] == \
             [d["level_w"] for d in sy.dispatch_classes(sy.symbolic(s))]
         assert all(d["solve_w"] == 8 for d in sy.unpaired_classes(sy.symbolic(s)))
     for s in sy.GENERAL_SHAPES:      # the general analysis of the shapes WITH Dirichlet nodes (the Hessian cases)
