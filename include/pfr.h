@@ -67,6 +67,11 @@ extern "C" {
 #define PFR_LOSS_MSE_AFC 2
 #define PFR_LOSS_MSE_LOG_AFC 3
 #define PFR_LOSS_COTANGENT 4  /* ref holds dL/dfr (real part), loss not computed */
+/* losses of the complex response H (pfr_sweep_complex only); g is the cotangent, d term = Re(g dH) */
+#define PFR_LOSS_CMSE 16        /* |H - ref|^2,            g = 2 conj(H - ref) */
+#define PFR_LOSS_CRMSE 17       /* |H - ref|^2 / |ref|^2,  g = 2 conj(H - ref) / |ref|^2 */
+#define PFR_LOSS_CLOG 18        /* |z|^2, z = log(H / ref) on the principal branch, g = 2 conj(z) / H */
+#define PFR_LOSS_CCOTANGENT 19  /* ref holds dL/dH (complex), loss not computed */
 
 typedef struct pfr_symbolic pfr_symbolic;
 typedef struct pfr_solver pfr_solver;
@@ -258,6 +263,30 @@ PFR_API int64_t pfr_sweep_graph_launches(const pfr_solver* s);
  * solves one adjoint system per frequency and refactorises for each (InnerState.h:289-305). */
 PFR_API int pfr_jacobian_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, double* fr_dev /* may be NULL */,
                                double* jc_dev, int32_t* flags_dev /* may be NULL */, void* stream);
+/* The complex response: with a real sensing axis d = (dU, dV, dW) (host, 3 doubles; read during the call),
+ *   H_q = dU ts U_q + dV ts V_q + dW W_q            (complex; U, V, W and ts of pfr_set_functional)
+ * -- d = (0, 0, 1) is the out-of-plane transfer function, (cos phi, sin phi, 1) a z-axis accelerometer with its
+ * transverse sensitivity along phi.  H is the number the solver's x gives, with NO conjugation: a reference recorded
+ * in the other time convention (e^{-i omega t} against e^{+i omega t}) must be conjugated by the caller.
+ * pfr_sweep_complex: h_dev[q] = H_q (complex nfreq, may be NULL) and, with a loss (PFR_LOSS_CMSE .. PFR_LOSS_CCOTANGENT,
+ * ref_dev complex nfreq), loss_dev[0] and w_dev accumulated as pfr_sweep does (fresh != 0: initialised by the sweep as
+ * pfr_sweep_fresh does), with A^T lam_q = scale g_q a_d and g the loss's complex cotangent, d term = Re(g dH).
+ * pfr_jacobian_sweep_complex: jc_dev[q * n_stiff + k] = -m_q mu_q^T S_k x_q + e_k t_q with A^T mu = a_d, so that
+ *   dH_q = sum_k jc[q][k] dc_k     (complex, no real part taken),
+ * and for any complex g, sum_q g_q jc[q][k] = w_k of a PFR_LOSS_CCOTANGENT sweep with ref = g and scale 1.
+ * H is linear in x, so mu does not depend on x and the functional correction H + mu^T r (PFR_CHECK_CORRECT) is exact
+ * in the forward solve's error.  Every pfr_set_check mode applies except PFR_CHECK_REFINE_ADJ (PFR_ERR_ARG).
+ * PFR_ERR_ARG before any launch: a loss id outside {PFR_LOSS_NONE, 16 .. 19} (the magnitude's ids 0 .. 4 included), a
+ * zero or non-finite axis, a loss without ref_dev.  Never part of the PFR_GRAPH graph; the next magnitude sweep is
+ * bit-identical to one run without them.  Out of scope: the Hessian of the complex losses, complex responses in the
+ * population sweep, several channels in one sweep.  The reference computes the phases and drops them
+ * (Problem.py _solve: uang, vang, wang). */
+PFR_API int pfr_sweep_complex(pfr_solver* s, int32_t nfreq, const double* freqs_dev, const double* axis /* host, 3 */,
+                              int32_t loss_type /* PFR_LOSS_NONE or 16..19 */, const double* ref_dev /* complex nfreq */,
+                              double scale, double* h_dev /* complex nfreq, may be NULL */, double* loss_dev,
+                              double* w_dev, int32_t* flags_dev, int32_t fresh /* as pfr_sweep_fresh */, void* stream);
+PFR_API int pfr_jacobian_sweep_complex(pfr_solver* s, int32_t nfreq, const double* freqs_dev, const double* axis,
+                                       double* h_dev /* may be NULL */, double* jc_dev, int32_t* flags_dev, void* stream);
 /* A population of parameter sets in one sweep: a lane is a (member, frequency) pair.
  * pfr_combine_batch: Kpop_dev[m * nnz + nz] = sum_k coef[m * n_stiff + k] S_k(nz) for m < n_members (member-major;
  * each row bitwise what pfr_combine gives for that member's coefficients), the stiffness read once.

@@ -429,12 +429,13 @@ class _Engine:
                 if a is not None and b is not a:
                     a.add_(b)
 
-    def loss_step(self, freqs, loss_type, ref, scale):
+    def loss_step(self, freqs, loss_type, ref, scale, axis=None):
         """One loss + gradient sweep with the step buffers reused across calls (the optimiser / bench loop:
         the host's step-to-step turnaround is GPU idle time).  Per lane, loss and the contracted partials
         accumulate into one slot of a single device buffer whose last entry receives the number of flagged
         frequencies; one fill per buffer, one device->host copy.  Returns (loss sum, w (18,) complex, flags
-        device tensor, flagged count); the backward errors land in ``last_berr``."""
+        device tensor, flagged count); the backward errors land in ``last_berr``.  ``axis`` (3 real numbers; None:
+        the magnitude fr): the loss of the complex response along it (``Solver.sweep_complex``, a LOSS_C* id)."""
         n = freqs.numel()
         key = (n, self.n_lanes, id(self.solvers[0]))
         b = self._step_bufs.get(key) if hasattr(self, "_step_bufs") else None
@@ -466,8 +467,12 @@ class _Engine:
             vb, vf, vr, vfl = views[lo]
             sv.set_check(self.check_mode, self.check_tol, vb)
             try:
-                sv.sweep(vf, loss_type, ref=vr, scale=scale, loss=bufs[0], w=bufs[1], flags=vfl, fresh=True,
-                         stream=stream)
+                if axis is None:
+                    sv.sweep(vf, loss_type, ref=vr, scale=scale, loss=bufs[0], w=bufs[1], flags=vfl, fresh=True,
+                             stream=stream)
+                else:
+                    sv.sweep_complex(vf, axis, loss_type, ref=vr, scale=scale, loss=bufs[0], w=bufs[1], flags=vfl,
+                                     fresh=True, stream=stream)
             finally:
                 sv.set_check(self.check_mode, self.check_tol)
         if self.check_mode & _native.PFR_CHECK_REFINE_ADJ:
@@ -502,9 +507,10 @@ class _Engine:
         return float(tot[0]), w, flags, int(np.count_nonzero(self.last_flags_host))
 
     def sweep(self, freqs, loss_type=_native.LOSS_NONE, ref=None, scale=1.0, fr=None, loss=None, w=None,
-              flags=None, berr=None):
+              flags=None, berr=None, axis=None):
         """``Solver.sweep`` over all lanes (fr / flags / berr (F, 2) written in place, loss / w
-        accumulated)."""
+        accumulated).  ``axis`` (3 real numbers): ``Solver.sweep_complex`` instead, ``fr`` a complex128 tensor that
+        receives the response H along the axis and ``loss_type`` one of the LOSS_C* ids."""
         if self.check_mode & _native.PFR_CHECK_REFINE_ADJ:
             self._seeded = True        # the lanes allocate their refinement seed vectors in this sweep
 
@@ -512,9 +518,14 @@ class _Engine:
             if berr is not None:
                 sv.set_check(self.check_mode, self.check_tol, berr[lo:hi])
             try:
-                sv.sweep(freqs[lo:hi], loss_type, ref=None if ref is None else ref[lo:hi], scale=scale,
-                         fr=None if fr is None else fr[lo:hi], loss=bufs[0], w=bufs[1],
-                         flags=None if flags is None else flags[lo:hi])
+                if axis is None:
+                    sv.sweep(freqs[lo:hi], loss_type, ref=None if ref is None else ref[lo:hi], scale=scale,
+                             fr=None if fr is None else fr[lo:hi], loss=bufs[0], w=bufs[1],
+                             flags=None if flags is None else flags[lo:hi])
+                else:
+                    sv.sweep_complex(freqs[lo:hi], axis, loss_type, ref=None if ref is None else ref[lo:hi],
+                                     scale=scale, h=None if fr is None else torch.view_as_real(fr[lo:hi]),
+                                     loss=bufs[0], w=bufs[1], flags=None if flags is None else flags[lo:hi])
             finally:
                 if berr is not None:
                     sv.set_check(self.check_mode, self.check_tol)
@@ -526,9 +537,10 @@ class _Engine:
                              h=bufs[2], flags=None if flags is None else flags[lo:hi])
         self._run(call, freqs.numel(), [loss, w, h])
 
-    def jacobian_sweep(self, freqs, jc, fr=None, flags=None, berr=None):
+    def jacobian_sweep(self, freqs, jc, fr=None, flags=None, berr=None, axis=None):
         """``Solver.jacobian_sweep`` over all lanes: every lane writes its own rows of ``jc`` (F, n_stiff) complex
-        (and of fr / flags / berr (F, 2)); nothing is accumulated.  Sets ``last_berr`` and ``last_flags``."""
+        (and of fr / flags / berr (F, 2)); nothing is accumulated.  Sets ``last_berr`` and ``last_flags``.
+        ``axis`` (3 real numbers): ``Solver.jacobian_sweep_complex``, ``fr`` a complex128 tensor for H."""
         if self.check_mode & _native.PFR_CHECK_REFINE_ADJ:
             self._seeded = True        # as sweep: the lanes allocate their refinement seed vectors
 
@@ -536,8 +548,14 @@ class _Engine:
             if berr is not None:
                 sv.set_check(self.check_mode, self.check_tol, berr[lo:hi])
             try:
-                sv.jacobian_sweep(freqs[lo:hi], torch.view_as_real(jc[lo:hi]), fr=None if fr is None else fr[lo:hi],
-                                  flags=None if flags is None else flags[lo:hi])
+                if axis is None:
+                    sv.jacobian_sweep(freqs[lo:hi], torch.view_as_real(jc[lo:hi]),
+                                      fr=None if fr is None else fr[lo:hi],
+                                      flags=None if flags is None else flags[lo:hi])
+                else:
+                    sv.jacobian_sweep_complex(freqs[lo:hi], axis, torch.view_as_real(jc[lo:hi]),
+                                              h=None if fr is None else torch.view_as_real(fr[lo:hi]),
+                                              flags=None if flags is None else flags[lo:hi])
             finally:
                 if berr is not None:
                     sv.set_check(self.check_mode, self.check_tol)
@@ -648,16 +666,58 @@ class _SweepFR(torch.autograd.Function):
         return torch.conj(engine.expand(w)).to(torch.complex128).cpu(), None, None
 
 
-class _SweepLoss(torch.autograd.Function):
-    """Fused loss + gradient: one factorisation per frequency (forward + adjoint)."""
+def _sensing_axis(axis) -> np.ndarray:
+    """The real sensing axis (dU, dV, dW) of the complex response as 3 float64 (default: out of plane)."""
+    a = np.asarray((0.0, 0.0, 1.0) if axis is None else axis, dtype=np.float64).reshape(-1)
+    if a.size != 3 or not np.isfinite(a).all() or not a.any():
+        raise ValueError(f'the sensing axis needs 3 finite components, not all zero: {axis!r}')
+    return a
+
+
+class _SweepTF(torch.autograd.Function):
+    """H(c) = axis . (ts U, ts V, W) (complex) for a frequency vector; backward = one PFR_LOSS_CCOTANGENT sweep with
+    g = conj(grad_out), torch's convention dL = Re(conj(grad) dH)."""
 
     @staticmethod
-    def forward(ctx, c, engine, freqs, ref, loss_id, n_total, reduce_fn):
+    def forward(ctx, c, engine, freqs, axis):
+        cn = c.detach().cpu().numpy()
+        engine.set_coefficients(cn)
+        h = torch.empty(freqs.numel(), dtype=torch.complex128, device=engine.device)
+        flags = torch.zeros(freqs.numel(), dtype=torch.int32, device=engine.device)
+        berr = torch.full((freqs.numel(), 2), float('nan'), dtype=torch.float64, device=engine.device)
+        engine.sweep(freqs, _native.LOSS_NONE, fr=h, flags=flags, berr=berr, axis=axis)
+        engine.last_berr = berr
+        engine.last_flags = _check_flags(flags)
+        ctx.engine, ctx.freqs, ctx.cn, ctx.axis = engine, freqs, cn, axis
+        return h
+
+    @staticmethod
+    def backward(ctx, grad_h):
+        engine = ctx.engine
+        engine.set_coefficients(ctx.cn)
+        g = torch.conj(grad_h.to(torch.complex128)).resolve_conj().contiguous()
+        w = torch.zeros(engine.n_stiff, dtype=torch.complex128, device=engine.device)
+        loss = torch.zeros(1, dtype=torch.float64, device=engine.device)
+        flags = torch.zeros(ctx.freqs.numel(), dtype=torch.int32, device=engine.device)
+        berr = torch.full((ctx.freqs.numel(), 2), float('nan'), dtype=torch.float64, device=engine.device)
+        engine.sweep(ctx.freqs, _native.LOSS_CCOTANGENT, ref=torch.view_as_real(g), scale=1.0,
+                     loss=loss, w=torch.view_as_real(w), flags=flags, berr=berr, axis=ctx.axis)
+        engine.last_berr = berr
+        engine.last_flags = _check_flags(flags)
+        return torch.conj(engine.expand(w)).to(torch.complex128).cpu(), None, None, None
+
+
+class _SweepLoss(torch.autograd.Function):
+    """Fused loss + gradient: one factorisation per frequency (forward + adjoint).  ``axis`` (None: the magnitude's
+    losses): the complex response's losses along it."""
+
+    @staticmethod
+    def forward(ctx, c, engine, freqs, ref, loss_id, n_total, reduce_fn, axis=None):
         cn = c.detach().cpu().numpy()
         engine.set_coefficients(cn)
         if reduce_fn is None:
             # the single-process step: reused buffers, one device->host copy (_Engine.loss_step)
-            lsum, w, flags, nflag = engine.loss_step(freqs, loss_id, torch.view_as_real(ref), 1.0 / n_total)
+            lsum, w, flags, nflag = engine.loss_step(freqs, loss_id, torch.view_as_real(ref), 1.0 / n_total, axis)
             engine.last_flags = _check_flags(flags) if nflag else np.zeros(flags.numel(), np.int32)
             ctx.save_for_backward(torch.from_numpy(w))
             return torch.tensor(lsum / n_total, dtype=torch.float64)
@@ -666,7 +726,7 @@ class _SweepLoss(torch.autograd.Function):
         flags = torch.zeros(freqs.numel(), dtype=torch.int32, device=engine.device)
         berr = torch.full((freqs.numel(), 2), float('nan'), dtype=torch.float64, device=engine.device)
         engine.sweep(freqs, loss_id, ref=torch.view_as_real(ref), scale=1.0 / n_total,
-                     loss=loss, w=torch.view_as_real(w), flags=flags, berr=berr)
+                     loss=loss, w=torch.view_as_real(w), flags=flags, berr=berr, axis=axis)
         engine.last_berr = berr
         packed = torch.cat([loss.to(torch.complex128), engine.expand(w)])
         if reduce_fn is not None:
@@ -681,7 +741,7 @@ class _SweepLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (w,) = ctx.saved_tensors
-        return torch.conj(w) * g, None, None, None, None, None, None
+        return torch.conj(w) * g, None, None, None, None, None, None, None
 
 
 class _JetSweepLoss(torch.autograd.Function):
@@ -693,14 +753,14 @@ class _JetSweepLoss(torch.autograd.Function):
     step-to-step turnaround (the GPU idles from one step's result to the next step's first launch)."""
 
     @staticmethod
-    def forward(ctx, params, material, h, scaling, engine, freqs, ref, loss_id, n_total):
+    def forward(ctx, params, material, h, scaling, engine, freqs, ref, loss_id, n_total, axis=None):
         # scaling: 1.0 or a float64 numpy array (the host arithmetic in numpy: the same IEEE products as the
         # chain's torch ones, a few us less per step)
         ctx.cast = params.dtype != torch.float64 or params.device.type != "cpu"
         p = (params.detach().to(torch.float64).cpu() if ctx.cast else params.detach()).numpy() * scaling
         c, J = _cached_abd(material, h, p)
         engine.set_coefficients(c)
-        lsum, w, flags, nflag = engine.loss_step(freqs, loss_id, torch.view_as_real(ref), 1.0 / n_total)
+        lsum, w, flags, nflag = engine.loss_step(freqs, loss_id, torch.view_as_real(ref), 1.0 / n_total, axis)
         engine.last_flags = _check_flags(flags) if nflag else np.zeros(flags.numel(), np.int32)
         # dL/dparams for an incoming gradient of 1 (the chain's values for it, bit for bit: Re(w J) * scaling)
         ctx.gt = torch.from_numpy(np.real(w @ J) * scaling)
@@ -711,7 +771,7 @@ class _JetSweepLoss(torch.autograd.Function):
     def backward(ctx, g):
         grad = ctx.gt * g
         return (grad.to(dtype=ctx.dtype, device=ctx.device) if ctx.cast else grad), None, None, None, None, None, \
-            None, None, None
+            None, None, None, None
 
 
 def residual_terms(fr, reference_fr, func_type: str):
@@ -735,6 +795,28 @@ def residual_terms(fr, reference_fr, func_type: str):
     if func_type == 'MSE_LOG_AFC':
         return np.log(fr) - np.log(rabs), one / fr, 0.0
     raise ValueError(f'Function type "{func_type}" is not supported!')
+
+
+def complex_residual_terms(H, reference_fr, func_type: str):
+    """The complex response's losses as least squares (host, numpy): ``(r (2F,), dz/dH (F,), const)`` with
+    ``r = [Re z; Im z]``, ``loss = (r @ r + const) / F`` and z holomorphic in H, so that
+    ``Jr = [Re(dz/dH dH); Im(dz/dH dH)]`` for the complex rows dH of ``getTFJacobianFunction``.
+
+        MSE_COMPLEX      z = H - ref              const = 0
+        RMSE_COMPLEX     z = (H - ref) / |ref|    const = 0
+        MSE_LOG_COMPLEX  z = log(H / ref)         const = 0    (principal branch)"""
+    H = np.asarray(H, dtype=np.complex128)
+    ref = np.asarray(reference_fr, dtype=np.complex128)
+    if func_type == 'MSE_COMPLEX':
+        z, dz = H - ref, np.ones_like(H)
+    elif func_type == 'RMSE_COMPLEX':
+        rabs = np.abs(ref)
+        z, dz = (H - ref) / rabs, 1.0 / rabs + 0j * H
+    elif func_type == 'MSE_LOG_COMPLEX':
+        z, dz = np.log(H / ref), 1.0 / H
+    else:
+        raise ValueError(f'Function type "{func_type}" is not supported!')
+    return np.concatenate([z.real, z.imag]), dz, 0.0
 
 
 def covariance_from_residual(r, Jr, const=0.0, rcond=1e-12):
@@ -993,6 +1075,31 @@ class Problem:
 
     getAFCFunction = getFRFunction
 
+    def getTFFunction(self, axis=(0, 0, 1)) -> Callable:
+        """``tf(freqs, params) -> (F,) complex128 tensor`` on the device, differentiable in params: the complex
+        response ``H = dU ts U + dV ts V + dW W`` along the real sensing ``axis`` (dU, dV, dW) -- (0, 0, 1) the
+        out-of-plane transfer function, (cos phi, sin phi, 1) a z-axis accelerometer with its transverse sensitivity
+        along phi; ``|H|`` along e1, e2, e3 squared and summed is ``getFRFunction``'s fr squared.  H is the number the
+        solver's x gives, not conjugated: a reference recorded in the other time convention must be conjugated by the
+        caller.  The reference computes these phases and drops them (``Problem.py`` ``_solve``)."""
+        transform = self._transform()
+        ax = _sensing_axis(axis)
+
+        def tf_function(freqs, params):
+            f = self._freqs(freqs)
+            p = params if isinstance(params, torch.Tensor) else torch.as_tensor(np.asarray(params, dtype=np.float64))
+            c = self._coeffs(transform, p.to(torch.float64).cpu())
+            return _SweepTF.apply(c, self.engine(f.numel()), f, ax)
+
+        return tf_function
+
+    def solveForwardComplex(self, freqs, params=None, axis=(0, 0, 1)) -> np.ndarray:
+        """The complex response along ``axis`` at ``freqs`` [Hz] (numpy complex128; ``getTFFunction``)."""
+        if params is None:
+            params = self.parameters
+        with torch.no_grad():
+            return self.getTFFunction(axis)(freqs, params).cpu().numpy()
+
     def solveForward(self, freqs, params=None, *, distributed: bool = False) -> np.ndarray:
         """Frequency response at ``freqs`` [Hz] (``Problem.py:611-639``).
 
@@ -1043,8 +1150,12 @@ class Problem:
         return fr.cpu().numpy(), berr[:, 0].cpu().numpy(), flags.cpu().numpy()
 
     def getLossFunction(self, frequencies, reference_fr, func_type: str, scaling_params=None,
-                        *, distributed: bool = False) -> Callable:
+                        *, distributed: bool = False, axis=None) -> Callable:
         """``loss(params) -> 0-dim tensor`` (``Problem.py:933-980``).
+
+        ``func_type`` MSE_COMPLEX, RMSE_COMPLEX or MSE_LOG_COMPLEX: the mean over the frequencies of ``|H - ref|^2``,
+        ``|H - ref|^2 / |ref|^2`` or ``|log(H / ref)|^2`` of the complex response H along ``axis`` (``getTFFunction``;
+        default (0, 0, 1)) -- amplitude and phase of the measurement, where the four losses above use its amplitude.
 
         With ``distributed=True`` and an initialised ``torch.distributed`` group,
         every rank sweeps its contiguous block of the frequencies and one
@@ -1053,9 +1164,14 @@ class Problem:
         frequencies = np.asarray(frequencies)
         reference_fr = np.asarray(reference_fr)
         assert frequencies.shape[0] == reference_fr.shape[0]
-        if func_type not in _native.LOSS_IDS:
+        if func_type in _native.COMPLEX_LOSS_IDS:
+            loss_id, axis = _native.COMPLEX_LOSS_IDS[func_type], _sensing_axis(axis)
+        elif func_type not in _native.LOSS_IDS:
             raise ValueError(f'Function type "{func_type}" is not supported!')
-        loss_id = _native.LOSS_IDS[func_type]
+        elif axis is not None:
+            raise ValueError(f'"{func_type}" is a loss of the magnitude fr: it takes no sensing axis')
+        else:
+            loss_id = _native.LOSS_IDS[func_type]
         scaling = 1.0 if scaling_params is None else torch.as_tensor(np.array(scaling_params, dtype=np.float64))
         scaling_np = 1.0 if scaling_params is None else np.array(scaling_params, dtype=np.float64)
         n_total = frequencies.shape[0]
@@ -1073,9 +1189,10 @@ class Problem:
             if reduce_fn is None and self.material.atype in _JET_TYPES:
                 # one autograd node (host turnaround of the optimiser / bench loop)
                 return _JetSweepLoss.apply(p, self.material, self.geometry.height, scaling_np,
-                                           self.engine(max(1, hi - lo)), f_local, ref_local, loss_id, n_total)
+                                           self.engine(max(1, hi - lo)), f_local, ref_local, loss_id, n_total, axis)
             c = self._coeffs(transform, p.to(torch.float64).cpu() * scaling)
-            return _SweepLoss.apply(c, self.engine(max(1, hi - lo)), f_local, ref_local, loss_id, n_total, reduce_fn)
+            return _SweepLoss.apply(c, self.engine(max(1, hi - lo)), f_local, ref_local, loss_id, n_total, reduce_fn,
+                                    axis)
 
         return loss
 
@@ -1094,6 +1211,8 @@ class Problem:
         frequencies = np.asarray(frequencies)
         reference_fr = np.asarray(reference_fr)
         assert frequencies.shape[0] == reference_fr.shape[0]
+        if func_type in _native.COMPLEX_LOSS_IDS:
+            raise ValueError(f'the Hessian sweep has no complex-response losses ("{func_type}")')
         if func_type not in ('MSE', 'RMSE', 'MSE_AFC', 'MSE_LOG_AFC'):
             raise ValueError(f'Function type "{func_type}" is not supported!')
         loss_id = _native.LOSS_IDS[func_type]
@@ -1154,27 +1273,11 @@ class Problem:
         ``J[q, i] = d fr_q / d params_i`` from ONE sweep (one factorisation and one adjoint solve per frequency,
         pfr_jacobian_sweep), where reverse mode through ``getFRFunction`` needs one adjoint sweep per frequency.
         ``scaling_params``: the function is of ``params * scaling_params`` and J is with respect to ``params``."""
-        scaling = 1.0 if scaling_params is None else torch.as_tensor(np.array(scaling_params, dtype=np.float64))
-        transform = self._transform()
-
-        def c_real(p):
-            return torch.view_as_real(_coeffs18(transform, p * scaling)).reshape(-1)      # (36,)
+        c_and_dc = self._coeffs_jacobian(scaling_params)
 
         def fn(freqs, params):
             f = self._freqs(freqs)
-            p = torch.as_tensor(np.asarray(params.detach().cpu() if isinstance(params, torch.Tensor) else params,
-                                           dtype=np.float64)).detach()
-            n = p.numel()
-            if self.material.atype in _JET_TYPES:
-                # c and d c / d params as getLossHessianFunction forms them
-                from ._abd_jet import abd_and_jacobian
-                sc = np.broadcast_to(np.asarray(scaling, dtype=np.float64), (n,))
-                c, J = abd_and_jacobian(self.material, self.geometry.height, (p * scaling).numpy())
-                dc = J * sc[None, :]                                                      # (18, n)
-            else:
-                c = _coeffs18(transform, p * scaling).detach().numpy()
-                jac = torch.autograd.functional.jacobian(c_real, p).numpy().reshape(18, 2, n)
-                dc = jac[:, 0] + 1j * jac[:, 1]                                            # (18, n)
+            c, dc = c_and_dc(params)
             eng = self.engine(f.numel())
             eng.set_coefficients(c)
             dev = eng.device
@@ -1190,6 +1293,54 @@ class Problem:
 
         return fn
 
+    def _coeffs_jacobian(self, scaling_params) -> Callable:
+        """``fn(params) -> (c (18,), dc (18, n_params))`` complex numpy: c(params * scaling) and its derivative with
+        respect to params, as ``getLossHessianFunction`` forms them."""
+        scaling = 1.0 if scaling_params is None else torch.as_tensor(np.array(scaling_params, dtype=np.float64))
+        transform = self._transform()
+
+        def c_real(p):
+            return torch.view_as_real(_coeffs18(transform, p * scaling)).reshape(-1)      # (36,)
+
+        def fn(params):
+            p = torch.as_tensor(np.asarray(params.detach().cpu() if isinstance(params, torch.Tensor) else params,
+                                           dtype=np.float64)).detach()
+            n = p.numel()
+            if self.material.atype in _JET_TYPES:
+                from ._abd_jet import abd_and_jacobian
+                sc = np.broadcast_to(np.asarray(scaling, dtype=np.float64), (n,))
+                c, J = abd_and_jacobian(self.material, self.geometry.height, (p * scaling).numpy())
+                return c, J * sc[None, :]
+            c = _coeffs18(transform, p * scaling).detach().numpy()
+            jac = torch.autograd.functional.jacobian(c_real, p).numpy().reshape(18, 2, n)
+            return c, jac[:, 0] + 1j * jac[:, 1]
+
+        return fn
+
+    def getTFJacobianFunction(self, scaling_params=None, axis=(0, 0, 1)) -> Callable:
+        """``fn(freqs, params) -> (H (F,), dH (F, n_params))``, complex128 tensors on the device: the complex response
+        along ``axis`` (``getTFFunction``) and ``dH[q, i] = d H_q / d params_i`` from ONE sweep
+        (pfr_jacobian_sweep_complex); H is holomorphic in the coefficients, so no real part is taken.
+        ``scaling_params`` as in ``getFRJacobianFunction``."""
+        c_and_dc = self._coeffs_jacobian(scaling_params)
+        ax = _sensing_axis(axis)
+
+        def fn(freqs, params):
+            f = self._freqs(freqs)
+            c, dc = c_and_dc(params)
+            eng = self.engine(f.numel())
+            eng.set_coefficients(c)
+            dev = eng.device
+            F = f.numel()
+            h = torch.empty(F, dtype=torch.complex128, device=dev)
+            jc = torch.empty((F, eng.n_stiff), dtype=torch.complex128, device=dev)
+            flags = torch.zeros(F, dtype=torch.int32, device=dev)
+            berr = torch.full((F, 2), float('nan'), dtype=torch.float64, device=dev)
+            eng.jacobian_sweep(f, jc, fr=h, flags=flags, berr=berr, axis=ax)
+            return h, jc @ torch.as_tensor(np.ascontiguousarray(dc[eng.kidx]), device=dev)
+
+        return fn
+
     def solveForwardJacobian(self, freqs, params=None):
         """``(fr (F,), J (F, n_params))`` (numpy): the frequency response and its derivative with respect to the
         material parameters at every frequency."""
@@ -1198,13 +1349,29 @@ class Problem:
         fr, J = self.getFRJacobianFunction()(freqs, params)
         return fr.cpu().numpy(), J.cpu().numpy()
 
-    def getResidualFunction(self, frequencies, reference_fr, func_type: str, scaling_params=None) -> Callable:
+    def getResidualFunction(self, frequencies, reference_fr, func_type: str, scaling_params=None,
+                            axis=None) -> Callable:
         """``res(params) -> (r (F,), Jr (F, p), const)`` (numpy): ``getLossFunction``'s loss as least squares,
         ``loss = (r @ r + const) / F`` and ``grad = 2 / F * Jr.T @ r`` (``residual_terms``), for Gauss-Newton /
-        Levenberg-Marquardt (``Optimizers.optimize_lm``) and ``parameterCovariance``."""
+        Levenberg-Marquardt (``Optimizers.optimize_lm``) and ``parameterCovariance``.  The complex response's losses
+        (``complex_residual_terms``) have 2 F residuals, ``r = [Re z; Im z]`` and ``Jr = [Re(dz/dH dH); Im(dz/dH dH)]``,
+        with ``loss = r @ r / F`` (``optimize_lm`` divides by the residual count and so reports half of it)."""
         frequencies = np.asarray(frequencies, dtype=np.float64)
         reference_fr = np.asarray(reference_fr)
         assert frequencies.shape[0] == reference_fr.shape[0]
+        if func_type in _native.COMPLEX_LOSS_IDS:
+            tfn = self.getTFJacobianFunction(scaling_params, _sensing_axis(axis))
+            f_dev = self._freqs(frequencies)
+
+            def cres(params):
+                H, dH = tfn(f_dev, params)
+                r, dz, const = complex_residual_terms(H.cpu().numpy(), reference_fr, func_type)
+                Jz = dz[:, None] * dH.cpu().numpy()
+                return r, np.concatenate([Jz.real, Jz.imag]), const
+
+            return cres
+        if axis is not None:
+            raise ValueError(f'"{func_type}" is a loss of the magnitude fr: it takes no sensing axis')
         if func_type not in _native.LOSS_IDS:
             raise ValueError(f'Function type "{func_type}" is not supported!')
         fn = self.getFRJacobianFunction(scaling_params)
@@ -1263,6 +1430,8 @@ class Problem:
         frequencies = np.asarray(frequencies, dtype=np.float64)
         reference_fr = np.asarray(reference_fr)
         assert frequencies.shape[0] == reference_fr.shape[0]
+        if func_type in _native.COMPLEX_LOSS_IDS:
+            raise ValueError(f'the population sweep has no complex-response losses ("{func_type}")')
         if func_type not in _native.LOSS_IDS:
             raise ValueError(f'Function type "{func_type}" is not supported!')
         scaling = 1.0 if scaling_params is None else np.array(scaling_params, dtype=np.float64)
@@ -1279,7 +1448,8 @@ class Problem:
 
         return fn
 
-    def parameterCovariance(self, frequencies, reference_fr, func_type: str, params=None, scaling_params=None):
+    def parameterCovariance(self, frequencies, reference_fr, func_type: str, params=None, scaling_params=None,
+                            axis=None):
         """``(cov (p, p), std (p,))`` of the parameters identified from ``reference_fr``: the Gauss-Newton
         covariance ``sigma^2 (Jr^T Jr)^+`` with ``sigma^2 = (r @ r + const) / (F - p)`` at ``params`` (default: the
         material's; in the units of ``params``, i.e. scaled ones with ``scaling_params``).  A parameter the
@@ -1287,7 +1457,7 @@ class Problem:
         if params is None:
             params = self.parameters if scaling_params is None else \
                 self.parameters / np.asarray(scaling_params, dtype=np.float64)
-        r, Jr, const = self.getResidualFunction(frequencies, reference_fr, func_type, scaling_params)(params)
+        r, Jr, const = self.getResidualFunction(frequencies, reference_fr, func_type, scaling_params, axis)(params)
         return covariance_from_residual(r, Jr, const)
 
     def solveInverse(self, *args, **kwargs):

@@ -27,6 +27,10 @@ PFR_CHECK_FORWARD, PFR_CHECK_ADJOINT, PFR_CHECK_REFINE, PFR_CHECK_CORRECT = 1, 2
 PFR_CHECK_REFINE_ADJ = 16
 LOSS_NONE, LOSS_MSE, LOSS_RMSE, LOSS_MSE_AFC, LOSS_MSE_LOG_AFC, LOSS_COTANGENT = -1, 0, 1, 2, 3, 4
 LOSS_IDS = {"MSE": LOSS_MSE, "RMSE": LOSS_RMSE, "MSE_AFC": LOSS_MSE_AFC, "MSE_LOG_AFC": LOSS_MSE_LOG_AFC}
+# losses of the complex response H (pfr_sweep_complex): |H - ref|^2, |H - ref|^2 / |ref|^2, |log(H / ref)|^2, and the
+# caller's complex dL/dH in ref
+LOSS_CMSE, LOSS_CRMSE, LOSS_CLOG, LOSS_CCOTANGENT = 16, 17, 18, 19
+COMPLEX_LOSS_IDS = {"MSE_COMPLEX": LOSS_CMSE, "RMSE_COMPLEX": LOSS_CRMSE, "MSE_LOG_COMPLEX": LOSS_CLOG}
 
 EXPORT = dict(PERM=0, IPERM=1, FRONTS=2, IDX=3, RELPOS=4, ASM_PTR=5, ASM_COL=6, ASM_NZ=7, EA_PTR=8,
               EA_SRC=9, LEVEL_PTR=10, LEVEL_FRONTS=11, DIRICHLET=12, COUPLING=13)
@@ -94,6 +98,8 @@ _PROTOS = {
     "pfr_stream_order": (C.c_int, [_P, _P]),
     "pfr_sweep_fresh": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_double, _P, _P, _P, _P, _P]),
     "pfr_jacobian_sweep": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P]),
+    "pfr_sweep_complex": (C.c_int, [_P, C.c_int32, _P, _DP, C.c_int32, _P, C.c_double, _P, _P, _P, _P, C.c_int32, _P]),
+    "pfr_jacobian_sweep_complex": (C.c_int, [_P, C.c_int32, _P, _DP, _P, _P, _P, _P]),
     "pfr_combine_batch": (C.c_int, [_P, C.c_int32, _DP, _P, _P]),
     "pfr_population_sweep": (C.c_int, [_P, C.c_int32, _P, _I32P, C.c_int32, _P, _DP, _P, _P, _P, _P]),
     "pfr_solve_multi": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, C.c_int64,
@@ -347,6 +353,29 @@ class Solver:
         ``fr`` (nfreq) on one factorisation per frequency, under the solver's check mode."""
         check(lib().pfr_jacobian_sweep(self._h, int(freqs.numel()), _ptr(freqs), _ptr(fr), _ptr(jc), _ptr(flags),
                                        self._stream(freqs) if stream is None else stream), "pfr_jacobian_sweep")
+
+    def sweep_complex(self, freqs, axis, loss_type=LOSS_NONE, ref=None, scale=1.0, h=None, loss=None, w=None,
+                      flags=None, fresh=False, stream=None):
+        """pfr_sweep_complex: the complex response ``h`` (nfreq, complex128) = axis . (ts U, ts V, W) -- the number the
+        solver's x gives, not conjugated (a reference recorded in the other time convention must be conjugated by the
+        caller) -- and, with one of the LOSS_C* ids and ``ref`` (complex), loss / w as ``sweep`` accumulates them
+        (``fresh``: initialised by the sweep).  ``axis``: 3 real numbers (host)."""
+        a, ap = _f64(np.asarray(axis, dtype=np.float64).reshape(-1))
+        if a.size != 3:
+            raise ValueError("sweep_complex: the sensing axis has 3 components")
+        check(lib().pfr_sweep_complex(self._h, int(freqs.numel()), _ptr(freqs), ap, int(loss_type), _ptr(ref),
+                                      float(scale), _ptr(h), _ptr(loss), _ptr(w), _ptr(flags), int(bool(fresh)),
+                                      self._stream(freqs) if stream is None else stream), "pfr_sweep_complex")
+
+    def jacobian_sweep_complex(self, freqs, axis, jc, h=None, flags=None, stream=None):
+        """pfr_jacobian_sweep_complex: rows ``jc`` (nfreq, n_stiff) complex with dH_q = sum_k jc[q, k] dc_k (no real
+        part taken) and ``h`` (nfreq) complex, under the solver's check mode."""
+        a, ap = _f64(np.asarray(axis, dtype=np.float64).reshape(-1))
+        if a.size != 3:
+            raise ValueError("jacobian_sweep_complex: the sensing axis has 3 components")
+        check(lib().pfr_jacobian_sweep_complex(self._h, int(freqs.numel()), _ptr(freqs), ap, _ptr(h), _ptr(jc),
+                                               _ptr(flags), self._stream(freqs) if stream is None else stream),
+              "pfr_jacobian_sweep_complex")
 
     def combine_batch(self, coef: np.ndarray, out, stream=None):
         """pfr_combine_batch: ``out`` (P, nnz) complex = the operators of the P coefficient rows ``coef`` (P, n_stiff),

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <functional>
 #include <cstring>
 #include <string>
@@ -147,6 +148,7 @@ struct pfr_solver {
   // functional correction (PFR_CHECK_CORRECT): fr of the solve, per-frequency cotangent scale, and
   // the residual walk's per-workgroup dot-product partials (residual_parts(n) x Fc)
   double* fr0 = nullptr;
+  double2* h0 = nullptr;                // the complex response of the solve (pfr_sweep_complex; allocated on first use)
   double2 *mscale = nullptr, *cpart = nullptr;     // mscale complex: the solve-error scale (k_correct_finish)
   int scale_corr = 1;                   // PFR_SCALE_CORR: the solve-error scale of the loss sweeps' cotangent
   int32_t* flags = nullptr;
@@ -1187,6 +1189,13 @@ int pfr_set_functional(pfr_solver* s, int32_t n_support, const int32_t* index, c
 }  // extern "C"
 
 namespace {
+// What a sweep senses: the magnitude fr (the default) or the complex response H along a real axis (pfr_sweep_complex).
+// A value of the call, never solver state: sweep_launches writes it into the chunk's FunctionalArgs.
+struct Response {
+  bool cpx = false;
+  double axis[3] = {0.0, 0.0, 1.0};
+};
+
 // The launches of one sweep (pfr_sweep after its argument checks), direct or under stream capture.
 // jc_dev != NULL (pfr_jacobian_sweep; loss_type = pfr::LOSS_UNIT, scale 1, no ref / loss / w): the reverse sweep of
 // a unit cotangent per frequency whose contraction stays per frequency -- the walk's kpart (or k_contract_q's, where
@@ -1194,11 +1203,15 @@ namespace {
 // k_reduce into w.
 // pop != NULL (pfr_population_sweep): lane group g of the sweep belongs to pop->member[g] and reads the operator
 // popK + pop->member[g] * pop->nnz (chunk_op).
+// resp.cpx (pfr_sweep_complex / pfr_jacobian_sweep_complex): fr_dev holds complex H, loss_type is a PFR_LOSS_C* id,
+// pfr::LOSS_UNIT or PFR_LOSS_NONE, and the functional kernels run in their CPX forms (seed kept in s->h0); every
+// launch after them takes G, fcoef and mscale as it does for the magnitude.
 int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_t loss_type, const double* ref_dev,
                    double scale, double* fr_dev, double* loss_dev, double* w_dev, int32_t* flags_dev, hipStream_t st,
                    bool fresh, double2* jc_dev = nullptr, const double2* popK = nullptr,
-                   const pfr::PopArgs* pop = nullptr) {
+                   const pfr::PopArgs* pop = nullptr, const Response& resp = Response{}) {
   const bool reverse = loss_type != PFR_LOSS_NONE;
+  double* const fr_out = resp.cpx ? nullptr : fr_dev;
   const bool jac = jc_dev != nullptr;
   reset_timing(s);
   const int64_t Fc = s->Fc;
@@ -1212,6 +1225,10 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
   const bool fn_fast = paired && s->fn_dot;            // functional from the bottom-up passes
   if (fn_fast)
     if (int rc0 = fn_setup(s)) return rc0;
+  if (resp.cpx && correct && !s->h0)
+    if (int rc0 = s->alloc(&s->h0, Fc)) return rc0;
+  // seed mode of the functional kernels: the response of this solve kept for k_correct_finish
+  auto seed = [&](pfr::FunctionalArgs& f) { resp.cpx ? (void)(f.h0 = s->h0) : (void)(f.fr0 = s->fr0); };
   bool used[5] = {true, true, true, adj, adj};
   for (int64_t q0 = 0; q0 < nfreq; q0 += Fc) {
     const int nv = (int)std::min<int64_t>(Fc, nfreq - q0);
@@ -1263,20 +1280,25 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
     fa.loss_type = reverse ? loss_type : -1;
     fa.ref = reinterpret_cast<const double2*>(ref_dev);
     fa.scale = scale;
+    if (resp.cpx) {
+      fa.cpx = 1;
+      std::copy(resp.axis, resp.axis + 3, fa.axis);
+      fa.h_out = reinterpret_cast<double2*>(fr_dev);
+    }
     if (adj) pfr::launch_zero(s->G, (int64_t)s->n * Fc, st);
     if (fn_fast) {
       const double2* Yk[3] = {s->Y2, s->YVk, s->YVk + (int64_t)s->n * Fc};
       pfr::launch_fn_dot(s->d_fn_rows, s->n_fn_rows, s->F, s->Y, Yk, Fc, s->fn_parts, st);
       pfr::FunctionalArgs fs = fa;
-      if (correct) fs.fr0 = s->fr0;
-      pfr::launch_functional_fn(fs, s->fn_parts, Fc, nv, q0, correct ? nullptr : fr_dev, correct ? nullptr : s->loss_terms,
+      if (correct) seed(fs);
+      pfr::launch_functional_fn(fs, s->fn_parts, Fc, nv, q0, correct ? nullptr : fr_out, correct ? nullptr : s->loss_terms,
                                 s->G, s->fcoef, st);
     } else if (correct) {
       pfr::FunctionalArgs fs = fa;
-      fs.fr0 = s->fr0;          // seed: fr of this solve kept, G = d fr / d x
+      seed(fs);                 // fr of this solve kept, G = d fr / d x
       pfr::launch_functional(fs, s->X, Fc, nv, q0, nullptr, nullptr, s->G, st);
     } else {
-      pfr::launch_functional(fa, s->X, Fc, nv, q0, fr_dev, s->loss_terms, s->G, st);
+      pfr::launch_functional(fa, s->X, Fc, nv, q0, fr_out, s->loss_terms, s->G, st);
     }
     record(s, 3, st);
     if (adj) {
@@ -1290,7 +1312,7 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
           // the correction fr(x) + Re(mu^T r) needs fr OF the solution x whose residual r is walked (the
           // dot product's fr has its own rounding error, which the correction does not see): fr0 from x
           pfr::FunctionalArgs fs = fa;
-          fs.fr0 = s->fr0;
+          seed(fs);
           pfr::launch_functional(fs, s->X, Fc, nv, q0, nullptr, nullptr, nullptr, st);
         }
       } else if (paired) {
@@ -1316,7 +1338,8 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
       }
       // selective adjoint refinement (PFR_CHECK_REFINE_ADJ): the groups next to a resonance, where the unrefined
       // solves' first-order error dominates the gradient, get one refinement step of mu
-      const bool refine_adj = reverse && correct && cwalk && fn_fast && (s->check_mode & PFR_CHECK_REFINE_ADJ);
+      const bool refine_adj =
+          reverse && correct && cwalk && fn_fast && !resp.cpx && (s->check_mode & PFR_CHECK_REFINE_ADJ);
       // the solve-error scale of the cotangent (k_correct_finish): t_q = mu^T rhsP in, m_q t_q out
       const bool scorr = reverse && correct && s->scale_corr;
       if (correct) {
@@ -1325,7 +1348,9 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
         check_solution(s, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st, s->XA, want_f, cwalk);
         want_f = false;
         if (scorr) pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st);
-        pfr::launch_correct_finish(fa, s->fr0, s->cpart, pfr::residual_parts(s->n), Fc, nv, q0, fr_dev, s->loss_terms,
+        pfr::FunctionalArgs fc = fa;
+        if (resp.cpx) fc.h0 = s->h0;    // the CPX form reads the solve's H there (the magnitude's fr0 is an argument)
+        pfr::launch_correct_finish(fc, s->fr0, s->cpart, pfr::residual_parts(s->n), Fc, nv, q0, fr_out, s->loss_terms,
                                    s->mscale, op, st, refine_adj ? s->gind : nullptr, scorr ? s->tq : nullptr);
       }
       if (refine_adj) {
@@ -1347,7 +1372,7 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
         pfr::launch_axpy_vec(s->XA, s->Y2, (int64_t)s->n * Fc, st, s->glist, Fc);
         check_solution(s, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st, s->XA, false, true, s->glist);
         if (scorr) pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st);
-        pfr::launch_correct_finish(fa, s->fr0, s->cpart, pfr::residual_parts(s->n), Fc, nv, q0, fr_dev, s->loss_terms,
+        pfr::launch_correct_finish(fa, s->fr0, s->cpart, pfr::residual_parts(s->n), Fc, nv, q0, fr_out, s->loss_terms,
                                    s->mscale, op, st, nullptr, scorr ? s->tq : nullptr);
       }
       const double2* msc = correct ? s->mscale : nullptr;
@@ -1471,6 +1496,52 @@ int pfr_jacobian_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, do
   HIP_TRY(hipSetDevice(s->device));
   return sweep_launches(s, nfreq, freqs_dev, pfr::LOSS_UNIT, nullptr, 1.0, fr_dev, nullptr, nullptr, flags_dev,
                         (hipStream_t)stream, false, reinterpret_cast<double2*>(jc_dev));
+}
+
+namespace {
+// the argument checks the two complex sweeps share; the loss sweeps' graph is dropped as pfr_jacobian_sweep does
+int complex_sweep_begin(pfr_solver* s, int32_t nfreq, const double* freqs_dev, const double* axis, bool reverse,
+                        Response* resp) {
+  if (!s || nfreq <= 0 || !freqs_dev || !axis) return fail(PFR_ERR_ARG, "bad complex sweep arguments");
+  if (!(std::isfinite(axis[0]) && std::isfinite(axis[1]) && std::isfinite(axis[2])) ||
+      (axis[0] == 0.0 && axis[1] == 0.0 && axis[2] == 0.0))
+    return fail(PFR_ERR_ARG, "sensing axis zero or not finite");
+  if (s->check_mode & PFR_CHECK_REFINE_ADJ)
+    return fail(PFR_ERR_ARG, "PFR_CHECK_REFINE_ADJ does not apply to the complex response");
+  if (!s->K || !s->M) return fail(PFR_ERR_STATE, "operator not set (pfr_set_operator)");
+  if (!s->has_rhs) return fail(PFR_ERR_STATE, "rhs not set (pfr_set_rhs)");
+  if (!s->has_fn) return fail(PFR_ERR_STATE, "functional not set (pfr_set_functional)");
+  if (reverse && !s->stiff) return fail(PFR_ERR_STATE, "reverse pass needs pfr_set_stiffness");
+  resp->cpx = true;
+  std::copy(axis, axis + 3, resp->axis);
+  s->drop_graph();
+  s->gkey_valid = false;
+  return PFR_OK;
+}
+}  // namespace
+
+int pfr_sweep_complex(pfr_solver* s, int32_t nfreq, const double* freqs_dev, const double* axis, int32_t loss_type,
+                      const double* ref_dev, double scale, double* h_dev, double* loss_dev, double* w_dev,
+                      int32_t* flags_dev, int32_t fresh, void* stream) {
+  const bool reverse = loss_type != PFR_LOSS_NONE;
+  if (reverse && (loss_type < PFR_LOSS_CMSE || loss_type > PFR_LOSS_CCOTANGENT || !ref_dev))
+    return fail(PFR_ERR_ARG, "bad complex loss type / missing ref");
+  if (reverse && s && !w_dev) return fail(PFR_ERR_STATE, "reverse pass needs w_dev");
+  Response resp;
+  if (int rc = complex_sweep_begin(s, nfreq, freqs_dev, axis, reverse, &resp)) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  return sweep_launches(s, nfreq, freqs_dev, loss_type, ref_dev, scale, h_dev, loss_dev, w_dev, flags_dev,
+                        (hipStream_t)stream, fresh != 0, nullptr, nullptr, nullptr, resp);
+}
+
+int pfr_jacobian_sweep_complex(pfr_solver* s, int32_t nfreq, const double* freqs_dev, const double* axis, double* h_dev,
+                               double* jc_dev, int32_t* flags_dev, void* stream) {
+  if (!jc_dev) return fail(PFR_ERR_ARG, "bad jacobian sweep arguments");
+  Response resp;
+  if (int rc = complex_sweep_begin(s, nfreq, freqs_dev, axis, true, &resp)) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  return sweep_launches(s, nfreq, freqs_dev, pfr::LOSS_UNIT, nullptr, 1.0, h_dev, nullptr, nullptr, flags_dev,
+                        (hipStream_t)stream, false, reinterpret_cast<double2*>(jc_dev), nullptr, nullptr, resp);
 }
 
 int pfr_combine_batch(pfr_solver* s, int32_t n_members, const double* coef, double* Kpop_dev, void* stream) {

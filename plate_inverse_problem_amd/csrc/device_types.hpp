@@ -105,6 +105,13 @@ struct ResidArgs {
 constexpr int LOSS_UNIT = PFR_LOSS_COTANGENT + 1;
 
 struct FunctionalArgs {
+  // the complex response H = axis . (ts U, ts V, W) (pfr_sweep_complex; the kernels' CPX forms, which read none of
+  // fr0).  In front of the magnitude's fields: k_functional_fn fetches ref .. fr0 and the kernel argument after this
+  // struct with one scalar load, which fields behind fr0 would split (48 bytes here move the offsets only)
+  int32_t cpx;            // != 0: the launchers take the CPX forms; loss_type PFR_LOSS_C*, LOSS_UNIT or -1
+  double axis[3];         // real sensing axis (dU, dV, dW)
+  double2* h_out;         // H per frequency, indexed by global frequency (may be NULL)
+  double2* h0;            // != NULL: seed mode: H of the solve -> h0, G = a_d = d H / d x; k_correct_finish reads it
   int32_t n_support;
   const int32_t* pidx;    // permuted DOF index of each support entry (device)
   const double* a;        // [aU | aV | aW], 3 * n_support (device)

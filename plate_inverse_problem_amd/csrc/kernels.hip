@@ -2919,6 +2919,73 @@ __device__ __forceinline__ cplx loss_ref(const FunctionalArgs& A, int64_t q) {
   return A.loss_type == LOSS_UNIT ? make_double2(0, 0) : A.ref[q];
 }
 
+// The complex response's loss term and its cotangent g, d term = Re(g dH) (H = d.(ts U, ts V, W), the number the
+// solver's x gives, no conjugation; z = log(H / ref) on the principal branch, its angle from H conj(ref)).
+// PFR_LOSS_CCOTANGENT: no term, g = ref (the caller's dL/dH); LOSS_UNIT (the Jacobian sweep): no term, g = 1.
+__device__ __forceinline__ void loss_term_c(int loss_type, cplx H, cplx r, double& term, cplx& g) {
+  term = 0.0;
+  g = make_double2(0, 0);
+  switch (loss_type) {
+    case PFR_LOSS_CMSE: {
+      const cplx z = make_double2(H.x - r.x, H.y - r.y);
+      term = z.x * z.x + z.y * z.y;
+      g = make_double2(2.0 * z.x, -2.0 * z.y);
+    } break;
+    case PFR_LOSS_CRMSE: {
+      const cplx z = make_double2(H.x - r.x, H.y - r.y);
+      const double r2 = r.x * r.x + r.y * r.y;
+      term = (z.x * z.x + z.y * z.y) / r2;
+      g = make_double2(2.0 * z.x / r2, -2.0 * z.y / r2);
+    } break;
+    case PFR_LOSS_CLOG: {
+      const double h2 = H.x * H.x + H.y * H.y;
+      if (h2 > 0.0) {
+        const cplx p = cmul(H, make_double2(r.x, -r.y));
+        const cplx z = make_double2(log(sqrt(h2)) - log(sqrt(r.x * r.x + r.y * r.y)), atan2(p.y, p.x));
+        term = z.x * z.x + z.y * z.y;
+        // 2 conj(z) / H = 2 conj(z) conj(H) / |H|^2
+        const cplx zh = cmul(make_double2(z.x, -z.y), make_double2(H.x, -H.y));
+        g = make_double2(2.0 * zh.x / h2, 2.0 * zh.y / h2);
+      }
+    } break;
+    case PFR_LOSS_CCOTANGENT:
+      g = r;
+      break;
+    case LOSS_UNIT:
+      g = make_double2(1.0, 0.0);
+      break;
+    default:
+      break;
+  }
+}
+
+// the complex response H = dU ts U + dV ts V + dW W of a frequency
+__device__ __forceinline__ cplx response_c(const FunctionalArgs& A, cplx U, cplx V, cplx W) {
+  const double cu = A.ts * A.axis[0], cv = A.ts * A.axis[1], cw = A.axis[2];
+  return make_double2(cu * U.x + cv * V.x + cw * W.x, cu * U.y + cv * V.y + cw * W.y);
+}
+
+// CPX forms of k_functional / k_functional_fn after U, V, W: H (kept in h0 in seed mode, else written to h_out and
+// its loss term formed) and the scalar s of the cotangent coefficients (cU, cV, cW) = s (ts dU, ts dV, dW) -- 1 in
+// seed mode, scale g_q otherwise; nothing is conjugated (H is linear in x).  false: nothing further to do (forward only)
+__device__ __forceinline__ bool functional_c(const FunctionalArgs& A, cplx H, int64_t q, bool valid, int64_t q_global0,
+                                             double* __restrict__ loss_terms, cplx& s) {
+  s = make_double2(0, 0);
+  if (A.h0) {
+    A.h0[q] = valid ? H : make_double2(0, 0);
+    if (valid) s.x = 1.0;
+    return true;
+  }
+  if (valid && A.h_out) A.h_out[q_global0 + q] = H;
+  if (A.loss_type < 0) return false;
+  double term = 0.0;
+  cplx g = make_double2(0, 0);
+  if (valid) loss_term_c(A.loss_type, H, loss_ref(A, q_global0 + q), term, g);
+  loss_terms[q] = term;
+  s = make_double2(A.scale * g.x, A.scale * g.y);
+  return true;
+}
+
 // Functional correction (adjoint-weighted residual): with mu the adjoint of fr (A^T mu = d fr / d x,
 // k_functional's seed mode) and r = b - A x the forward residual, fr(x*) = fr(x) + Re(mu^T r) up to
 // second order in the solve's error -- the accuracy UMFPACK's default refinement (IRSTEP = 2) buys the
@@ -2937,7 +3004,10 @@ __device__ __forceinline__ cplx loss_ref(const FunctionalArgs& A, int64_t q) {
 // mu^T A x = mu^T b - mu^T r is two dot products the sweep has already formed (k_rhs_dot, the correction's
 // walk): dividing by it removes both factors with no further solve ("Gradient at full size")
 // POP (the population sweep): the rhs scale's beta from the member of the workgroup's group
-template <bool POP = false>
+// CPX (the complex response, linear in x: mu = A^-T a_d does not depend on x, so H + mu^T r is exact in the forward
+// error and first order only in mu's): H_c = h0 + mu^T r with the whole complex sum, m_q = scale g(H_c), under tq
+// m_q = scale g(H_c) H_c / (mu^T b - mu^T r) -- the same identity, H* = mu*^T b; gind is not formed
+template <bool POP = false, bool CPX = false>
 __global__ __launch_bounds__(256) void k_correct_finish(FunctionalArgs A, const double* __restrict__ fr0,
                                                         const cplx* __restrict__ cpart, int nparts, int64_t Fc,
                                                         int nvalid, int64_t q_global0, double* __restrict__ fr_out,
@@ -2957,6 +3027,33 @@ __global__ __launch_bounds__(256) void k_correct_finish(FunctionalArgs A, const 
   if (w != 0) return;
   d = cadd(cadd(sd[0][lane], sd[1][lane]), cadd(sd[2][lane], sd[3][lane]));
   const bool valid = q < nvalid;
+  if constexpr (CPX) {
+    const cplx H = cadd(A.h0[q], d);
+    if (valid && A.h_out) A.h_out[q_global0 + q] = H;
+    if (A.loss_type < 0) return;
+    double term = 0.0;
+    cplx g = make_double2(0, 0);
+    if (valid) loss_term_c(A.loss_type, H, loss_ref(A, q_global0 + q), term, g);
+    loss_terms[q] = term;
+    cplx m = make_double2(A.scale * g.x, A.scale * g.y);
+    if (tq) {
+      const cplx t0 = tq[q];
+      if (valid) {
+        const double om = 6.283185307179586 * bsc.freqs[q];
+        const cplx bs = make_double2(fma(-om * om, bsc.mass_sum, bsc.beta_re), bsc.beta_im);
+        const cplx bt = cmul(bs, t0);
+        const cplx den = make_double2(bt.x - d.x, bt.y - d.y);        // mu^T A x
+        const double dd = den.x * den.x + den.y * den.y;
+        if (dd > 0.0 && isfinite(dd)) {
+          const cplx mh = cmul(cmul(m, H), make_double2(den.x, -den.y));   // m H / den = m H conj(den) / |den|^2
+          m = make_double2(mh.x / dd, mh.y / dd);
+        }
+      }
+      tq[q] = cmul(m, t0);
+    }
+    mscale[q] = m;
+    return;
+  }
   const double fr = fr0[q] + d.x;
   if (gind) {
     double v = valid ? fabs(d.x) / fabs(fr) : 0.0;
@@ -3111,6 +3208,8 @@ __global__ void k_functional_tangent(FunctionalArgs A, const cplx* __restrict__ 
 // ------------------------------------------------------------------ K4: functional + loss cotangent
 // U = aU.x, V = aV.x, W = aW.x; fr = sqrt(ts^2|U|^2 + ts^2|V|^2 + |W|^2)  (Problem.py:454-477)
 // loss terms of Problem.py:948-975; g = dl/fr * (ts^2 conj(U) aU + ts^2 conj(V) aV + conj(W) aW)
+// CPX: the complex response H = d.(ts U, ts V, W) in place of fr (functional_c), g = s (ts dU aU + ts dV aV + dW aW)
+template <bool CPX = false>
 __global__ void k_functional(FunctionalArgs A, const cplx* __restrict__ X, int64_t Fc, int nvalid, int64_t q_global0,
                              double* __restrict__ fr_out, double* __restrict__ loss_terms, cplx* __restrict__ G) {
   const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -3123,6 +3222,16 @@ __global__ void k_functional(FunctionalArgs A, const cplx* __restrict__ X, int64
     U.x = fma(au, x.x, U.x); U.y = fma(au, x.y, U.y);
     Vv.x = fma(av, x.x, Vv.x); Vv.y = fma(av, x.y, Vv.y);
     W.x = fma(aw, x.x, W.x); W.y = fma(aw, x.y, W.y);
+  }
+  if constexpr (CPX) {
+    cplx sc;
+    if (!functional_c(A, response_c(A, U, Vv, W), q, q < nvalid, q_global0, loss_terms, sc) || !G) return;
+    const double du = A.ts * A.axis[0], dv = A.ts * A.axis[1], dw = A.axis[2];
+    for (int t = 0; t < A.n_support; ++t) {
+      const double ad = A.a[t] * du + A.a[A.n_support + t] * dv + A.a[2 * A.n_support + t] * dw;
+      G[(int64_t)A.pidx[t] * Fc + q] = make_double2(ad * sc.x, ad * sc.y);
+    }
+    return;
   }
   const double ts2 = A.ts * A.ts;
   const double u2 = U.x * U.x + U.y * U.y, v2 = Vv.x * Vv.x + Vv.y * Vv.y, w2 = W.x * W.x + W.y * W.y;
@@ -3188,6 +3297,7 @@ __global__ __launch_bounds__(256) void k_fn_dot(const int2* __restrict__ rows, i
 
 // k_functional with U, V, W from k_fn_dot's partials; also the cotangent coefficients (c_U, c_V, c_W)
 // per frequency (fcoef, 3 x Fc) for k_fn_combine.  G (zeroed) gets the adjoint rhs at the support rows.
+template <bool CPX = false>
 __global__ void k_functional_fn(FunctionalArgs A, const cplx* __restrict__ parts, int64_t Fc, int nvalid,
                                 int64_t q_global0, double* __restrict__ fr_out, double* __restrict__ loss_terms,
                                 cplx* __restrict__ G, cplx* __restrict__ fcoef) {
@@ -3198,6 +3308,19 @@ __global__ void k_functional_fn(FunctionalArgs A, const cplx* __restrict__ parts
     U = cadd(U, parts[((int64_t)p * 3 + 0) * Fc + q]);
     Vv = cadd(Vv, parts[((int64_t)p * 3 + 1) * Fc + q]);
     W = cadd(W, parts[((int64_t)p * 3 + 2) * Fc + q]);
+  }
+  if constexpr (CPX) {
+    cplx sc;
+    (void)functional_c(A, response_c(A, U, Vv, W), q, q < nvalid, q_global0, loss_terms, sc);
+    const double du = A.ts * A.axis[0], dv = A.ts * A.axis[1], dw = A.axis[2];
+    fcoef[q] = make_double2(du * sc.x, du * sc.y);
+    fcoef[Fc + q] = make_double2(dv * sc.x, dv * sc.y);
+    fcoef[2 * Fc + q] = make_double2(dw * sc.x, dw * sc.y);
+    for (int t = 0; t < A.n_support; ++t) {
+      const double ad = A.a[t] * du + A.a[A.n_support + t] * dv + A.a[2 * A.n_support + t] * dw;
+      G[(int64_t)A.pidx[t] * Fc + q] = make_double2(ad * sc.x, ad * sc.y);
+    }
+    return;
   }
   const double ts2 = A.ts * A.ts;
   const double fr = sqrt(ts2 * (U.x * U.x + U.y * U.y) + ts2 * (Vv.x * Vv.x + Vv.y * Vv.y) + W.x * W.x + W.y * W.y);
@@ -3750,8 +3873,10 @@ void launch_fn_dot(const int2* rows, int nrows, const double2* F, const double2*
 
 void launch_functional_fn(const FunctionalArgs& A, const double2* parts, int64_t Fc, int nvalid, int64_t q0,
                           double* fr_out, double* loss_terms, double2* G, double2* fcoef, hipStream_t st) {
-  LAUNCH(k_functional_fn, dim3((unsigned)((Fc + 63) / 64)), dim3(64), st, A, parts, Fc, nvalid, q0, fr_out, loss_terms,
-         G, fcoef);
+  with_bool(A.cpx != 0, [&](auto cx) {
+    LAUNCH(k_functional_fn<CV(cx)>, dim3((unsigned)((Fc + 63) / 64)), dim3(64), st, A, parts, Fc, nvalid, q0, fr_out,
+           loss_terms, G, fcoef);
+  });
 }
 
 void launch_fn_combine(const int* rows, int nrows, const double2* fcoef, double2* const* Yk, int64_t Fc, hipStream_t st) {
@@ -3838,10 +3963,11 @@ void launch_correct_finish(const FunctionalArgs& A, const double* fr0, const dou
   bsc.mass_sum = op.mass_sum;
   bsc.beta_re = op.beta_re;
   bsc.beta_im = op.beta_im;
-  with_bool(op.pop.member != nullptr, [&](auto pp) {
-    LAUNCH(k_correct_finish<CV(pp)>, dim3((unsigned)(Fc / 64)), dim3(256), st, A, fr0, cpart, nparts, Fc, nvalid, q0,
-           fr_out, loss_terms, mscale, gind, tq, bsc, op.pop);
-  });
+  dispatch([&](auto pp, auto cx) {
+    if constexpr (!(CV(pp) && CV(cx)))   // the population sweep has no complex response
+      LAUNCH((k_correct_finish<CV(pp), CV(cx)>), dim3((unsigned)(Fc / 64)), dim3(256), st, A, fr0, cpart, nparts, Fc,
+             nvalid, q0, fr_out, loss_terms, mscale, gind, tq, bsc, op.pop);
+  }, flag(op.pop.member != nullptr), flag(A.cpx != 0));
 }
 
 void launch_berr_finish(double* acc, int64_t Fc, int nvalid, double tol, int flag, int* flags, double* berr_out,
@@ -3871,7 +3997,10 @@ void launch_functional_tangent(const FunctionalArgs& A, const double2* X, const 
 
 void launch_functional(const FunctionalArgs& A, const double2* X, int64_t Fc, int nvalid, int64_t q0, double* fr_out,
                        double* loss_terms, double2* G, hipStream_t st) {
-  LAUNCH(k_functional, dim3((unsigned)((Fc + 63) / 64)), dim3(64), st, A, X, Fc, nvalid, q0, fr_out, loss_terms, G);
+  with_bool(A.cpx != 0, [&](auto cx) {
+    LAUNCH(k_functional<CV(cx)>, dim3((unsigned)((Fc + 63) / 64)), dim3(64), st, A, X, Fc, nvalid, q0, fr_out, loss_terms,
+           G);
+  });
 }
 
 void launch_gather_entries(const int4* ent, int nent, const double* stiff, int ns, double* se, hipStream_t st) {
