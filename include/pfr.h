@@ -184,6 +184,39 @@ PFR_API int32_t pfr_solver_max_batch(const pfr_solver* s);
 PFR_API int pfr_symbolic_schedule(const pfr_symbolic* sym, int32_t max_batch, int32_t* dst, int64_t capacity_bytes);
 PFR_API int pfr_solver_schedule(const pfr_solver* s, int32_t* dst, int64_t capacity_bytes);
 
+/* Pruning: factor and solve only the trees of the elimination forest that the load reaches (symmetric solvers; off
+ * by default).  A tree is loaded when one of its rows has a non-zero entry of the vector given to pfr_set_rhs, or is
+ * a coupled row of a Dirichlet node whose entry of that vector is non-zero; on every other tree the forward solution
+ * of the operator right-hand side is exactly zero, and so is every term of the loss, the gradient, the Jacobian rows
+ * and the functional correction that the tree's adjoint enters (each multiplies it by the forward solution or by the
+ * load).  With pruning on, the operator-form sweeps (pfr_sweep, pfr_sweep_fresh, pfr_sweep_complex, the two Jacobian
+ * sweeps, pfr_population_sweep) factorise, solve and walk the loaded trees only: a view of the plan and schedule over
+ * their fronts, rebuilt when pfr_set_rhs changes which trees are loaded.  Rows of unloaded trees hold exact zeros in
+ * the solution vectors, the adjoint's backward error is taken over the loaded rows, and a pivot failure inside an
+ * unloaded tree no longer flags its frequency (nothing of that tree is factorised).  A solver on which every tree is
+ * loaded builds nothing and launches exactly what it launches with pruning off.  pfr_hessian_sweep and the refinement
+ * check modes (PFR_CHECK_REFINE, PFR_CHECK_REFINE_ADJ) keep the full plan; so do pfr_solve / pfr_solve_multi, which
+ * need a general analysis, where no view is ever built.
+ * pfr_debug_solution still returns the whole adjoint: it completes the unloaded trees for the last chunk on demand.
+ * pfr_solver_active: the number of fronts the sweeps factorise, and per front 0 / 1 into mask (may be NULL; capacity in
+ * entries).  pfr_solver_schedule_active: the schedule of the view the sweeps launch (pfr_solver_schedule's layout;
+ * the full schedule while nothing is pruned).  pfr_solver_alg_bytes / pfr_solver_solve_bytes count what the sweeps
+ * launch under the current check mode: the view, or the full plan under the refinement modes. */
+PFR_API int pfr_set_prune(pfr_solver* s, int32_t on);
+/* Host only, no device: the views pruning builds on a solver for max_batch whose right-hand side vector is rhs (caller
+ * numbering, n entries) and whose functional support is index[0 .. n_support).  mask (n_fronts): 1 = the front's tree
+ * is loaded.  Builds the plan and schedule of the loaded trees and of the rest (the view pfr_debug_solution completes
+ * the adjoint on) and checks every index and record of both as pfr_solver_create's plan is checked (PFR_ERR_STATE and
+ * pfr_last_error on a violation); sched_active / sched_rest / sched_full (may be NULL, capacity in bytes each): their
+ * schedules and the full plan's with the same reaches, in pfr_symbolic_schedule's layout.  A view's records take every
+ * launch-shape decision as the full plan takes it (from the whole analysis' level geometry and the full reaches) and
+ * only their counts from the view: each front runs the same arithmetic in the same order with pruning on and off. */
+PFR_API int pfr_symbolic_prune(const pfr_symbolic* sym, int32_t max_batch, const double* rhs, int32_t n_support,
+                               const int32_t* index, int32_t* mask, int32_t* sched_active, int32_t* sched_rest,
+                               int32_t* sched_full, int64_t capacity_bytes);
+PFR_API int32_t pfr_solver_active(const pfr_solver* s, int32_t* mask, int64_t capacity);
+PFR_API int pfr_solver_schedule_active(const pfr_solver* s, int32_t* dst, int64_t capacity_bytes);
+
 /* ---------------------------------------------------------------- InnerState-compatible entry points
  * pfr_solve: x[q] = A_q^{-1} b[q]  (transpose != 0: A_q^{-T} b[q], NON-conjugate, = UMFPACK_Aat,
  * InnerState.h:183-185).  A_q values on the CSC pattern: data_dev + q * data_stride (complex, nnz);

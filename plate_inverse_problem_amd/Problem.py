@@ -296,10 +296,15 @@ class _Engine:
         self.streams = [torch.cuda.Stream(self.device) for i in range(lanes)]
         if lanes > 1 and os.environ.get("PFR_PAR_LAUNCH", "1") != "0":
             self._pool = [_LaneThread() for _ in range(lanes - 1)]
+        # pruning (include/pfr.h, pfr_set_prune; PFR_PRUNE=0: off): only the elimination trees the load reaches are
+        # factorised and solved -- for a mid-plane-symmetric material the in-plane block carries none
+        prune = self.symmetric and os.environ.get("PFR_PRUNE", "1") != "0"
         for sv in self.solvers:
             sv.set_stiffness(self.stiff, self.e[self.kidx])
             sv.set_operator(torch.view_as_real(self.K), self.mass)      # K(theta) shared by the lanes
             sv.set_functional(self._sup, self._a3, self._ts)
+            if prune:
+                sv.set_prune(True)
             sv.set_check(self.check_mode, self.check_tol)
             sv.set_refine_tol(self.refine_tol)
         self._coef_key = None          # new solvers: rhs scale not set yet
@@ -349,7 +354,31 @@ class _Engine:
         beta = complex(self.e @ c)
         for sv in self.solvers:
             sv.set_rhs(self.rhs, beta, self.mass_sum)
+        if self._coef_key is None:
+            self._pruned_stats()
         self._coef_key = key
+
+    def _pruned_stats(self):
+        """``stats`` of what the sweeps factorise: under pruning the loaded trees' fronts (the whole pattern's
+        figures beside them as ``*_full``); ``Symbolic.stats()`` itself is unchanged."""
+        full = self.sym.stats()
+        st = dict(full)
+        mask = self.solver.active_fronts().astype(bool)
+        if not mask.all():
+            fr = self.sym.export("FRONTS")[mask]
+            ns, f = fr[:, 0].astype(np.float64), fr[:, 1].astype(np.float64)
+            # sum over the pivots k of a front of 8 m^2 + 8 m, m = f - k - 1 (symbolic.cpp)
+            a, b = f - ns, f - 1.0          # m runs over a .. b
+            s1 = (b * (b + 1) - (a - 1) * a) / 2.0
+            s2 = (b * (b + 1) * (2 * b + 1) - (a - 1) * a * (2 * a - 1)) / 6.0
+            part = dict(n_fronts=int(mask.sum()), total_rows=int(fr[:, 1].sum()),
+                        factor_entries=int((fr[:, 1] ** 2).sum()),
+                        nnz_lu=int((2 * fr[:, 0] * fr[:, 1] - fr[:, 0] ** 2).sum()),
+                        factor_flops=float((8.0 * s2 + 8.0 * s1).sum()), max_front=int(fr[:, 1].max()))
+            for k, v in part.items():
+                st[k + "_full"] = full[k]
+                st[k] = v
+        self.stats = st
 
     def _split(self, n):
         """Contiguous frequency block of each lane (multiples of 64 but the last)."""
@@ -586,6 +615,7 @@ class _Engine:
             # the Dirichlet vector and the mass sum (the population sweep reads them, not this beta)
             for sv in self.solvers:
                 sv.set_rhs(self.rhs, complex(beta[0]), self.mass_sum)
+            self._pruned_stats()
         f = freqs[torch.as_tensor(index, device=dev)].contiguous()
         fr = torch.empty(L, dtype=torch.float64, device=dev)
         jc = torch.empty((L, self.n_stiff), dtype=torch.complex128, device=dev) if jac else None

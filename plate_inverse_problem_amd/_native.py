@@ -86,6 +86,10 @@ _PROTOS = {
     "pfr_solver_max_batch": (C.c_int32, [_P]),
     "pfr_symbolic_schedule": (C.c_int, [_P, C.c_int32, _I32P, C.c_int64]),
     "pfr_solver_schedule": (C.c_int, [_P, _I32P, C.c_int64]),
+    "pfr_set_prune": (C.c_int, [_P, C.c_int32]),
+    "pfr_symbolic_prune": (C.c_int, [_P, C.c_int32, _DP, C.c_int32, _I32P, _I32P, _I32P, _I32P, _I32P, C.c_int64]),
+    "pfr_solver_active": (C.c_int32, [_P, _I32P, C.c_int64]),
+    "pfr_solver_schedule_active": (C.c_int, [_P, _I32P, C.c_int64]),
     "pfr_solve": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32, _P, _P]),
     "pfr_matvec": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32, _P]),
     "pfr_set_stiffness": (C.c_int, [_P, C.c_int32, _P, _DP]),
@@ -264,6 +268,25 @@ class Symbolic:
         return _schedule(self.stats()["n_levels"], lambda dst, cap: check(
             lib().pfr_symbolic_schedule(self._h, int(max_batch), dst, cap), "pfr_symbolic_schedule"))
 
+    def prune(self, max_batch: int, rhs, support=()) -> tuple:
+        """pfr_symbolic_prune: (mask, schedule of the loaded trees' view, of the rest, of the full plan) for a solver whose
+        right-hand side vector is ``rhs`` (caller numbering) and whose functional support is ``support``; both
+        views' plans and schedules are checked (NativeError on a violation).  Needs no device."""
+        st = self.stats()
+        r, rp = _f64(rhs)
+        sup, sp = _i32(np.asarray(support, dtype=np.int32))
+        mask = np.zeros(st["n_fronts"], dtype=np.int32)
+        cols = sum(len(c) for _, c in SCHEDULE)
+        flat = np.zeros((3, st["n_levels"] * cols), dtype=np.int32)
+        check(lib().pfr_symbolic_prune(self._h, int(max_batch), rp, int(sup.size), sp, mask.ctypes.data_as(_I32P),
+                                       flat[0].ctypes.data_as(_I32P), flat[1].ctypes.data_as(_I32P),
+                                       flat[2].ctypes.data_as(_I32P), flat[0].nbytes),
+              "pfr_symbolic_prune")
+
+        def table(row):
+            return _schedule(st["n_levels"], lambda dst, cap: C.memmove(dst, row.ctypes.data, row.nbytes))
+        return mask, table(flat[0]), table(flat[1]), table(flat[2])
+
     def __del__(self):
         h = getattr(self, "_h", None)
         if h is not None and _lib is not None:
@@ -297,6 +320,23 @@ class Solver:
         """pfr_solver_schedule: the records this solver's level loops launch, with its current reaches."""
         return _schedule(self.sym.stats()["n_levels"], lambda dst, cap: check(
             lib().pfr_solver_schedule(self._h, dst, cap), "pfr_solver_schedule"))
+
+    def set_prune(self, on: bool = True):
+        """pfr_set_prune: the operator-form sweeps factorise and solve only the elimination trees the load
+        reaches (include/pfr.h).  Off by default; nothing changes on a solver whose trees are all loaded."""
+        check(lib().pfr_set_prune(self._h, int(bool(on))), "pfr_set_prune")
+
+    def active_fronts(self) -> np.ndarray:
+        """pfr_solver_active: per front 1 when the sweeps factorise it (all ones while nothing is pruned)."""
+        mask = np.zeros(self.sym.stats()["n_fronts"], dtype=np.int32)
+        lib().pfr_solver_active(self._h, mask.ctypes.data_as(_I32P), mask.size)
+        return mask
+
+    def schedule_active(self) -> dict:
+        """pfr_solver_schedule_active: the schedule of the view the sweeps launch (``schedule()`` while nothing is
+        pruned)."""
+        return _schedule(self.sym.stats()["n_levels"], lambda dst, cap: check(
+            lib().pfr_solver_schedule_active(self._h, dst, cap), "pfr_solver_schedule_active"))
 
     @staticmethod
     def _stream(t):

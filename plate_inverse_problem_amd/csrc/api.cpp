@@ -57,16 +57,20 @@ int64_t round64(int64_t x) { return (x + 63) / 64 * 64; }
 
 }  // namespace
 
-struct pfr_solver {
-  int device = 0;
-  int n = 0;
-  int64_t nnz = 0;
-  int64_t Fc = 0;  // frequencies per chunk (multiple of 64)
-  std::vector<int32_t> level_ptr, perm, iperm;
+// What the level loops of a sweep walk: the level lists, the gather records of the factor classes, the reaches, the
+// row lists derived from them and the launch schedule of a set of whole elimination trees -- every front (the solver
+// itself: the full view), the loaded trees (pfr_set_prune: pfr_solver::act) or the unloaded ones (pfr_solver::comp,
+// built when pfr_debug_solution completes the adjoint).  All views index the same factor storage and vectors.
+struct SolverView {
+  std::vector<char> active;             // per front: covered by the view
+  std::vector<int32_t> level_ptr;       // per level: first front of the view's list
   std::vector<int32_t> tile_ptr, blk_ptr, asm_ptr, item_ptr;   // per level: first Schur tile / block, A11 record, L21 item
-  DevPattern P{};
-  // owned device arrays
-  std::vector<void*> owned;
+  std::vector<void*> mine;              // device arrays of a view built after the solver (freed with the view)
+  int32_t* d_walk = nullptr;            // the residual walks' row list (original order); -1: a row the view skips
+  int post_n = 0;                       // Dirichlet nodes on the view's fronts, with their column entries
+  int2* post_dir = nullptr;             // (k_dirichlet_post over them)
+  int32_t* post_dptr = nullptr;
+  int2* post_de = nullptr;
   int32_t* d_level_fronts = nullptr;
   int4* d_tiles = nullptr;              // Schur tiles (front, i0, j0, 0), grouped by level
   int4* d_items = nullptr;              // off-diagonal panel items (front, first row/col, kind, record offset)
@@ -85,6 +89,54 @@ struct pfr_solver {
   int4* d_asm = nullptr;                // panel-entry assembly records (dst, nz, first child source, 0), by level
   int32_t* d_asm_xp = nullptr;          // per 8-record chunk: range of further child sources in d_asm_x
   int2* d_asm_x = nullptr;              // (record within chunk, child element id)
+  // right-hand-side reach (0 = forward operator rhs, 1 = loss adjoint on the functional support):
+  // the fronts holding a support row and their elimination-tree ancestors -- the only fronts
+  // whose bottom-up solve can be non-zero (per-front flags + the fronts level by level)
+  std::vector<int32_t> level_fronts_host;
+  std::vector<char> reach_host[2];
+  int32_t* d_reach[2] = {nullptr, nullptr};
+  int32_t* d_reach_fronts[2] = {nullptr, nullptr};
+  std::vector<int32_t> reach_ptr[2];
+  bool fn_ready = false;                // row lists below match the current reaches
+  int2* d_fn_rows = nullptr;            // (row, factor element of U(row, row)): pivot rows in both reaches
+  int n_fn_rows = 0;
+  int32_t* d_sup_rows = nullptr;        // pivot rows of the support-reach fronts
+  int n_sup_rows = 0;
+  // algorithmic HBM bytes per frequency of each factorisation kernel class, per level (16 B per complex entry
+  // loaded or stored; index data is shared by all frequencies and not counted)
+  std::vector<std::array<int64_t, pfr::NKC>> lev_bytes;
+  // which kernel form every level launches in every pass, with what shape (plan.hpp): built with the view from the
+  // launch-shape knobs (sched.knobs, read from the environment when the solver is created), its reach-dependent
+  // records again whenever a reach changes (set_reach)
+  pfr::Schedule sched;
+};
+
+struct pfr_solver : SolverView {
+  int device = 0;
+  int n = 0;
+  int64_t nnz = 0;
+  int64_t Fc = 0;  // frequencies per chunk (multiple of 64)
+  std::vector<int32_t> perm, iperm;
+  DevPattern P{};
+  // owned device arrays
+  std::vector<void*> owned;
+  // pruning (pfr_set_prune): the operator-form sweeps on the loaded trees only.  S: the analysis
+  // (kept by symmetric solvers: views are built from it); act: the loaded trees' view, NULL while pruning is off or
+  // every tree is loaded; comp: its complement; unl_rows: the pivot rows of the unloaded fronts as [first, last)
+  // ranges; unl_dirty: a sweep on the full view (or the accessor's completion) wrote rows of unloaded trees in X / XA,
+  // zeroed again before the next pruned sweep; comp_done: the accessor completed the last chunk's adjoint already
+  int prune = 0;
+  Symbolic S;
+  std::vector<pfr::I2> h_dir, h_de;
+  std::vector<int32_t> h_dptr;
+  std::vector<int32_t> reach_rows[2];   // the rows the full view's reaches were set from
+  SolverView* act = nullptr;
+  SolverView* comp = nullptr;
+  std::vector<std::pair<int32_t, int32_t>> unl_rows;
+  bool unl_dirty = false, comp_done = false, last_pruned = false;
+  pfr::ChunkOp last_op;                 // the last chunk's operator (the accessor's completion factorises with it)
+  hipStream_t last_st = nullptr;        // ... and its stream
+  bool last_adj = false;                // ... which solved an adjoint (G holds its seed)
   int32_t* d_colptr = nullptr;
   int32_t* d_rowind = nullptr;
   // symmetric mode (options.symmetric): U never formed; Dirichlet nodes decoupled
@@ -98,25 +150,16 @@ struct pfr_solver {
   int2* d_de = nullptr;                 // (permuted row, entry) by Dirichlet node
   int32_t* d_cslot = nullptr;           // per permuted row: coupled-row slot or -1
   double2* Bc = nullptr;                // forward right-hand-side corrections (n_crow x Fc)
-  // right-hand-side reach (0 = forward operator rhs, 1 = loss adjoint on the functional support):
-  // the fronts holding a support row and their elimination-tree ancestors -- the only fronts
-  // whose bottom-up solve can be non-zero (per-front flags + the fronts level by level)
-  std::vector<int32_t> front_of_col, front_parent, level_fronts_host, front_ns, front_f;
-  std::vector<char> reach_host[2];
+  std::vector<int32_t> front_of_col, front_parent, front_ns, front_f;
   // functional from the bottom-up passes (symmetric loss / correction sweeps, PFR_FN_DOT, default on):
   // slices 1-3 of the forward bottom-up chain solve L w_k = a_k over the support's reach; F_k = w_k^T
   // diag(U)^-1 y; the adjoint's bottom-up result = sum_k c_k w_k -- no top-down pass over the support's
   // fronts and no separate adjoint bottom-up pass
   int fn_dot = 1;
-  bool fn_ready = false;                // row lists below match the current reaches
   std::vector<int32_t> front_off, front_col0;
   std::vector<double> a_perm;           // 3 x n: a_k at the permuted support rows
   double* d_aP = nullptr;               // device copy of a_perm
   int32_t* d_noslot = nullptr;          // n x -1 (no coupling slot: slices 1-3)
-  int2* d_fn_rows = nullptr;            // (row, factor element of U(row, row)): pivot rows in both reaches
-  int n_fn_rows = 0;
-  int32_t* d_sup_rows = nullptr;        // pivot rows of the support-reach fronts
-  int n_sup_rows = 0;
   double2* WVk = nullptr;               // 3 x total_rows x Fc (slices 1-3 work vectors)
   double2* YVk = nullptr;               // 2 x n x Fc (slices 2, 3 solutions; slice 1's is Y2)
   double2* fn_parts = nullptr;          // FN_PARTS x 3 x Fc
@@ -125,16 +168,13 @@ struct pfr_solver {
   // the functional correction's walk): per (workgroup, k, frequency) sums, reduced with m_q by k_reduce_q
   int contract_walk = 1;
   double2* kpart = nullptr;
-  int32_t* d_reach[2] = {nullptr, nullptr};
-  int32_t* d_reach_fronts[2] = {nullptr, nullptr};
-  std::vector<int32_t> reach_ptr[2];
   double2 *F = nullptr, *WV = nullptr, *X = nullptr, *Y = nullptr, *XA = nullptr, *G = nullptr, *Y2 = nullptr;
   double2* XR = nullptr;                // refinement correction of the adjoint (PFR_CHECK_REFINE)
   // Hessian sweep: permuted matrix by rows and by columns ((ptr, index, nz) each),
   // tangent solution / adjoint vectors, combined tangent operators (lazily allocated)
   int32_t *d_rptr = nullptr, *d_ridx = nullptr, *d_rnz = nullptr;
-  int32_t* d_walk = nullptr;            // rows (permuted numbering) in original order: the residual
-                                        // walks' order (mesh-local gathers, whatever the ordering)
+  // d_walk (SolverView): rows (permuted numbering) in original order: the residual walks' order (mesh-local
+  // gathers, whatever the ordering)
   int32_t *d_cptr = nullptr, *d_cidx = nullptr, *d_cnz = nullptr;
   double2 *DX = nullptr, *DL = nullptr, *Kdir = nullptr;
   // gradient contraction entries (k_contract_eg): per permuted row a pseudo-entry (-1, -1, -1, i), then
@@ -180,14 +220,7 @@ struct pfr_solver {
   int timing = 0;
   std::vector<ChunkEvents> tev;
   int n_tev = 0;                        // chunks recorded by the last call
-  // algorithmic HBM bytes per frequency of each factorisation kernel class, per level (16 B per complex entry
-  // loaded or stored; index data is shared by all frequencies and not counted)
-  std::vector<std::array<int64_t, pfr::NKC>> lev_bytes;
   pfr::Workspace ws;                    // element counts of the chunk buffers (plan.cpp; what is allocated)
-  // which kernel form every level launches in every pass, with what shape (plan.hpp): built when the solver is
-  // created from the launch-shape knobs (sched.knobs, read from the environment then), its reach-dependent records
-  // again whenever a reach changes (set_reach)
-  pfr::Schedule sched;
   int res_unroll = 8;                   // PFR_RES_UNROLL: entries per gather batch of the adjoint check walk (4 / 8)
   // backward-error checks (pfr_set_check): PFR_CHECK_* bits, tolerance, optional per-item output;
   // per-frequency maxima scratch, forward and adjoint (kept zero between checks)
@@ -229,6 +262,8 @@ struct pfr_solver {
   }
   ~pfr_solver() {
     drop_graph();
+    delete act;    // their device arrays are in `owned`
+    delete comp;
     for (void* p : owned) (void)hipFree(p);
     for (auto& g : stage) {
       if (g.host) (void)hipHostFree(g.host);
@@ -370,8 +405,9 @@ int stage_upload(pfr_solver* s, int slot, const void* src, size_t bytes, void** 
   return PFR_OK;
 }
 
-int factor_all(pfr_solver* s, const pfr::ChunkOp& op, int mode, const double2* data, int64_t ds, int nvalid,
-               hipStream_t st) {
+// v (here and below): the view whose fronts the pass walks -- *s for every front
+int factor_all(pfr_solver* s, const SolverView& v, const pfr::ChunkOp& op, int mode, const double2* data, int64_t ds,
+               int nvalid, hipStream_t st) {
   const int L = (int)s->level_ptr.size() - 1;
   const int ngroups = (int)(s->Fc / 64);
   const bool kt = (s->timing & 2) && s->n_tev < (int)s->tev.size() && !s->tev[s->n_tev].kev.empty();
@@ -381,17 +417,17 @@ int factor_all(pfr_solver* s, const pfr::ChunkOp& op, int mode, const double2* d
   };
   if (kt) s->tev[s->n_tev].f0 = false;
   for (int l = 0; l < L; ++l) {
-    const pfr::FactorLevel& r = s->sched.factor[l];
-    const int32_t* lvl = s->d_level_fronts + s->level_ptr[l];
+    const pfr::FactorLevel& r = v.sched.factor[l];
+    const int32_t* lvl = v.d_level_fronts + v.level_ptr[l];
     mark(l, 0);
     if (r.fused0 && mode == 0) {
       if (kt) s->tev[s->n_tev].f0 = true;
       // the bottom level's leaf fronts in one pass (k_front0): A11, L21 and update block per frequency in registers
-      pfr::launch_front0(s->P, s->d_f0_front, r, s->d_f0_ptr, s->d_f0_nz, ngroups, s->F, s->Fc, op, s->flags, st);
+      pfr::launch_front0(s->P, v.d_f0_front, r, v.d_f0_ptr, v.d_f0_nz, ngroups, s->F, s->Fc, op, s->flags, st);
       for (int c = 1; c <= 5; ++c) mark(l, c);
       continue;
     }
-    pfr::launch_assemble(mode, s->d_asm + s->asm_ptr[l], r.nasm, s->d_asm_xp + s->asm_ptr[l] / 8, s->d_asm_x, ngroups,
+    pfr::launch_assemble(mode, v.d_asm + v.asm_ptr[l], r.nasm, v.d_asm_xp + v.asm_ptr[l] / 8, v.d_asm_x, ngroups,
                          s->F, s->Fc, op, data, ds, nvalid, st);
     mark(l, 1);
     if (r.lds)
@@ -399,16 +435,16 @@ int factor_all(pfr_solver* s, const pfr::ChunkOp& op, int mode, const double2* d
     else
       pfr::launch_factor(s->sym, s->P, lvl, r, ngroups, s->F, s->Fc, s->flags, st);
     mark(l, 2);
-    pfr::launch_offdiag(mode, s->P, s->d_items + s->item_ptr[l], r, s->d_orec, s->d_oxp + s->item_ptr[l], s->d_ox,
+    pfr::launch_offdiag(mode, s->P, v.d_items + v.item_ptr[l], r, v.d_orec, v.d_oxp + v.item_ptr[l], v.d_ox,
                         ngroups, s->F, s->Fc, op, data, ds, nvalid, st);
     mark(l, 3);
-    pfr::launch_schur_blk(s->P, s->d_blocks + s->blk_ptr[l], r.nblocks,
-                          s->d_bg1 + (int64_t)s->blk_ptr[l] * 16 * 16, s->d_bgxp + s->blk_ptr[l], s->d_bgx, ngroups, s->F,
+    pfr::launch_schur_blk(s->P, v.d_blocks + v.blk_ptr[l], r.nblocks,
+                          v.d_bg1 + (int64_t)v.blk_ptr[l] * 16 * 16, v.d_bgxp + v.blk_ptr[l], v.d_bgx, ngroups, s->F,
                           s->Fc, st);
     mark(l, 4);
-    pfr::launch_schur(s->sym, s->P, s->d_tiles + s->tile_ptr[l], r.ntiles,
-                      s->d_g1 + (int64_t)s->tile_ptr[l] * pfr::SCHUR_TM * pfr::SCHUR_TN * pfr::SCHUR_SR * pfr::SCHUR_SC,
-                      s->d_gxp + s->tile_ptr[l], s->d_gx, ngroups, s->F, s->Fc, st);
+    pfr::launch_schur(s->sym, s->P, v.d_tiles + v.tile_ptr[l], r.ntiles,
+                      v.d_g1 + (int64_t)v.tile_ptr[l] * pfr::SCHUR_TM * pfr::SCHUR_TN * pfr::SCHUR_SR * pfr::SCHUR_SC,
+                      v.d_gxp + v.tile_ptr[l], v.d_gx, ngroups, s->F, s->Fc, st);
     mark(l, 5);
   }
   LAUNCH_TRY();
@@ -418,18 +454,18 @@ int factor_all(pfr_solver* s, const pfr::ChunkOp& op, int mode, const double2* d
 // which: 0 L, 1 U, 2 U^T, 3 L^T ; bottom-up for 0/2, top-down for 1/3
 // subset (0 forward rhs, 1 loss adjoint, -1 none): bottom-up passes visit only the reached
 // fronts; top-down passes treat the pivot values of unreached fronts as zero
-int solve_all(pfr_solver* s, const pfr::ChunkOp& op, int which, int rhs_mode, const pfr::RhsArgs& rd, const double2* Yin,
-              double2* Out, hipStream_t st, int subset = -1, const int* glist = nullptr) {
+int solve_all(pfr_solver* s, const SolverView& v, const pfr::ChunkOp& op, int which, int rhs_mode, const pfr::RhsArgs& rd,
+              const double2* Yin, double2* Out, hipStream_t st, int subset = -1, const int* glist = nullptr) {
   const int L = (int)s->level_ptr.size() - 1;
   const int ngroups = glist ? pfr::REFINE_CAP : (int)(s->Fc / 64);
   const bool up = (which == 0 || which == 2);
-  const int* reach = subset >= 0 ? s->d_reach[subset] : nullptr;
+  const int* reach = subset >= 0 ? v.d_reach[subset] : nullptr;
   for (int t = 0; t < L; ++t) {
     int l = up ? t : L - 1 - t;
     // bottom-up over the subset's fronts only, top-down over the whole level
     const bool part = up && subset >= 0;
-    const int32_t* lvl = part ? s->d_reach_fronts[subset] + s->reach_ptr[subset][l] : s->d_level_fronts + s->level_ptr[l];
-    const pfr::SolveLevel& r = s->sched.solve[part ? pfr::SUBSET_REACH0 + subset : pfr::SUBSET_ALL][l];
+    const int32_t* lvl = part ? v.d_reach_fronts[subset] + v.reach_ptr[subset][l] : v.d_level_fronts + v.level_ptr[l];
+    const pfr::SolveLevel& r = v.sched.solve[part ? pfr::SUBSET_REACH0 + subset : pfr::SUBSET_ALL][l];
     pfr::launch_solve(which, rhs_mode, s->sym, s->P, lvl, r, ngroups, s->F, s->Fc, s->WV, rd, op.pop, Yin, Out, reach, st,
                       glist);
   }
@@ -450,12 +486,20 @@ pfr::DirArgs dir_desc(const pfr_solver* s, const pfr::ChunkOp& op) {
   d.freqs = op.freqs;
   return d;
 }
+// the adjoint's Dirichlet rows (k_dirichlet_post) over the nodes on the view's fronts
+pfr::DirArgs post_desc(const pfr_solver* s, const SolverView& v, const pfr::ChunkOp& op) {
+  pfr::DirArgs d = dir_desc(s, op);
+  d.dir = v.post_dir;
+  d.dptr = v.post_dptr;
+  d.de = v.post_de;
+  return d;
+}
 
 // A x = b on the chunk's factors, x -> Out (permuted).  rhs_mode 0: operator right-hand side
 // (rd.rhsP ...); 2: vector rd.G (overwritten in symmetric mode).  Symmetric mode: Dirichlet
 // columns moved to the right-hand side first, then L and U = diag(U) L^T.
-int forward_solve(pfr_solver* s, const pfr::ChunkOp& op, int rhs_mode, pfr::RhsArgs rd, double2* Out, hipStream_t st,
-                  int subset = -1) {
+int forward_solve(pfr_solver* s, const SolverView& v, const pfr::ChunkOp& op, int rhs_mode, pfr::RhsArgs rd, double2* Out,
+                  hipStream_t st, int subset = -1) {
   int rc;
   if (s->sym) {
     const pfr::DirArgs dd = dir_desc(s, op);
@@ -468,63 +512,71 @@ int forward_solve(pfr_solver* s, const pfr::ChunkOp& op, int rhs_mode, pfr::RhsA
       pfr::launch_dirichlet_rhs(2, dd, op.pop, s->n_crow, rd, const_cast<double2*>(rd.G), nullptr, s->Fc, st);
     }
   }
-  if ((rc = solve_all(s, op, 0, rhs_mode, rd, nullptr, s->Y, st, subset))) return rc;
-  return solve_all(s, op, 1, 0, rd, s->Y, Out, st, subset);
+  if ((rc = solve_all(s, v, op, 0, rhs_mode, rd, nullptr, s->Y, st, subset))) return rc;
+  return solve_all(s, v, op, 1, 0, rd, s->Y, Out, st, subset);
 }
 
 // A^T l = g (g = rg.G, permuted), l -> Out.  Symmetric mode: the decoupled matrix is symmetric,
 // so L and U = diag(U) L^T again, then the Dirichlet rows of l are corrected.
-int adjoint_solve(pfr_solver* s, const pfr::ChunkOp& op, const pfr::RhsArgs& rg, double2* Out, hipStream_t st,
-                  int subset = -1, const int* glist = nullptr) {
+int adjoint_solve(pfr_solver* s, const SolverView& v, const pfr::ChunkOp& op, const pfr::RhsArgs& rg, double2* Out,
+                  hipStream_t st, int subset = -1, const int* glist = nullptr) {
   int rc;
   if (s->sym) {
-    if ((rc = solve_all(s, op, 0, 2, rg, nullptr, s->Y, st, subset, glist)) ||
-        (rc = solve_all(s, op, 1, 0, rg, s->Y, Out, st, subset, glist)))
+    if ((rc = solve_all(s, v, op, 0, 2, rg, nullptr, s->Y, st, subset, glist)) ||
+        (rc = solve_all(s, v, op, 1, 0, rg, s->Y, Out, st, subset, glist)))
       return rc;
-    pfr::launch_dirichlet_post(dir_desc(s, op), op.pop, s->n_dir, Out, s->Fc, st, glist);
+    pfr::launch_dirichlet_post(post_desc(s, v, op), op.pop, v.post_n, Out, s->Fc, st, glist);
     return PFR_OK;
   }
-  if ((rc = solve_all(s, op, 2, 2, rg, nullptr, s->Y, st, subset))) return rc;
-  return solve_all(s, op, 3, 0, rg, s->Y, Out, st, subset);
+  if ((rc = solve_all(s, v, op, 2, 2, rg, nullptr, s->Y, st, subset))) return rc;
+  return solve_all(s, v, op, 3, 0, rg, s->Y, Out, st, subset);
 }
 
 // Row lists and buffers of the functional-from-bottom-up path (allocated on first use, lists rebuilt
 // whenever a reach changed)
-int fn_setup(pfr_solver* s) {
+int fn_setup(pfr_solver* s, SolverView& v) {
   int rc;
   const int64_t n = s->n;
   if (!s->WVk) {
     if ((rc = s->alloc(&s->WVk, s->ws.WVk)) || (rc = s->alloc(&s->YVk, s->ws.YVk)) ||
         (rc = s->alloc(&s->fn_parts, s->ws.fn_parts)) || (rc = s->alloc(&s->fcoef, s->ws.fcoef)) ||
-        (rc = s->up(&s->d_noslot, std::vector<int32_t>(n, -1))) || (rc = s->alloc(&s->d_aP, 3 * n)) ||
-        (rc = s->alloc(&s->d_fn_rows, n)) || (rc = s->alloc(&s->d_sup_rows, n)))
+        (rc = s->up(&s->d_noslot, std::vector<int32_t>(n, -1))) || (rc = s->alloc(&s->d_aP, 3 * n)))
       return rc;
     HIP_TRY(hipMemcpy(s->d_aP, s->a_perm.data(), s->a_perm.size() * 8, hipMemcpyHostToDevice));
   }
-  if (s->fn_ready) return PFR_OK;
+  if (!v.d_fn_rows) {
+    if ((rc = s->alloc(&v.d_fn_rows, n)) || (rc = s->alloc(&v.d_sup_rows, n))) return rc;
+    if (&v != s) v.mine.insert(v.mine.end(), {(void*)v.d_fn_rows, (void*)v.d_sup_rows});
+  }
+  if (v.fn_ready) return PFR_OK;
   std::vector<int2> both;
   std::vector<int32_t> sup;
+  // a view keeps the full list's slots (k_fn_dot assigns a slot to a partial and a wave by its position, and the
+  // partials must add the same terms in the same order); the rows it does not reach become skip entries (-1)
   for (size_t t = 0; t < s->front_ns.size(); ++t) {
     if (!s->reach_host[1][t]) continue;
     for (int a = 0; a < s->front_ns[t]; ++a) {
       const int32_t row = s->front_col0[t] + a;
-      sup.push_back(row);
+      if (v.reach_host[1][t]) sup.push_back(row);
       if (s->reach_host[0][t])
-        both.push_back(make_int2(row, s->front_off[t] + a * s->front_f[t] + a));
+        both.push_back(v.reach_host[1][t] && v.reach_host[0][t]
+                           ? make_int2(row, s->front_off[t] + a * s->front_f[t] + a)
+                           : make_int2(-1, -1));
     }
   }
-  s->n_fn_rows = (int)both.size();
-  s->n_sup_rows = (int)sup.size();
+  v.n_fn_rows = (int)both.size();
+  v.n_sup_rows = (int)sup.size();
   // at most n rows each (pivot rows are distinct): into the buffers allocated for n
-  if (!both.empty()) HIP_TRY(hipMemcpy(s->d_fn_rows, both.data(), both.size() * sizeof(int2), hipMemcpyHostToDevice));
-  if (!sup.empty()) HIP_TRY(hipMemcpy(s->d_sup_rows, sup.data(), sup.size() * 4, hipMemcpyHostToDevice));
-  s->fn_ready = true;
+  if (!both.empty()) HIP_TRY(hipMemcpy(v.d_fn_rows, both.data(), both.size() * sizeof(int2), hipMemcpyHostToDevice));
+  if (!sup.empty()) HIP_TRY(hipMemcpy(v.d_sup_rows, sup.data(), sup.size() * 4, hipMemcpyHostToDevice));
+  v.fn_ready = true;
   return PFR_OK;
 }
 
 // forward bottom-up over the rhs reach (slice 0) and L w_k = a_k over the support reach (slices 1-3),
 // one launch chain
-int fn_bottom_up(pfr_solver* s, const pfr::ChunkOp& op, int rhs_mode, const pfr::RhsArgs& rf, hipStream_t st) {
+int fn_bottom_up(pfr_solver* s, const SolverView& v, const pfr::ChunkOp& op, int rhs_mode, const pfr::RhsArgs& rf,
+                 hipStream_t st) {
   const int L = (int)s->level_ptr.size() - 1;
   const int ngroups = (int)(s->Fc / 64);
   int64_t total_rows = 0;
@@ -532,7 +584,7 @@ int fn_bottom_up(pfr_solver* s, const pfr::ChunkOp& op, int rhs_mode, const pfr:
   pfr::RhsArgs rd[4] = {rf, rf, rf, rf};
   double2* WV[4] = {s->WV, s->WVk, s->WVk + total_rows * s->Fc, s->WVk + 2 * total_rows * s->Fc};
   double2* Y[4] = {s->Y, s->Y2, s->YVk, s->YVk + (int64_t)s->n * s->Fc};
-  const int* reach[4] = {s->d_reach[0], s->d_reach[1], s->d_reach[1], s->d_reach[1]};
+  const int* reach[4] = {v.d_reach[0], v.d_reach[1], v.d_reach[1], v.d_reach[1]};
   for (int k = 1; k < 4; ++k) {
     rd[k].rhsP = s->d_aP + (int64_t)(k - 1) * s->n;
     rd[k].mass_sum = 0.0;
@@ -541,9 +593,9 @@ int fn_bottom_up(pfr_solver* s, const pfr::ChunkOp& op, int rhs_mode, const pfr:
     rd[k].cslot = s->d_noslot;
   }
   for (int l = 0; l < L; ++l) {
-    const int32_t* sup = s->d_reach_fronts[1] + s->reach_ptr[1][l];
-    const int* lvl[4] = {s->d_reach_fronts[0] + s->reach_ptr[0][l], sup, sup, sup};
-    pfr::launch_lsolve_multi(rhs_mode, s->P, 4, lvl, s->sched.chain[l], ngroups, s->F, s->Fc, WV, rd, op.pop, Y, reach, st);
+    const int32_t* sup = v.d_reach_fronts[1] + v.reach_ptr[1][l];
+    const int* lvl[4] = {v.d_reach_fronts[0] + v.reach_ptr[0][l], sup, sup, sup};
+    pfr::launch_lsolve_multi(rhs_mode, s->P, 4, lvl, v.sched.chain[l], ngroups, s->F, s->Fc, WV, rd, op.pop, Y, reach, st);
   }
   LAUNCH_TRY();
   return PFR_OK;
@@ -553,23 +605,23 @@ int fn_bottom_up(pfr_solver* s, const pfr::ChunkOp& op, int rhs_mode, const pfr:
 // support reaches only (they hold every support row), then -- once the loss cotangent is known
 // and its bottom-up pass (same fronts) done -- ONE top-down pass computes the adjoint on every
 // front and the forward solution on the rest, each factor value loaded once for both.
-int sym_top_down_support(pfr_solver* s, hipStream_t st) {
+int sym_top_down_support(pfr_solver* s, const SolverView& v, hipStream_t st) {
   const int L = (int)s->level_ptr.size() - 1;
   const int ngroups = (int)(s->Fc / 64);
   for (int l = L - 1; l >= 0; --l) {
-    pfr::launch_solve(1, 0, true, s->P, s->d_reach_fronts[1] + s->reach_ptr[1][l], s->sched.solve[pfr::SUBSET_REACH1][l],
-                      ngroups, s->F, s->Fc, s->WV, pfr::RhsArgs(), pfr::PopArgs(), s->Y, s->X, s->d_reach[0], st);
+    pfr::launch_solve(1, 0, true, s->P, v.d_reach_fronts[1] + v.reach_ptr[1][l], v.sched.solve[pfr::SUBSET_REACH1][l],
+                      ngroups, s->F, s->Fc, s->WV, pfr::RhsArgs(), pfr::PopArgs(), s->Y, s->X, v.d_reach[0], st);
   }
   LAUNCH_TRY();
   return PFR_OK;
 }
 
-int sym_top_down_pair(pfr_solver* s, hipStream_t st, bool fwd_all = false) {
+int sym_top_down_pair(pfr_solver* s, const SolverView& v, hipStream_t st, bool fwd_all = false) {
   const int L = (int)s->level_ptr.size() - 1;
   const int ngroups = (int)(s->Fc / 64);
   for (int l = L - 1; l >= 0; --l) {
-    pfr::launch_usolve2(s->P, s->d_level_fronts + s->level_ptr[l], s->sched.pair[l], ngroups, s->F, s->Fc, s->Y, s->X,
-                        s->d_reach[0], fwd_all ? nullptr : s->d_reach[1], s->Y2, s->XA, s->d_reach[1], st);
+    pfr::launch_usolve2(s->P, v.d_level_fronts + v.level_ptr[l], v.sched.pair[l], ngroups, s->F, s->Fc, s->Y, s->X,
+                        v.d_reach[0], fwd_all ? nullptr : v.d_reach[1], s->Y2, s->XA, v.d_reach[1], st);
   }
   LAUNCH_TRY();
   return PFR_OK;
@@ -577,15 +629,18 @@ int sym_top_down_pair(pfr_solver* s, hipStream_t st, bool fwd_all = false) {
 
 // Mark the fronts holding the given permuted rows and all their ancestors; upload the flags and
 // the marked fronts level by level (level_fronts order kept).
-int set_reach(pfr_solver* s, int which, const std::vector<int32_t>& prows) {
+// (a view other than the solver itself takes the rows on its own fronts only)
+int set_reach(pfr_solver* s, SolverView& v, int which, const std::vector<int32_t>& prows) {
   std::vector<int32_t> mark, list;
-  pfr::reach_lists(s->front_of_col, s->front_parent, s->level_ptr, s->level_fronts_host, prows, mark, list,
-                   s->reach_ptr[which]);
-  s->reach_host[which].assign(mark.begin(), mark.end());
-  s->fn_ready = false;
-  pfr::schedule_reach(s->sched, s->reach_ptr);
-  HIP_TRY(hipMemcpy(s->d_reach[which], mark.data(), mark.size() * 4, hipMemcpyHostToDevice));
-  if (!list.empty()) HIP_TRY(hipMemcpy(s->d_reach_fronts[which], list.data(), list.size() * 4, hipMemcpyHostToDevice));
+  pfr::reach_lists(s->front_of_col, s->front_parent, v.level_ptr, v.level_fronts_host, prows, mark, list,
+                   v.reach_ptr[which]);
+  v.reach_host[which].assign(mark.begin(), mark.end());
+  v.fn_ready = false;
+  if (&v == s && s->act) s->act->fn_ready = false;
+  // a view decides its launch shapes for the full reaches (set before the view's): plan.hpp, level_schedule
+  pfr::schedule_reach(v.sched, v.reach_ptr, &v != s ? &s->reach_ptr : nullptr);
+  HIP_TRY(hipMemcpy(v.d_reach[which], mark.data(), mark.size() * 4, hipMemcpyHostToDevice));
+  if (!list.empty()) HIP_TRY(hipMemcpy(v.d_reach_fronts[which], list.data(), list.size() * 4, hipMemcpyHostToDevice));
   return PFR_OK;
 }
 
@@ -594,7 +649,7 @@ int set_reach(pfr_solver* s, int which, const std::vector<int32_t>& prows) {
 // (data, ds, nvalid); rhs as launch_residual (0 operator, 1 explicit B, 2 vector G).  Sets the
 // chunk's flags and the caller's berr slots (q0 < 0: no berr output).  R != NULL: only the residual
 // b - A x is written there (the refinement step), nothing is checked.
-void check_solution(pfr_solver* s, const pfr::ChunkOp& op, int which, int mode, int rhs, const pfr::RhsArgs& rd,
+void check_solution(pfr_solver* s, const SolverView& v, const pfr::ChunkOp& op, int which, int mode, int rhs, const pfr::RhsArgs& rd,
                     const double2* data, int64_t ds, int nvalid, const double2* X, double2* R, int64_t q0, hipStream_t st,
                     const double2* Mu = nullptr, bool check = true, bool contract = false, const int* glist = nullptr) {
   pfr::ResidArgs d;
@@ -616,7 +671,7 @@ void check_solution(pfr_solver* s, const pfr::ChunkOp& op, int which, int mode, 
   d.b_stride = rd.b_stride;
   d.perm = s->P.perm;
   d.G = rd.G;
-  d.walk = s->d_walk;
+  d.walk = v.d_walk;
   d.glist = glist;
   if (contract) {   // the gradient contraction fused into the forward walk: stiffness values nz-major, kpart out
     d.se = s->stiff;
@@ -641,6 +696,124 @@ void check_solution(pfr_solver* s, const pfr::ChunkOp& op, int which, int mode, 
 // (k_contract_eg, the loss sweep's contraction; no checks)
 void contract_rows(pfr_solver* s, const double2* lam, const double2* x, int nv, hipStream_t st) {
   pfr::launch_contract_eg(s->d_uent, s->n_uent, s->d_se, s->n_stiff, lam, x, s->Fc, nv, s->partial, st);
+}
+
+// The device side of a view: the plan's level lists and factor-class records, the walk list (rows of other fronts
+// -1), the reach arrays, and the schedule with no front reached yet.  v == *s: the solver's own (full) view.
+int upload_view(pfr_solver* s, SolverView& v, const Symbolic& S, const pfr::Plan& pl, const pfr::Knobs& knobs) {
+  int rc;
+  const size_t own0 = s->owned.size();
+  const int nf = (int)S.fronts.size();
+  v.active = pl.active;
+  v.level_ptr = pl.level_ptr;
+  v.level_fronts_host = pl.level_fronts;
+  v.tile_ptr = pl.tile_ptr;
+  v.blk_ptr = pl.blk_ptr;
+  v.asm_ptr = pl.asm_ptr;
+  v.item_ptr = pl.item_ptr;
+  v.lev_bytes = pl.lev_bytes;
+  for (auto& r : v.reach_ptr) r.clear();
+  v.sched = pfr::level_schedule(S, pl, s->Fc, knobs, v.reach_ptr);
+  const pfr::I2 z2{0, 0}, n2{-1, -1};
+  const pfr::I4 z4{0, 0, 0, 0}, n4{-1, -1, -1, -1};
+  std::vector<int32_t> walk(S.iperm);
+  for (int32_t& p : walk)
+    if (!pl.active[s->front_of_col[p]]) p = -1;
+  if ((rc = s->up_rec(&v.d_level_fronts, pl.level_fronts, 0)) || (rc = s->up(&v.d_walk, walk)) ||
+      (rc = s->up_rec(&v.d_tiles, pl.tiles, z4)) || (rc = s->up_rec(&v.d_g1, pl.g1, -1)) || (rc = s->up(&v.d_gxp, pl.gxp)) ||
+      (rc = s->up_rec(&v.d_gx, pl.gx, z2)) || (rc = s->up_rec(&v.d_blocks, pl.blocks, z4)) ||
+      (rc = s->up_rec(&v.d_bg1, pl.bg1, -1)) || (rc = s->up(&v.d_bgxp, pl.bgxp)) || (rc = s->up_rec(&v.d_bgx, pl.bgx, z2)) ||
+      (rc = s->up_rec(&v.d_asm, pl.asm_rec, n4)) || (rc = s->up(&v.d_asm_xp, pl.asm_xp)) ||
+      (rc = s->up_rec(&v.d_asm_x, pl.asm_x, z2)) || (rc = s->up_rec(&v.d_items, pl.items, z4)) ||
+      (rc = s->up_rec(&v.d_orec, pl.orec, n2)) || (rc = s->up(&v.d_oxp, pl.oxp)) || (rc = s->up_rec(&v.d_ox, pl.ox, z2)))
+    return rc;
+  if (v.sched.factor[0].fused0 && ((rc = s->up(&v.d_f0_front, pl.f0_front)) || (rc = s->up(&v.d_f0_ptr, pl.f0_ptr)) ||
+                                   (rc = s->up(&v.d_f0_nz, pl.f0_nz))))
+    return rc;
+  for (int w = 0; w < 2; ++w) {
+    if ((rc = s->alloc(&v.d_reach[w], nf)) || (rc = s->alloc(&v.d_reach_fronts[w], nf))) return rc;
+    if ((rc = set_reach(s, v, w, {}))) return rc;
+  }
+  if (&v != s) v.mine.assign(s->owned.begin() + own0, s->owned.end());
+  return PFR_OK;
+}
+
+void release_view(pfr_solver* s, SolverView*& v) {
+  if (!v) return;
+  (void)hipDeviceSynchronize();   // launches that read the view's arrays
+  for (void* p : v->mine) {
+    s->owned.erase(std::remove(s->owned.begin(), s->owned.end(), p), s->owned.end());
+    (void)hipFree(p);
+  }
+  delete v;
+  v = nullptr;
+}
+
+// A view of the fronts in `mask` (whole trees): its plan and schedule, the Dirichlet nodes on its fronts, and the
+// solver's current reaches restricted to it (keep0 = false: no forward reach -- the complement carries no load)
+int make_view(pfr_solver* s, const std::vector<char>& mask, bool keep0, SolverView** out) {
+  pfr::Plan pl;
+  std::string perr;
+  if (pfr::build_plan(s->S, s->sched.knobs.blk_min, pl, perr, &mask)) return fail(PFR_ERR_ARG, perr);
+  auto* v = new SolverView();
+  int rc = upload_view(s, *v, s->S, pl, s->sched.knobs);
+  std::vector<pfr::I2> dir, de;
+  std::vector<int32_t> dptr(1, 0);
+  for (size_t d = 0; d < s->h_dir.size() && rc == PFR_OK; ++d) {
+    if (!mask[s->front_of_col[s->h_dir[d].x]]) continue;
+    dir.push_back(s->h_dir[d]);
+    de.insert(de.end(), s->h_de.begin() + s->h_dptr[d], s->h_de.begin() + s->h_dptr[d + 1]);
+    dptr.push_back((int32_t)de.size());
+  }
+  const size_t own0 = s->owned.size();
+  v->post_n = (int)dir.size();
+  if (rc == PFR_OK)
+    (void)((rc = s->up_rec(&v->post_dir, dir, pfr::I2{0, 0})) || (rc = s->up(&v->post_dptr, dptr)) ||
+           (rc = s->up_rec(&v->post_de, de, pfr::I2{0, 0})));
+  v->mine.insert(v->mine.end(), s->owned.begin() + own0, s->owned.end());
+  for (int w = keep0 ? 0 : 1; w < 2 && rc == PFR_OK; ++w) rc = set_reach(s, *v, w, pfr::rows_in(s->S, mask, s->reach_rows[w]));
+  if (rc != PFR_OK) {
+    release_view(s, v);
+    return rc;
+  }
+  *out = v;
+  return PFR_OK;
+}
+
+// The loaded trees' view for the solver's right-hand side vector (pfr_set_prune, pfr_set_rhs): built when pruning
+// is on and some tree carries no load, kept while the set of loaded trees stays the same
+int update_prune(pfr_solver* s) {
+  std::vector<char> mask;
+  bool any_off = false;
+  if (s->prune && s->sym && s->has_rhs) {
+    std::vector<double> rp(s->n);
+    for (int p = 0; p < s->n; ++p) rp[p] = s->rhs_host[s->perm[p]];
+    mask = pfr::loaded_fronts(s->S, rp.data());
+    for (char m : mask) any_off = any_off || !m;
+  }
+  if (s->act && any_off && s->act->active == mask) return PFR_OK;
+  ++s->gen;
+  release_view(s, s->act);
+  release_view(s, s->comp);
+  s->unl_rows.clear();
+  s->comp_done = false;
+  if (!any_off) return PFR_OK;
+  for (size_t t = 0; t < mask.size(); ++t) {
+    if (mask[t]) continue;
+    const int32_t a = s->front_col0[t], b = a + s->front_ns[t];
+    s->unl_rows.emplace_back(a, b);
+  }
+  std::sort(s->unl_rows.begin(), s->unl_rows.end());
+  size_t k = 0;
+  for (size_t i = 1; i < s->unl_rows.size(); ++i) {
+    if (s->unl_rows[i].first == s->unl_rows[k].second)
+      s->unl_rows[k].second = s->unl_rows[i].second;
+    else
+      s->unl_rows[++k] = s->unl_rows[i];
+  }
+  if (!s->unl_rows.empty()) s->unl_rows.resize(k + 1);
+  s->unl_dirty = true;   // the rows of the unloaded trees in X / XA: exact zeros from the first pruned sweep on
+  return make_view(s, mask, true, &s->act);
 }
 
 }  // namespace
@@ -806,13 +979,6 @@ int pfr_solver_create(const pfr_symbolic* sym, const int32_t* colptr, const int3
   std::string perr;
   if (pfr::build_plan(S, knobs.blk_min, pl, perr)) return bail(fail(PFR_ERR_ARG, perr));
   s->sym = pl.sym;
-  s->tile_ptr = pl.tile_ptr;
-  s->blk_ptr = pl.blk_ptr;
-  s->asm_ptr = pl.asm_ptr;
-  s->item_ptr = pl.item_ptr;
-  s->lev_bytes = pl.lev_bytes;
-  s->sched = pfr::level_schedule(S, pl, s->Fc, knobs, s->reach_ptr);
-  const bool fused0 = s->sched.factor[0].fused0;
   Front* d_fronts = nullptr;
   int rc = PFR_OK;
   std::vector<Front> fv(S.fronts);
@@ -821,20 +987,10 @@ int pfr_solver_create(const pfr_symbolic* sym, const int32_t* colptr, const int3
   if ((rc = s->up(&idx, S.idx)) || (rc = s->up(&relpos, S.relpos)) || (rc = s->up(&rowf, S.row_front)) ||
       (rc = s->up(&ap, S.asm_ptr)) || (rc = s->up(&ac, S.asm_col)) || (rc = s->up(&an, S.asm_nz)) ||
       (rc = s->up(&ep, S.ea_ptr)) || (rc = s->up(&es, S.ea_src)) || (rc = s->up(&pm, S.perm)) ||
-      (rc = s->up(&pr, S.prow)) || (rc = s->up(&pc, S.pcol)) || (rc = s->up(&s->d_level_fronts, S.level_fronts)))
+      (rc = s->up(&pr, S.prow)) || (rc = s->up(&pc, S.pcol)))
     return bail(rc);
-  const pfr::I2 z2{0, 0}, n2{-1, -1};
-  const pfr::I4 z4{0, 0, 0, 0}, n4{-1, -1, -1, -1};
-  if ((rc = s->up_rec(&s->d_tiles, pl.tiles, z4)) || (rc = s->up(&s->d_g1, pl.g1)) || (rc = s->up(&s->d_gxp, pl.gxp)) ||
-      (rc = s->up_rec(&s->d_gx, pl.gx, z2)) || (rc = s->up_rec(&s->d_blocks, pl.blocks, z4)) ||
-      (rc = s->up_rec(&s->d_bg1, pl.bg1, -1)) || (rc = s->up(&s->d_bgxp, pl.bgxp)) || (rc = s->up_rec(&s->d_bgx, pl.bgx, z2)) ||
-      (rc = s->up_rec(&s->d_asm, pl.asm_rec, n4)) || (rc = s->up(&s->d_asm_xp, pl.asm_xp)) ||
-      (rc = s->up_rec(&s->d_asm_x, pl.asm_x, z2)) || (rc = s->up_rec(&s->d_items, pl.items, z4)) ||
-      (rc = s->up_rec(&s->d_orec, pl.orec, n2)) || (rc = s->up(&s->d_oxp, pl.oxp)) || (rc = s->up_rec(&s->d_ox, pl.ox, z2)))
-    return bail(rc);
-  if (fused0 && ((rc = s->up(&s->d_f0_front, pl.f0_front)) || (rc = s->up(&s->d_f0_ptr, pl.f0_ptr)) ||
-                    (rc = s->up(&s->d_f0_nz, pl.f0_nz))))
-    return bail(rc);
+  const pfr::I2 z2{0, 0};
+  const pfr::I4 n4{-1, -1, -1, -1};
   std::vector<int32_t> cp(colptr, colptr + S.n + 1), ri(rowind, rowind + S.nnz);
   if ((rc = s->up(&s->d_colptr, cp)) || (rc = s->up(&s->d_rowind, ri))) return bail(rc);
   if (s->sym && !S.dir_p.empty()) {
@@ -848,7 +1004,7 @@ int pfr_solver_create(const pfr_symbolic* sym, const int32_t* colptr, const int3
   }
   if ((rc = s->up(&s->d_rptr, pl.rptr)) || (rc = s->up(&s->d_ridx, pl.ridx)) || (rc = s->up(&s->d_rnz, pl.rnz)) ||
       (rc = s->up(&s->d_cptr, pl.cptr)) || (rc = s->up(&s->d_cidx, pl.cidx)) || (rc = s->up(&s->d_cnz, pl.cnz)) ||
-      (rc = s->up(&s->d_walk, S.iperm)) || (rc = s->up_rec(&s->d_uent, pl.uent, n4)))
+      (rc = s->up_rec(&s->d_uent, pl.uent, n4)))
     return bail(rc);
   s->n_uent = pl.n_uent;
   s->P = DevPattern{d_fronts, idx, relpos, rowf, ap, ac, an, ep, es, pm, pr, pc, S.n};
@@ -865,11 +1021,18 @@ int pfr_solver_create(const pfr_symbolic* sym, const int32_t* colptr, const int3
       s->front_col0.push_back(F.col0);
       for (int a = 0; a < F.ns; ++a) s->front_of_col[F.col0 + a] = t;
     }
-    s->level_fronts_host = S.level_fronts;
-    for (int w = 0; w < 2; ++w) {
-      if ((rc = s->alloc(&s->d_reach[w], nf)) || (rc = s->alloc(&s->d_reach_fronts[w], nf))) return bail(rc);
-      if ((rc = set_reach(s, w, {}))) return bail(rc);
-    }
+  }
+  // the full view: every front (no front reached yet: set_reach)
+  if ((rc = upload_view(s, *s, S, pl, knobs))) return bail(rc);
+  s->post_n = s->n_dir;
+  s->post_dir = s->d_dir;
+  s->post_dptr = s->d_dptr;
+  s->post_de = s->d_de;
+  if (s->sym) {   // what a pruned view is built from (pfr_set_prune)
+    s->S = S;
+    s->h_dir = pl.dir;
+    s->h_dptr = pl.dptr;
+    s->h_de = pl.de;
   }
   const int64_t Fc = s->Fc;
   s->ws = pfr::workspace(S, Fc, s->n_crow);
@@ -929,9 +1092,86 @@ int pfr_symbolic_schedule(const pfr_symbolic* sym, int32_t max_batch, int32_t* d
   return schedule_out(pfr::level_schedule(sym->S, pl, Fc, knobs, all), dst, cap);
 }
 
+int pfr_symbolic_prune(const pfr_symbolic* sym, int32_t max_batch, const double* rhs, int32_t n_support,
+                       const int32_t* index, int32_t* mask_out, int32_t* sched_active, int32_t* sched_rest,
+                       int32_t* sched_full, int64_t cap) {
+  if (!sym || max_batch <= 0 || !rhs || n_support < 0 || (n_support > 0 && !index) || !mask_out)
+    return fail(PFR_ERR_ARG, "bad arguments");
+  const Symbolic& S = sym->S;
+  const int64_t Fc = round64(max_batch);
+  const pfr::Knobs knobs = pfr::knobs_from_env(Fc);
+  std::vector<double> rp(S.n);
+  for (int p = 0; p < S.n; ++p) rp[p] = rhs[S.perm[p]];
+  std::vector<char> mask = pfr::loaded_fronts(S, rp.data());
+  for (size_t t = 0; t < mask.size(); ++t) mask_out[t] = mask[t];
+  // the reaches a solver sets (pfr_set_rhs, pfr_set_functional): the vector's support and every coupled row; the
+  // functional's support
+  std::vector<int32_t> rows[2], front_of_col(S.n, -1), front_parent;
+  for (const Front& F : S.fronts) {
+    for (int a = 0; a < F.ns; ++a) front_of_col[F.col0 + a] = (int32_t)front_parent.size();
+    front_parent.push_back(F.parent);
+  }
+  for (int p = 0; p < S.n; ++p)
+    if (rp[p] != 0.0) rows[0].push_back(p);
+  for (size_t c = 0; c < S.cpl_p.size(); ++c)
+    if (c == 0 || S.cpl_p[c] != S.cpl_p[c - 1]) rows[0].push_back(S.cpl_p[c]);
+  for (int i = 0; i < n_support; ++i) {
+    if (index[i] < 0 || index[i] >= S.n) return fail(PFR_ERR_ARG, "functional index out of range");
+    rows[1].push_back(S.iperm[index[i]]);
+  }
+  std::vector<int32_t> full_ptr[2], mark, list;
+  for (int w = 0; w < 2; ++w)
+    pfr::reach_lists(front_of_col, front_parent, S.level_ptr, S.level_fronts, rows[w], mark, list, full_ptr[w]);
+  for (int side = 0; side < 3; ++side) {   // the loaded trees, the rest (no forward reach there), every front
+    int32_t* dst = side == 0 ? sched_active : side == 1 ? sched_rest : sched_full;
+    if (side == 1)
+      for (char& m : mask) m = !m;
+    if (side == 2) mask.assign(mask.size(), 1);
+    pfr::Plan pl;
+    std::string perr;
+    if (pfr::build_plan(S, knobs.blk_min, pl, perr, &mask)) return fail(PFR_ERR_ARG, perr);
+    std::vector<int32_t> reach_ptr[2];
+    for (int w = side == 1 ? 1 : 0; w < 2; ++w)
+      pfr::reach_lists(front_of_col, front_parent, pl.level_ptr, pl.level_fronts, pfr::rows_in(S, mask, rows[w]), mark, list,
+                       reach_ptr[w]);
+    const pfr::Schedule sc = pfr::level_schedule(S, pl, Fc, knobs, reach_ptr, &full_ptr);
+    std::string bad = pfr::check_plan(S, pl, Fc);
+    if (bad.empty()) bad = pfr::check_schedule(S, pl, sc);
+    if (!bad.empty())
+      return fail(PFR_ERR_STATE, std::string(side == 0 ? "loaded view: " : side == 1 ? "unloaded view: " : "full plan: ") + bad);
+    if (dst)
+      if (int rc = schedule_out(sc, dst, cap)) return rc;
+  }
+  return PFR_OK;
+}
+
 int pfr_solver_schedule(const pfr_solver* s, int32_t* dst, int64_t cap) {
   if (!s) return fail(PFR_ERR_ARG, "null solver");
   return schedule_out(s->sched, dst, cap);
+}
+
+int pfr_set_prune(pfr_solver* s, int32_t on) {
+  if (!s) return fail(PFR_ERR_ARG, "null solver");
+  HIP_TRY(hipSetDevice(s->device));
+  s->prune = on != 0;
+  return update_prune(s);
+}
+
+int32_t pfr_solver_active(const pfr_solver* s, int32_t* mask, int64_t cap) {
+  if (!s) return -1;
+  const int64_t nf = (int64_t)s->front_ns.size();
+  int32_t count = 0;
+  for (int64_t t = 0; t < nf; ++t) {
+    const int32_t a = s->act ? s->act->active[t] != 0 : 1;
+    count += a;
+    if (mask && t < cap) mask[t] = a;
+  }
+  return s->act ? count : (int32_t)nf;
+}
+
+int pfr_solver_schedule_active(const pfr_solver* s, int32_t* dst, int64_t cap) {
+  if (!s) return fail(PFR_ERR_ARG, "null solver");
+  return schedule_out(s->act ? s->act->sched : s->sched, dst, cap);
 }
 
 int pfr_set_timing(pfr_solver* s, int32_t enable) {
@@ -941,9 +1181,34 @@ int pfr_set_timing(pfr_solver* s, int32_t enable) {
   return PFR_OK;
 }
 
+namespace {
+// The last chunk's adjoint on the unloaded trees, which a pruned sweep leaves zero (nothing it returns reads it): those
+// fronts factorised from the retained chunk operator and the adjoint solved on them for the seed the sweep left in G
+// (the same per-frequency coefficients), once per chunk.  The loaded rows keep what the sweep computed.
+int complete_adjoint(pfr_solver* s) {
+  if (!s->act || !s->last_pruned || !s->last_adj || s->comp_done) return PFR_OK;
+  int rc;
+  if (!s->comp) {
+    std::vector<char> mask(s->act->active);
+    for (char& m : mask) m = !m;
+    if ((rc = make_view(s, mask, false, &s->comp))) return rc;
+  }
+  const int timing = s->timing;
+  s->timing = 0;
+  rc = factor_all(s, *s->comp, s->last_op, 0, nullptr, 0, (int)s->Fc, s->last_st);
+  if (rc == PFR_OK) rc = adjoint_solve(s, *s->comp, s->last_op, rhs_vector(s->G), s->XA, s->last_st, 1);
+  s->timing = timing;
+  s->comp_done = true;
+  s->unl_dirty = true;
+  return rc;
+}
+}  // namespace
+
 int pfr_debug_solution(pfr_solver* s, int32_t which, int32_t q, double* out) {
   if (!s || !out || which < 0 || which > 1 || q < 0 || q >= s->Fc) return fail(PFR_ERR_ARG, "bad debug arguments");
   HIP_TRY(hipSetDevice(s->device));
+  if (which == 1)
+    if (int rc = complete_adjoint(s)) return rc;
   HIP_TRY(hipDeviceSynchronize());
   std::vector<double2> col((size_t)s->n);
   const double2* src = which == 0 ? s->X : s->XA;
@@ -997,7 +1262,8 @@ int pfr_last_kernel_timings(const pfr_solver* s, double* ms, int64_t* launches) 
   for (int c = 0; c < s->n_tev; ++c) {
     if (!s->tev[c].used[0]) continue;
     for (int l = 0; l < L; ++l) {
-      const pfr::FactorLevel& r = s->sched.factor[l];
+      // the records the last call's level loops launched: the loaded trees' under pruning
+      const pfr::FactorLevel& r = (s->last_pruned && s->act ? s->act->sched : s->sched).factor[l];
       int work[pfr::NKC] = {r.nasm, r.nf, r.nitems, r.nblocks, r.ntiles};
       if (l == 0 && s->tev[c].f0) {   // the fused bottom level: one or two k_front0 launches, all in class 0
         work[0] = (r.f0_small > 0) + (r.nf > r.f0_small);
@@ -1017,8 +1283,12 @@ int pfr_last_kernel_timings(const pfr_solver* s, double* ms, int64_t* launches) 
 int pfr_solver_alg_bytes(const pfr_solver* s, int64_t* bytes) {
   if (!s || !bytes) return fail(PFR_ERR_ARG, "null argument");
   for (int i = 0; i < pfr::NKC; ++i) bytes[i] = 0;
+  // what the operator-form sweeps launch under the current check mode (the refinement modes keep the full plan)
+  const SolverView& v = s->act && !(s->check_mode & (PFR_CHECK_REFINE | PFR_CHECK_REFINE_ADJ))
+                            ? *s->act
+                            : static_cast<const SolverView&>(*s);
   for (int l = 0; l + 1 < (int)s->level_ptr.size(); ++l)
-    for (int i = 0; i < pfr::NKC; ++i) bytes[i] += s->lev_bytes[l][i];
+    for (int i = 0; i < pfr::NKC; ++i) bytes[i] += v.lev_bytes[l][i];
   return PFR_OK;
 }
 
@@ -1027,22 +1297,29 @@ int pfr_solver_solve_bytes(const pfr_solver* s, int64_t* bytes) {
   // factor entries each pass reads once: lower[w] = L11 + L21 of the fronts reach w holds (the
   // bottom-up pass of rhs w), upper_r[w] = U11 + U12 of those fronts, upper / lower_all = every front
   int64_t lower[2] = {0, 0}, upper_r[2] = {0, 0}, upper = 0, lower_all = 0, lower_union = 0, sup_rows = 0;
+  const bool refine = (s->check_mode & PFR_CHECK_REFINE) != 0;
+  // the fronts the sweeps walk: the loaded trees under pruning (the refinement modes keep the full view)
+  const SolverView& v = s->act && !(s->check_mode & (PFR_CHECK_REFINE | PFR_CHECK_REFINE_ADJ))
+                            ? *s->act
+                            : static_cast<const SolverView&>(*s);
+  int64_t nrows = 0;
   for (size_t t = 0; t < s->front_ns.size(); ++t) {
+    if (!v.active[t]) continue;
     const int64_t ns = s->front_ns[t], r = s->front_f[t] - ns;
+    nrows += ns;
     const int64_t u = ns * (ns + 1) / 2 + r * ns;             // U11 + U12 (symmetric: diag(U) L^T)
     const int64_t l = ns * (ns - 1) / 2 + r * ns;             // L11 (unit diagonal) + L21
     upper += u;
     lower_all += l;
-    if (s->reach_host[0][t] || s->reach_host[1][t]) lower_union += l;
-    if (s->reach_host[1][t]) sup_rows += ns;
+    if (v.reach_host[0][t] || v.reach_host[1][t]) lower_union += l;
+    if (v.reach_host[1][t]) sup_rows += ns;
     for (int w = 0; w < 2; ++w)
-      if (s->reach_host[w][t]) {
+      if (v.reach_host[w][t]) {
         lower[w] += l;
         upper_r[w] += u;
       }
   }
-  const int64_t vec = 2 * 16 * (int64_t)s->n;                 // rhs in, solution out
-  const bool refine = (s->check_mode & PFR_CHECK_REFINE) != 0;
+  const int64_t vec = 2 * 16 * nrows;                         // rhs in, solution out
   if (s->sym && !refine && s->fn_dot) {
     // loss sweep, functional from the bottom-up passes: ONE bottom-up chain over the rhs reach and the
     // support reach together (the support's three vectors share each L value of their fronts) + the
@@ -1152,10 +1429,17 @@ int pfr_set_rhs(pfr_solver* s, const double* rhs, double beta_re, double beta_im
       HIP_TRY(hipMemcpy(crow.data(), s->d_crow, s->n_crow * 4, hipMemcpyDeviceToHost));
       rows.insert(rows.end(), crow.begin(), crow.begin() + s->n_crow);
     }
-    if ((rc = set_reach(s, 0, rows))) return rc;
+    s->reach_rows[0] = rows;
+    if ((rc = set_reach(s, *s, 0, rows))) return rc;
   }
   s->rhs_host.assign(rhs, rhs + s->n);
   s->has_rhs = true;
+  // the loaded trees follow the vector's support (pfr_set_prune); the same trees: the view's forward reach again
+  const SolverView* before = s->act;
+  if ((rc = update_prune(s))) return rc;
+  if (s->act && s->act == before &&
+      (rc = set_reach(s, *s->act, 0, pfr::rows_in(s->S, s->act->active, s->reach_rows[0]))))
+    return rc;
   return PFR_OK;
 }
 
@@ -1173,7 +1457,11 @@ int pfr_set_functional(pfr_solver* s, int32_t n_support, const int32_t* index, c
   double* d_a;
   int rc;
   if ((rc = s->up(&d_idx, pidx)) || (rc = s->up(&d_a, av))) return rc;
-  if ((rc = set_reach(s, 1, pidx))) return rc;        // loss adjoint reach: functional support
+  s->reach_rows[1] = pidx;
+  if ((rc = set_reach(s, *s, 1, pidx))) return rc;    // loss adjoint reach: functional support
+  // the sensor rows on unloaded trees multiply exact zeros of the forward solution: the pruned view drops them
+  if (s->act && (rc = set_reach(s, *s->act, 1, pfr::rows_in(s->S, s->act->active, pidx)))) return rc;
+  release_view(s, s->comp);
   s->a_perm.assign(3 * (size_t)s->n, 0.0);
   for (int k = 0; k < 3; ++k)
     for (int i = 0; i < n_support; ++i) s->a_perm[(size_t)k * s->n + pidx[i]] += av[(size_t)k * n_support + i];
@@ -1223,8 +1511,24 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
   const bool paired = s->sym && adj && !refine;        // one top-down pass for both solutions
   const bool fwd_late = paired || correct;             // forward residual walk after the adjoint
   const bool fn_fast = paired && s->fn_dot;            // functional from the bottom-up passes
+  // pruning (pfr_set_prune): the loaded trees' view; the refinement modes keep the full one (their corrections solve
+  // right-hand sides that are not the operator's)
+  const bool pruned = s->act && !(s->check_mode & (PFR_CHECK_REFINE | PFR_CHECK_REFINE_ADJ));
+  SolverView& v = pruned ? *s->act : static_cast<SolverView&>(*s);
+  if (pruned && s->unl_dirty) {   // rows of the unloaded trees: exact zeros, written here and by no pruned sweep
+    for (const auto& r : s->unl_rows) {
+      pfr::launch_zero(s->X + (int64_t)r.first * Fc, (int64_t)(r.second - r.first) * Fc, st);
+      pfr::launch_zero(s->XA + (int64_t)r.first * Fc, (int64_t)(r.second - r.first) * Fc, st);
+    }
+    s->unl_dirty = false;
+  } else if (!pruned && s->act) {
+    s->unl_dirty = true;
+  }
+  s->last_pruned = pruned;
+  s->last_adj = adj;
+  s->last_st = st;
   if (fn_fast)
-    if (int rc0 = fn_setup(s)) return rc0;
+    if (int rc0 = fn_setup(s, v)) return rc0;
   if (resp.cpx && correct && !s->h0)
     if (int rc0 = s->alloc(&s->h0, Fc)) return rc0;
   // seed mode of the functional kernels: the response of this solve kept for k_correct_finish
@@ -1240,6 +1544,8 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
     if (int rc0 = begin_chunk(s)) return rc0;
     record(s, 0, st);
     const pfr::ChunkOp op = chunk_op(s, popK, pop, q0);
+    s->last_op = op;
+    s->comp_done = false;
     const pfr::DirArgs dd = dir_desc(s, op);
     const pfr::RhsArgs rd = rhs_operator(op);
     pfr::RhsArgs rf = rd;
@@ -1248,32 +1554,32 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
       pfr::launch_dirichlet_rhs(0, dd, op.pop, s->n_crow, rd, nullptr, s->Bc, s->Fc, st);
       rf.cslot = s->d_cslot;
       rf.Bc = s->Bc;
-      if ((rc = factor_all(s, op, 0, nullptr, 0, nv, st))) return rc;
+      if ((rc = factor_all(s, v, op, 0, nullptr, 0, nv, st))) return rc;
       record(s, 1, st);   // the forward bottom-up pass belongs to the solve phases (sptrsv_roofline)
       if (fn_fast) {
-        if ((rc = fn_bottom_up(s, op, s->n_crow > 0 ? 3 : 0, rf, st))) return rc;
-      } else if ((rc = solve_all(s, op, 0, s->n_crow > 0 ? 3 : 0, rf, nullptr, s->Y, st, 0))) {
+        if ((rc = fn_bottom_up(s, v, op, s->n_crow > 0 ? 3 : 0, rf, st))) return rc;
+      } else if ((rc = solve_all(s, v, op, 0, s->n_crow > 0 ? 3 : 0, rf, nullptr, s->Y, st, 0))) {
         return rc;
       }
     } else {
-      rc = factor_all(s, op, 0, nullptr, 0, nv, st);
+      rc = factor_all(s, v, op, 0, nullptr, 0, nv, st);
       if (rc) return rc;
       record(s, 1, st);
     }
     // symmetric mode with an adjoint: forward top-down only over the loss support's fronts, then one
     // combined top-down pass (sym_top_down_pair); otherwise the full forward solve first
     if (paired) {
-      if (!fn_fast && (rc = sym_top_down_support(s, st))) return rc;
+      if (!fn_fast && (rc = sym_top_down_support(s, v, st))) return rc;
     } else {
-      if ((rc = forward_solve(s, op, 0, rd, s->X, st, 0))) return rc;
+      if ((rc = forward_solve(s, v, op, 0, rd, s->X, st, 0))) return rc;
       if (refine) {
         // one refinement step on the same factors: r = b - A x (into G), A d = r (into XA), x += d
-        check_solution(s, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, s->G, q0, st);
-        if ((rc = forward_solve(s, op, 2, rhs_vector(s->G), s->XA, st))) return rc;
+        check_solution(s, v, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, s->G, q0, st);
+        if ((rc = forward_solve(s, v, op, 2, rhs_vector(s->G), s->XA, st))) return rc;
         pfr::launch_axpy_vec(s->X, s->XA, (int64_t)s->n * Fc, st);
       }
       if (!fwd_late && (s->check_mode & PFR_CHECK_FORWARD))
-        check_solution(s, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st);
+        check_solution(s, v, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st);
     }
     record(s, 2, st);
     pfr::FunctionalArgs fa = s->fn;
@@ -1288,7 +1594,7 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
     if (adj) pfr::launch_zero(s->G, (int64_t)s->n * Fc, st);
     if (fn_fast) {
       const double2* Yk[3] = {s->Y2, s->YVk, s->YVk + (int64_t)s->n * Fc};
-      pfr::launch_fn_dot(s->d_fn_rows, s->n_fn_rows, s->F, s->Y, Yk, Fc, s->fn_parts, st);
+      pfr::launch_fn_dot(v.d_fn_rows, v.n_fn_rows, s->F, s->Y, Yk, Fc, s->fn_parts, st);
       pfr::FunctionalArgs fs = fa;
       if (correct) seed(fs);
       pfr::launch_functional_fn(fs, s->fn_parts, Fc, nv, q0, correct ? nullptr : fr_out, correct ? nullptr : s->loss_terms,
@@ -1305,9 +1611,9 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
       const pfr::RhsArgs rg = rhs_vector(s->G);
       if (fn_fast) {
         double2* Yk[3] = {s->Y2, s->YVk, s->YVk + (int64_t)s->n * Fc};
-        pfr::launch_fn_combine(s->d_sup_rows, s->n_sup_rows, s->fcoef, Yk, Fc, st);
-        if ((rc = sym_top_down_pair(s, st, true))) return rc;
-        pfr::launch_dirichlet_post(dd, op.pop, s->n_dir, s->XA, s->Fc, st);
+        pfr::launch_fn_combine(v.d_sup_rows, v.n_sup_rows, s->fcoef, Yk, Fc, st);
+        if ((rc = sym_top_down_pair(s, v, st, true))) return rc;
+        pfr::launch_dirichlet_post(post_desc(s, v, op), op.pop, v.post_n, s->XA, s->Fc, st);
         if (correct) {
           // the correction fr(x) + Re(mu^T r) needs fr OF the solution x whose residual r is walked (the
           // dot product's fr has its own rounding error, which the correction does not see): fr0 from x
@@ -1316,14 +1622,14 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
           pfr::launch_functional(fs, s->X, Fc, nv, q0, nullptr, nullptr, nullptr, st);
         }
       } else if (paired) {
-        if ((rc = solve_all(s, op, 0, 2, rg, nullptr, s->Y2, st, 1)) || (rc = sym_top_down_pair(s, st))) return rc;
-        pfr::launch_dirichlet_post(dd, op.pop, s->n_dir, s->XA, s->Fc, st);
+        if ((rc = solve_all(s, v, op, 0, 2, rg, nullptr, s->Y2, st, 1)) || (rc = sym_top_down_pair(s, v, st))) return rc;
+        pfr::launch_dirichlet_post(post_desc(s, v, op), op.pop, v.post_n, s->XA, s->Fc, st);
       } else {
-        if ((rc = adjoint_solve(s, op, rg, s->XA, st, 1))) return rc;
+        if ((rc = adjoint_solve(s, v, op, rg, s->XA, st, 1))) return rc;
         if (refine) {
           // l += A^{-T} (g - A^T l): residual into Y2, correction into XR
-          check_solution(s, op, 1, 0, 2, rg, nullptr, 0, nv, s->XA, s->Y2, q0, st);
-          if ((rc = adjoint_solve(s, op, rhs_vector(s->Y2), s->XR, st))) return rc;
+          check_solution(s, v, op, 1, 0, 2, rg, nullptr, 0, nv, s->XA, s->Y2, q0, st);
+          if ((rc = adjoint_solve(s, v, op, rhs_vector(s->Y2), s->XR, st))) return rc;
           pfr::launch_axpy_vec(s->XA, s->XR, (int64_t)s->n * Fc, st);
         }
       }
@@ -1345,7 +1651,7 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
       if (correct) {
         // the forward residual walk: backward error (when checked) + the correction's dot products,
         // then the corrected fr, its loss terms and the per-frequency cotangent scales
-        check_solution(s, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st, s->XA, want_f, cwalk);
+        check_solution(s, v, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st, s->XA, want_f, cwalk);
         want_f = false;
         if (scorr) pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st);
         pfr::FunctionalArgs fc = fa;
@@ -1366,11 +1672,11 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
         pfr::FunctionalArgs fs = fa;
         fs.fr0 = s->fr0;
         pfr::launch_functional(fs, s->X, Fc, nv, q0, nullptr, nullptr, s->Gx, st);
-        check_solution(s, op, 1, 0, 2, rhs_vector(s->Gx), nullptr, 0, nv, s->XA, s->XR, q0, st, nullptr, false, false,
+        check_solution(s, v, op, 1, 0, 2, rhs_vector(s->Gx), nullptr, 0, nv, s->XA, s->XR, q0, st, nullptr, false, false,
                        s->glist);
-        if ((rc = adjoint_solve(s, op, rhs_vector(s->XR), s->Y2, st, -1, s->glist))) return rc;
+        if ((rc = adjoint_solve(s, v, op, rhs_vector(s->XR), s->Y2, st, -1, s->glist))) return rc;
         pfr::launch_axpy_vec(s->XA, s->Y2, (int64_t)s->n * Fc, st, s->glist, Fc);
-        check_solution(s, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st, s->XA, false, true, s->glist);
+        check_solution(s, v, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st, s->XA, false, true, s->glist);
         if (scorr) pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st);
         pfr::launch_correct_finish(fa, s->fr0, s->cpart, pfr::residual_parts(s->n), Fc, nv, q0, fr_out, s->loss_terms,
                                    s->mscale, op, st, nullptr, scorr ? s->tq : nullptr);
@@ -1384,8 +1690,8 @@ int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_
       else if (reverse)
         pfr::launch_contract_eg(s->d_uent, s->n_uent, s->d_se, s->n_stiff, s->XA, s->X, Fc, nv, s->partial, st, msc);
       // the checks as row / column walks of the original pattern (k_residual)
-      if (want_f) check_solution(s, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st);
-      if (want_a) check_solution(s, op, 1, 0, 2, rg, nullptr, 0, nv, s->XA, nullptr, q0, st);
+      if (want_f) check_solution(s, v, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st);
+      if (want_a) check_solution(s, v, op, 1, 0, 2, rg, nullptr, 0, nv, s->XA, nullptr, q0, st);
       if (reverse) {
         if (!scorr) pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st, msc);
         if (jac)
@@ -1465,6 +1771,7 @@ int sweep_impl(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_t lo
       return direct();
     }
   }
+  s->comp_done = false;
   HIP_TRY(hipGraphLaunch(s->gexec, st));
   ++s->graph_launches;
   return PFR_OK;
@@ -1626,6 +1933,9 @@ int pfr_hessian_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int
   hipStream_t st = (hipStream_t)stream;
   reset_timing(s);
   const int64_t Fc = s->Fc, n = s->n;
+  SolverView& v = *s;                   // the tangent solves' right-hand sides are not the operator's: every front
+  if (s->act) s->unl_dirty = true;
+  s->last_pruned = false;
   int rc;
   if (!s->DX && ((rc = s->alloc(&s->DX, n * Fc)) || (rc = s->alloc(&s->DL, n * Fc)))) return rc;
   if (s->n_kdir < n_dir) {
@@ -1652,10 +1962,10 @@ int pfr_hessian_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int
     const int nv = (int)std::min<int64_t>(Fc, nfreq - q0);
     pfr::launch_chunk_start(s->freqs, freqs_dev + q0, nv, Fc, s->flags, st);
     const pfr::ChunkOp op = chunk_op(s);
-    if ((rc = factor_all(s, op, 0, nullptr, 0, nv, st))) return rc;
+    if ((rc = factor_all(s, v, op, 0, nullptr, 0, nv, st))) return rc;
     // forward solve, loss, adjoint, gradient partials (as pfr_sweep)
     const pfr::RhsArgs rd = rhs_operator(op);
-    if ((rc = forward_solve(s, op, 0, rd, s->X, st, 0))) return rc;
+    if ((rc = forward_solve(s, v, op, 0, rd, s->X, st, 0))) return rc;
     pfr::FunctionalArgs fa = s->fn;
     fa.loss_type = loss_type;
     fa.ref = reinterpret_cast<const double2*>(ref_dev);
@@ -1668,8 +1978,8 @@ int pfr_hessian_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int
       pfr::FunctionalArgs fs = fa;
       fs.fr0 = s->fr0;
       pfr::launch_functional(fs, s->X, Fc, nv, q0, nullptr, nullptr, s->G, st);
-      if ((rc = adjoint_solve(s, op, rg, s->XA, st, 1))) return rc;
-      check_solution(s, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st, s->XA, false);
+      if ((rc = adjoint_solve(s, v, op, rg, s->XA, st, 1))) return rc;
+      check_solution(s, v, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st, s->XA, false);
       // the loss sweep's cotangent, solve-error scale included (k_correct_finish): its gradient is the loss sweep's
       if (s->scale_corr) pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st);
       pfr::launch_correct_finish(fa, s->fr0, s->cpart, pfr::residual_parts(s->n), Fc, nv, q0, nullptr, s->loss_terms,
@@ -1678,7 +1988,7 @@ int pfr_hessian_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int
       // the second-order seeds G (k_functional_tangent) are formed from fa, not the seed mode
     } else {
       pfr::launch_functional(fa, s->X, Fc, nv, q0, nullptr, s->loss_terms, s->G, st);
-      if ((rc = adjoint_solve(s, op, rg, s->XA, st, 1))) return rc;
+      if ((rc = adjoint_solve(s, v, op, rg, s->XA, st, 1))) return rc;
     }
     contract_rows(s, s->XA, s->X, nv, st);
     pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st);
@@ -1690,12 +2000,12 @@ int pfr_hessian_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int
     for (int i = 0; i < n_dir; ++i) {
       const double2* Kd = s->Kdir + (int64_t)i * s->nnz;
       pfr::launch_tangent_spmv(s->d_rptr, s->d_ridx, s->d_rnz, (int)n, Kd, s->X, Fc, s->rhsP, beta[i], s->G, 0, st);
-      if ((rc = forward_solve(s, op, 2, rg, s->DX, st))) return rc;
+      if ((rc = forward_solve(s, v, op, 2, rg, s->DX, st))) return rc;
       HIP_TRY(hipMemsetAsync(s->G, 0, (size_t)n * Fc * 16, st));
       pfr::launch_functional_tangent(fa, s->X, s->DX, Fc, nv, q0, s->G, st);
       pfr::launch_tangent_spmv(s->d_cptr, s->d_cidx, s->d_cnz, (int)n, Kd, s->XA, Fc, nullptr, make_double2(0, 0),
                                s->G, 1, st);
-      if ((rc = adjoint_solve(s, op, rg, s->DL, st))) return rc;
+      if ((rc = adjoint_solve(s, v, op, rg, s->DL, st))) return rc;
       contract_rows(s, s->DL, s->X, nv, st);
       pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->DL, Fc, s->tq, st);
       pfr::launch_reduce(s->partial, pfr::contract_eg_parts(s->n_uent), s->n_stiff, s->tq, s->e, s->loss_terms, nv, Fc,
@@ -1726,6 +2036,9 @@ int pfr_solve_multi(pfr_solver* s, int32_t batch, int32_t nrhs, const double* da
   hipStream_t st = (hipStream_t)stream;
   reset_timing(s);
   const int64_t Fc = s->Fc;
+  SolverView& v = *s;                   // a caller's matrices: every front (a general analysis: no view exists;
+  if (s->act) s->unl_dirty = true;      // kept right should that ever change)
+  s->last_pruned = false;
   const double2* data = reinterpret_cast<const double2*>(data_dev);
   const double2* B = reinterpret_cast<const double2*>(b_dev);
   double2* Xo = reinterpret_cast<double2*>(x_dev);
@@ -1737,7 +2050,7 @@ int pfr_solve_multi(pfr_solver* s, int32_t batch, int32_t nrhs, const double* da
     record(s, 0, st);
     // padded lanes repeat the last valid item (stride 0 broadcast handled by the kernel's clamp)
     const pfr::ChunkOp op = chunk_op(s);   // explicit matrices: K and the rhs may be unset, none of it is read
-    int rc = factor_all(s, op, 1, data + q0 * data_stride, data_stride, nv, st);
+    int rc = factor_all(s, v, op, 1, data + q0 * data_stride, data_stride, nv, st);
     if (rc) return rc;
     record(s, 1, st);
     // every right-hand side of the chunk on the same factors (reference mode 4
@@ -1748,29 +2061,29 @@ int pfr_solve_multi(pfr_solver* s, int32_t batch, int32_t nrhs, const double* da
       rd.b_stride = b_stride;
       rd.nvalid = nv;
       if (!transpose) {
-        if ((rc = solve_all(s, op, 0, 1, rd, nullptr, s->Y, st))) return rc;
-        if ((rc = solve_all(s, op, 1, 1, rd, s->Y, s->X, st))) return rc;
+        if ((rc = solve_all(s, v, op, 0, 1, rd, nullptr, s->Y, st))) return rc;
+        if ((rc = solve_all(s, v, op, 1, 1, rd, s->Y, s->X, st))) return rc;
       }
       if (r == 0) {
         record(s, 2, st);
         record(s, 3, st);
       }
       if (transpose) {
-        if ((rc = solve_all(s, op, 2, 1, rd, nullptr, s->Y, st))) return rc;
-        if ((rc = solve_all(s, op, 3, 1, rd, s->Y, s->X, st))) return rc;
+        if ((rc = solve_all(s, v, op, 2, 1, rd, nullptr, s->Y, st))) return rc;
+        if ((rc = solve_all(s, v, op, 3, 1, rd, s->Y, s->X, st))) return rc;
       }
       const int which = transpose ? 1 : 0;
       const double2* dq = data + q0 * data_stride;
       if (s->check_mode & PFR_CHECK_REFINE) {
         // x += A^{-1} (b - A x) (or the transposed system) on the same factors
-        check_solution(s, op, which, 1, 1, rd, dq, data_stride, nv, s->X, s->G, r == 0 ? q0 : -1, st);
+        check_solution(s, v, op, which, 1, 1, rd, dq, data_stride, nv, s->X, s->G, r == 0 ? q0 : -1, st);
         const pfr::RhsArgs rr = rhs_vector(s->G);
-        if ((rc = solve_all(s, op, transpose ? 2 : 0, 2, rr, nullptr, s->Y, st))) return rc;
-        if ((rc = solve_all(s, op, transpose ? 3 : 1, 0, rr, s->Y, s->XA, st))) return rc;
+        if ((rc = solve_all(s, v, op, transpose ? 2 : 0, 2, rr, nullptr, s->Y, st))) return rc;
+        if ((rc = solve_all(s, v, op, transpose ? 3 : 1, 0, rr, s->Y, s->XA, st))) return rc;
         pfr::launch_axpy_vec(s->X, s->XA, (int64_t)s->n * Fc, st);
       }
       if (s->check_mode & (transpose ? PFR_CHECK_ADJOINT : PFR_CHECK_FORWARD))
-        check_solution(s, op, which, 1, 1, rd, dq, data_stride, nv, s->X, nullptr, r == 0 ? q0 : -1, st);
+        check_solution(s, v, op, which, 1, 1, rd, dq, data_stride, nv, s->X, nullptr, r == 0 ? q0 : -1, st);
       pfr::launch_unpermute(s->P.perm, s->n, s->X, Fc, nv, Xo + r * x_rhs_stride + q0 * s->n, st);
     }
     record(s, 4, st);

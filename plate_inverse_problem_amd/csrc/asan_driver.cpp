@@ -6,14 +6,20 @@
 // into such chunks), Schur block thresholds and solve split targets.  For each shape it also builds the launch
 // schedule (pfr::level_schedule, the records the level loops launch) under the environment's knobs, once with every
 // front reached and once with the reach of a single leaf row, and has every record checked (pfr::check_schedule).
+// Pruning's views go through the same checks for every shape: with a load on one leaf row (the trees
+// pfr::loaded_fronts marks for it) the plan and schedule of the loaded trees and of the rest, their reaches the
+// load's and the support's rows on each.  `symbolic_asan --forest` runs all of it on a built-in forest of three
+// trees (load in the first, sensor rows in the first two) and prints "forest ok <plans checked>".
 //
 // Input file (little-endian): int32 n, int64 nnz, int32 colptr[n + 1], int32 rowind[nnz],
 // int32 n_last, int32 last[n_last].  Each further argument is one option set
 // "leaf,ordering,symmetric,max_ns,md_delta,use_last"; per set one output line:
 // "n_fronts n_levels max_front total_rows nnz_lu factor_flops perm_hash n_dirichlet n_coupling", then one line
 // "plan ok <plans checked>" or "plan error <shape>: <violation>".
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 #include "plan.hpp"
@@ -24,9 +30,120 @@ template <class T>
 bool rd(FILE* f, T* p, size_t n) {
   return fread(p, sizeof(T), n, f) == n;
 }
+
+// Pruning's two views for a load on `load_row` (permuted) and the sensor rows `sup`: plans built with blk_min bm, then
+// every index and record checked for chunk Fc under the knobs k.  Returns "" or the first violation.  *split: some
+// tree is unloaded (the views differ from the full plan).
+struct Views {
+  pfr::Plan P[2];
+  std::vector<char> mask[2];
+  std::vector<int32_t> full_ptr[2], ptr[2][2];
+};
+std::string build_views(const pfr::Symbolic& S, int bm, int32_t load_row, const std::vector<int32_t>& sup,
+                        const std::vector<int32_t>& foc, const std::vector<int32_t>& par, Views& V) {
+  std::vector<double> rhs(S.n, 0.0);
+  rhs[load_row] = 1.0;
+  V.mask[0] = pfr::loaded_fronts(S, rhs.data());
+  V.mask[1] = V.mask[0];
+  for (char& m : V.mask[1]) m = !m;
+  if (!V.mask[0][foc[load_row]]) return "the loaded row's front is not loaded";
+  std::vector<int32_t> rows[2] = {{load_row}, sup}, mark, list;
+  for (size_t c = 0; c < S.cpl_p.size(); ++c) rows[0].push_back(S.cpl_p[c]);   // pfr_set_rhs: every coupled row
+  for (int w = 0; w < 2; ++w) pfr::reach_lists(foc, par, S.level_ptr, S.level_fronts, rows[w], mark, list, V.full_ptr[w]);
+  std::string err;
+  for (int side = 0; side < 2; ++side) {
+    if (pfr::build_plan(S, bm, V.P[side], err, &V.mask[side])) return err;
+    for (int w = side; w < 2; ++w)   // the rest carries no load: no forward reach
+      pfr::reach_lists(foc, par, V.P[side].level_ptr, V.P[side].level_fronts, pfr::rows_in(S, V.mask[side], rows[w]), mark,
+                       list, V.ptr[side][w]);
+  }
+  // the two views partition the fronts, level by level
+  for (size_t l = 0; l + 1 < S.level_ptr.size(); ++l)
+    if (V.P[0].level_ptr[l + 1] - V.P[0].level_ptr[l] + V.P[1].level_ptr[l + 1] - V.P[1].level_ptr[l] !=
+        S.level_ptr[l + 1] - S.level_ptr[l])
+      return "views do not partition a level";
+  return "";
+}
+std::string check_views(const pfr::Symbolic& S, const Views& V, int64_t Fc, const pfr::Knobs& k) {
+  for (int side = 0; side < 2; ++side) {
+    std::string e = pfr::check_plan(S, V.P[side], Fc);
+    if (e.empty()) e = pfr::check_schedule(S, V.P[side], pfr::level_schedule(S, V.P[side], Fc, k, V.ptr[side], &V.full_ptr));
+    if (!e.empty()) return std::string(side == 0 ? "loaded view: " : "unloaded view: ") + e;
+  }
+  return "";
+}
+
+// three tridiagonal blocks of 40, 33 and 21 nodes: a forest of three elimination trees
+int forest() {
+  const int sizes[3] = {40, 33, 21};
+  std::vector<int32_t> colptr(1, 0), rowind;
+  for (int b = 0, o = 0; b < 3; o += sizes[b++])
+    for (int j = 0; j < sizes[b]; ++j) {
+      for (int i = std::max(0, j - 1); i <= std::min(sizes[b] - 1, j + 1); ++i) rowind.push_back(o + i);
+      colptr.push_back((int32_t)rowind.size());
+    }
+  const int n = (int)colptr.size() - 1;
+  int checked = 0;
+  for (int leaf : {4, 16, 10000}) {
+    pfr::SymbolicOptions o;
+    o.leaf_size = leaf;
+    o.symmetric = 1;
+    pfr::Symbolic S;
+    if (pfr::analyse(n, (int64_t)rowind.size(), colptr.data(), rowind.data(), o, S) != 0) {
+      printf("forest error %s\n", S.error.c_str());
+      return 1;
+    }
+    std::vector<int32_t> foc(S.n, -1), par;
+    for (size_t t = 0; t < S.fronts.size(); ++t) {
+      par.push_back(S.fronts[t].parent);
+      for (int a = 0; a < S.fronts[t].ns; ++a) foc[S.fronts[t].col0 + a] = (int32_t)t;
+    }
+    const std::vector<int32_t> sup = {S.iperm[3], S.iperm[17], S.iperm[45], S.iperm[60]};   // trees 0, 0, 1, 1
+    for (int bm : {24, 0, 4}) {
+      Views V;
+      std::string e = build_views(S, bm, S.iperm[7], sup, foc, par, V);
+      // the loaded view is exactly tree 0: the fronts whose pivots are among the first block's nodes
+      for (size_t t = 0; t < S.fronts.size() && e.empty(); ++t)
+        if ((V.mask[0][t] != 0) != (S.perm[S.fronts[t].col0] < sizes[0])) e = "loaded mask is not the first tree";
+      // the reaches: the loaded view holds the load's and its sensor rows' fronts, the rest no forward reach and the
+      // second tree's sensor rows' fronts; together they are the full reaches (the third tree has no sensor row)
+      if (e.empty()) {
+        auto total = [](const std::vector<int32_t>& p) { return p.empty() ? 0 : p.back(); };
+        // the fronts holding the rows and their ancestors, counted by walking the tree
+        auto reached = [&](std::initializer_list<int32_t> rows) {
+          std::vector<char> seen(S.fronts.size(), 0);
+          int n_seen = 0;
+          for (int32_t p : rows)
+            for (int t = foc[p]; t >= 0 && !seen[t]; t = par[t]) seen[t] = 1, ++n_seen;
+          return n_seen;
+        };
+        if (total(V.ptr[0][0]) != reached({S.iperm[7]}) || total(V.ptr[1][0]) != 0 ||
+            total(V.ptr[0][1]) != reached({S.iperm[3], S.iperm[17]}) ||
+            total(V.ptr[1][1]) != reached({S.iperm[45], S.iperm[60]}) ||
+            total(V.ptr[0][1]) + total(V.ptr[1][1]) != total(V.full_ptr[1]))
+          e = "reaches of the views are not the loaded tree's rows and the second tree's";
+      }
+      for (int64_t Fc : {64, 512, 2048})
+        for (int sp : {256, 0, 1000000}) {
+          pfr::Knobs k = pfr::knobs_from_env(Fc);
+          k.blk_min = bm;
+          k.split_target = sp;
+          if (e.empty()) e = check_views(S, V, Fc, k);
+          if (!e.empty()) {
+            printf("forest error leaf=%d blk_min=%d Fc=%lld split=%d: %s\n", leaf, bm, (long long)Fc, sp, e.c_str());
+            return 1;
+          }
+          ++checked;
+        }
+    }
+  }
+  printf("forest ok %d\n", checked);
+  return 0;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
+  if (argc == 2 && std::string(argv[1]) == "--forest") return forest();
   if (argc < 3) {
     fprintf(stderr, "usage: %s pattern.bin leaf,ordering,symmetric,max_ns,md_delta,use_last ...\n", argv[0]);
     return 2;
@@ -83,6 +200,18 @@ int main(int argc, char** argv) {
         printf("plan error blk_min=%d: %s\n", bm, err.c_str());
         goto next;
       }
+      // pruning's views (symmetric analyses): a load on one leaf row, the support (or every 97th row) as sensor rows
+      Views V;
+      if (S.symmetric) {
+        std::vector<int32_t> sup;
+        for (int32_t v : last) sup.push_back(S.iperm[v]);
+        for (int i = 0; i < S.n && last.empty(); i += 97) sup.push_back(i);
+        err = build_views(S, bm, S.fronts[S.level_fronts[0]].col0, sup, foc, par, V);
+        if (!err.empty()) {
+          printf("plan error blk_min=%d views: %s\n", bm, err.c_str());
+          goto next;
+        }
+      }
       for (int64_t Fc : chunks)
         for (int sp : splits) {
           pfr::Knobs k = pfr::knobs_from_env(Fc);
@@ -91,6 +220,7 @@ int main(int argc, char** argv) {
           std::string e = pfr::check_plan(S, P, Fc);
           for (const auto& reach : {&reach_all, &reach_leaf})
             if (e.empty()) e = pfr::check_schedule(S, P, pfr::level_schedule(S, P, Fc, k, *reach));
+          if (e.empty() && S.symmetric) e = check_views(S, V, Fc, k);
           if (!e.empty()) {
             printf("plan error blk_min=%d Fc=%lld split=%d: %s\n", bm, (long long)Fc, sp, e.c_str());
             goto next;

@@ -2773,6 +2773,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NSK > 0 ? R
   for (int k = 0; k < (NSK > 0 ? NSK : 1); ++k) ks[k] = make_double2(0, 0);
   for (int t = wave0; t < A.n; t += nwaves) {
     const int p = A.walk[t];
+    if (p < 0) continue;    // a row of an unloaded tree (a pruned view's walk list); wave-uniform, as t is
     cplx mup = make_double2(0, 0);
     if (NSK > 0) mup = Mu[(int64_t)p * Fc + q];
     cplx b;
@@ -3278,6 +3279,7 @@ __global__ __launch_bounds__(256) void k_fn_dot(const int2* __restrict__ rows, i
   cplx s0 = make_double2(0, 0), s1 = s0, s2 = s0;
   for (int t = part * 4 + w; t < nrows; t += FN_PARTS * 4) {
     const int2 r = rows[t];
+    if (r.x < 0) continue;   // a slot a pruned view skips (its row's terms are exact zeros); wave-uniform
     const int64_t o = (int64_t)r.x * Fc + q;
     const cplx yb = cmul(Yb[o], crecip(F[(int64_t)r.y * Fc + q]));
     s0 = cadd(s0, cmul(Y0[o], yb));
@@ -3738,6 +3740,7 @@ void launch_assemble(int mode, const int4* recs, int nrec, const int* xptr, cons
 
 void launch_factor_lds(const DevPattern& P, const int* lvl, const FactorLevel& r, double2* F, int64_t Fc, int* flags,
                        hipStream_t st) {
+  if (r.nf <= 0) return;   // a view without a front on this level
   const size_t lds = (size_t)fac_lds_bytes(r.maxns);
   static_assert(FAC_LB == 8, "fac_lds_bytes: 8 W columns per row");
   // dynamic LDS beyond the default 64 KiB (up to 64 pivots: 37 KiB; headroom)
@@ -3748,6 +3751,7 @@ void launch_factor_lds(const DevPattern& P, const int* lvl, const FactorLevel& r
 
 void launch_factor(bool sym, const DevPattern& P, const int* lvl, const FactorLevel& r, int ngroups, double2* F,
                    int64_t Fc, int* flags, hipStream_t st) {
+  if (r.nf <= 0) return;   // a view without a front on this level
   if (!sym) {
     LAUNCH(k_factor_level<true>, dim3(r.nf, ngroups * FAC_G), dim3(64 * r.waves), st, P, lvl, F, Fc, flags);
     return;

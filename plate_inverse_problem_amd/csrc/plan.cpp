@@ -73,7 +73,7 @@ void each_more(const std::vector<std::pair<int32_t, int32_t>>& more, int32_t key
 
 }  // namespace
 
-int build_plan(const Symbolic& S, int blk_min, Plan& P, std::string& err) {
+int build_plan(const Symbolic& S, int blk_min, Plan& P, std::string& err, const std::vector<char>* mask) {
   P = Plan();
   if (S.max_front > MAX_FRONT) {
     err = "front larger than MAX_FRONT (plan.hpp)";
@@ -88,8 +88,41 @@ int build_plan(const Symbolic& S, int blk_min, Plan& P, std::string& err) {
   const int nfr = (int)S.fronts.size();
   P.L = L;
   P.sym = sym;
+  if (mask) {
+    if ((int)mask->size() != nfr) {
+      err = "front mask size";
+      return 1;
+    }
+    for (int t = 0; t < nfr; ++t)
+      if (S.fronts[t].parent >= 0 && (*mask)[t] != (*mask)[S.fronts[t].parent]) {
+        err = "front mask splits a tree";
+        return 1;
+      }
+    P.active = *mask;
+  } else {
+    P.active.assign(nfr, 1);
+  }
   P.level_maxns.assign(L, 0);
-  for (const Front& F : S.fronts) P.level_maxns[F.level] = std::max(P.level_maxns[F.level], F.ns);
+  P.level_maxf.assign(L, 0);
+  P.dec_maxns.assign(L, 0);
+  P.dec_maxf.assign(L, 0);
+  P.level_ptr.assign(1, 0);
+  P.dec_nitems.assign(L, 0);
+  for (int l = 0; l < L; ++l) {
+    P.dec_nf.push_back(S.level_ptr[l + 1] - S.level_ptr[l]);
+    for (int e = S.level_ptr[l]; e < S.level_ptr[l + 1]; ++e) {
+      const int t = S.level_fronts[e];
+      // L21 (U12) items of the front: one per OFF_G OFF_RPL update rows (general mode: and columns)
+      P.dec_nitems[l] += (sym ? 1 : 2) * ((S.fronts[t].f - S.fronts[t].ns + OFF_G * OFF_RPL - 1) / (OFF_G * OFF_RPL));
+      P.dec_maxns[l] = std::max(P.dec_maxns[l], S.fronts[t].ns);
+      P.dec_maxf[l] = std::max(P.dec_maxf[l], S.fronts[t].f);
+      if (!P.active[t]) continue;
+      P.level_fronts.push_back(t);
+      P.level_maxns[l] = std::max(P.level_maxns[l], S.fronts[t].ns);
+      P.level_maxf[l] = std::max(P.level_maxf[l], S.fronts[t].f);
+    }
+    P.level_ptr.push_back((int32_t)P.level_fronts.size());
+  }
   std::vector<std::vector<int>> kids(nfr);
   for (int t = 0; t < nfr; ++t)
     if (S.fronts[t].parent >= 0) kids[S.fronts[t].parent].push_back(t);
@@ -104,8 +137,8 @@ int build_plan(const Symbolic& S, int blk_min, Plan& P, std::string& err) {
   std::vector<int32_t> first;
   std::vector<std::pair<int32_t, int32_t>> more;
   for (int l = 0; l < L; ++l) {
-    for (int e = S.level_ptr[l]; e < S.level_ptr[l + 1]; ++e) {
-      const int t = S.level_fronts[e];
+    for (int e = P.level_ptr[l]; e < P.level_ptr[l + 1]; ++e) {
+      const int t = P.level_fronts[e];
       const Front& F = S.fronts[t];
       const int r = F.f - F.ns;
       a22_sources(S, kids, t, sym, first, more);
@@ -167,8 +200,8 @@ int build_plan(const Symbolic& S, int blk_min, Plan& P, std::string& err) {
   bool ok0 = sym;
   std::vector<std::pair<int32_t, std::vector<int32_t>>> f0;   // level-0 fronts: (front, records)
   for (int l = 0; l < L; ++l) {
-    for (int e = S.level_ptr[l]; e < S.level_ptr[l + 1]; ++e) {
-      const int t = S.level_fronts[e];
+    for (int e = P.level_ptr[l]; e < P.level_ptr[l + 1]; ++e) {
+      const int t = P.level_fronts[e];
       const Front& F = S.fronts[t];
       const int f = F.f, ns = F.ns;
       nzm.assign((size_t)f * f, -1);
@@ -256,6 +289,7 @@ int build_plan(const Symbolic& S, int blk_min, Plan& P, std::string& err) {
   // ---- algorithmic bytes per frequency and level of classes 0-4 (16 B per complex entry loaded or stored)
   P.lev_bytes.assign(L, std::array<int64_t, NKC>{});
   for (int t = 0; t < nfr; ++t) {
+    if (!P.active[t]) continue;
     const Front& F = S.fronts[t];
     const int64_t r = F.f - F.ns, ns = F.ns;
     const int64_t a11 = sym ? ns * (ns + 1) / 2 : ns * ns;
@@ -369,6 +403,46 @@ int build_plan(const Symbolic& S, int blk_min, Plan& P, std::string& err) {
   return 0;
 }
 
+std::vector<char> loaded_fronts(const Symbolic& S, const double* rhs_perm) {
+  const int nfr = (int)S.fronts.size();
+  std::vector<int32_t> front_of_col(S.n, -1), root(nfr);
+  for (int t = 0; t < nfr; ++t)
+    for (int a = 0; a < S.fronts[t].ns; ++a) front_of_col[S.fronts[t].col0 + a] = t;
+  for (int t = 0; t < nfr; ++t) {
+    int r = t;
+    while (S.fronts[r].parent >= 0) r = S.fronts[r].parent;
+    root[t] = r;
+  }
+  std::vector<char> loaded_root(nfr, 0);
+  auto load = [&](int32_t p) {
+    if (p >= 0 && p < S.n && front_of_col[p] >= 0) loaded_root[root[front_of_col[p]]] = 1;
+  };
+  for (int32_t p = 0; p < S.n; ++p)
+    if (rhs_perm[p] != 0.0) load(p);
+  for (size_t c = 0; c < S.cpl_p.size(); ++c)
+    if (rhs_perm[S.dir_p[S.cpl_dir[c]]] != 0.0) load(S.cpl_p[c]);
+  // a Dirichlet node whose column reaches a loaded tree stays with it (the node's own value is zero: its forward
+  // solution is zero too, but its 1 x 1 front is not worth a second kind of tree -- the loaded set is then the union
+  // of the pattern's connected components that hold a loaded row)
+  const std::vector<char> by_value(loaded_root);
+  for (size_t c = 0; c < S.cpl_p.size(); ++c)
+    if (by_value[root[front_of_col[S.cpl_p[c]]]]) load(S.dir_p[S.cpl_dir[c]]);
+  std::vector<char> mask(nfr);
+  for (int t = 0; t < nfr; ++t) mask[t] = loaded_root[root[t]];
+  return mask;
+}
+
+std::vector<int32_t> rows_in(const Symbolic& S, const std::vector<char>& mask, const std::vector<int32_t>& prows) {
+  std::vector<char> row_on(S.n, 0);
+  for (size_t t = 0; t < S.fronts.size(); ++t)
+    if (mask[t])
+      for (int a = 0; a < S.fronts[t].ns; ++a) row_on[S.fronts[t].col0 + a] = 1;
+  std::vector<int32_t> out;
+  for (int32_t p : prows)
+    if (p >= 0 && p < S.n && row_on[p]) out.push_back(p);
+  return out;
+}
+
 void reach_lists(const std::vector<int32_t>& front_of_col, const std::vector<int32_t>& front_parent,
                  const std::vector<int32_t>& level_ptr, const std::vector<int32_t>& level_fronts,
                  const std::vector<int32_t>& prows, std::vector<int32_t>& mark, std::vector<int32_t>& list,
@@ -408,6 +482,24 @@ std::string check_plan(const Symbolic& S, const Plan& P, int64_t Fc) {
   }
   for (int64_t r = 0; r < S.total_rows; ++r)
     if (S.idx[r] < 0 || S.idx[r] >= S.n) return bad("front row index", r, S.idx[r], S.n);
+  // the covered fronts: whole trees, each listed once in its level; every record's front among them
+  if ((int)P.active.size() != nfr || (int)P.level_ptr.size() != L + 1 || (int)P.level_maxf.size() != L ||
+      (int)P.level_maxns.size() != L || P.level_ptr[0] != 0 || P.level_ptr[L] != (int)P.level_fronts.size())
+    return "covered fronts";
+  {
+    int64_t n_act = 0;
+    for (int t = 0; t < nfr; ++t) {
+      n_act += P.active[t] != 0;
+      if (S.fronts[t].parent >= 0 && P.active[t] != P.active[S.fronts[t].parent]) return bad("view splits a tree", t, P.active[t], 2);
+    }
+    if (n_act != (int64_t)P.level_fronts.size()) return bad("covered front lists", 0, (int64_t)P.level_fronts.size(), n_act + 1);
+    for (int l = 0; l < L; ++l)
+      for (int e = P.level_ptr[l]; e < P.level_ptr[l + 1]; ++e) {
+        const int t = P.level_fronts[e];
+        if (t < 0 || t >= nfr || !P.active[t] || S.fronts[t].level != l) return bad("covered front", e, t, nfr);
+        if (S.fronts[t].ns > P.level_maxns[l] || S.fronts[t].f > P.level_maxf[l]) return bad("level geometry", l, S.fronts[t].f, P.level_maxf[l] + 1);
+      }
+  }
   // A11 assembly: records in chunks of 8 per launch (grid covers asm_ptr[l + 1] - asm_ptr[l] records)
   if (P.asm_rec.size() % 8 || P.asm_xp.size() != P.asm_rec.size() / 8 + 1) return "assembly chunks";
   for (size_t x = 0; x < P.asm_rec.size(); ++x) {
@@ -424,7 +516,7 @@ std::string check_plan(const Symbolic& S, const Plan& P, int64_t Fc) {
   if (P.oxp.size() != P.items.size() + 1) return "item overflow ranges";
   for (size_t i = 0; i < P.items.size(); ++i) {
     const I4& it = P.items[i];
-    if (it.x < 0 || it.x >= nfr) return bad("item front", i, it.x, nfr);
+    if (it.x < 0 || it.x >= nfr || !P.active[it.x]) return bad("item front", i, it.x, nfr);
     const Front& F = S.fronts[it.x];
     if (it.y < F.ns || it.y >= F.f) return bad("item row", i, it.y, F.f);
     if (it.w < 0 || it.w + (int64_t)OFF_G * OFF_RPL * F.ns > (int64_t)P.orec.size()) return bad("item records", i, it.w, P.orec.size());
@@ -440,14 +532,14 @@ std::string check_plan(const Symbolic& S, const Plan& P, int64_t Fc) {
   if (P.bg1.size() != P.blocks.size() * SCHUR_BLK_IDS || P.bgxp.size() != P.blocks.size() + 1) return "block sources";
   for (size_t i = 0; i < P.tiles.size(); ++i) {
     const I4& tt = P.tiles[i];
-    if (tt.x < 0 || tt.x >= nfr) return bad("tile front", i, tt.x, nfr);
+    if (tt.x < 0 || tt.x >= nfr || !P.active[tt.x]) return bad("tile front", i, tt.x, nfr);
     const int r = S.fronts[tt.x].f - S.fronts[tt.x].ns;
     if (tt.y < 0 || tt.y >= r || tt.z < 0 || tt.z >= r) return bad("tile origin", i, tt.y, r);
     if (P.gxp[i] > P.gxp[i + 1] || P.gxp[i + 1] > (int64_t)P.gx.size()) return bad("tile overflow", i, P.gxp[i], P.gx.size());
   }
   for (size_t i = 0; i < P.blocks.size(); ++i) {
     const I4& bk = P.blocks[i];
-    if (bk.x < 0 || bk.x >= nfr) return bad("block front", i, bk.x, nfr);
+    if (bk.x < 0 || bk.x >= nfr || !P.active[bk.x]) return bad("block front", i, bk.x, nfr);
     const int r = S.fronts[bk.x].f - S.fronts[bk.x].ns;
     if (bk.y < 0 || bk.y >= r || bk.z < 0 || bk.z > bk.y + SCHUR_BLK) return bad("block origin", i, bk.y, r);
     if (P.bgxp[i] > P.bgxp[i + 1] || P.bgxp[i + 1] > (int64_t)P.bgx.size()) return bad("block overflow", i, P.bgxp[i], P.bgx.size());
@@ -464,11 +556,11 @@ std::string check_plan(const Symbolic& S, const Plan& P, int64_t Fc) {
   if (P.fused0) {
     const int n0 = (int)P.f0_front.size();
     if ((int)P.f0_ptr.size() != n0 + 1 || P.f0_ptr[0] != 0 || P.f0_ptr[n0] != (int)P.f0_nz.size() ||
-        n0 != S.level_ptr[1] - S.level_ptr[0] || P.f0_small < 0 || P.f0_small > n0)
+        n0 != P.level_ptr[1] - P.level_ptr[0] || P.f0_small < 0 || P.f0_small > n0)
       return "fused level 0 lists";
     for (int i = 0; i < n0; ++i) {
       const int t = P.f0_front[i];
-      if (t < 0 || t >= (int)S.fronts.size()) return bad("fused level 0 front", i, t, (int64_t)S.fronts.size());
+      if (t < 0 || t >= (int)S.fronts.size() || !P.active[t]) return bad("fused level 0 front", i, t, (int64_t)S.fronts.size());
       const Front& F = S.fronts[t];
       const int r = F.f - F.ns;
       if (F.level != 0 || F.ns > F0_NS || r > F0_RM || (F.ns <= 2) != (i < P.f0_small) ||
@@ -486,6 +578,12 @@ std::string check_plan(const Symbolic& S, const Plan& P, int64_t Fc) {
     if (P.tile_ptr[l] > P.tile_ptr[l + 1] || P.blk_ptr[l] > P.blk_ptr[l + 1] || P.item_ptr[l] > P.item_ptr[l + 1] ||
         P.asm_ptr[l] > P.asm_ptr[l + 1])
       return bad("level range order", l, P.tile_ptr[l], P.tile_ptr[l + 1]);
+  // the whole analysis' item count per level (the L21 prefix is decided for it): the view's items are among them
+  if ((int)P.dec_nitems.size() != L || (int)P.dec_nf.size() != L) return "level item counts";
+  for (int l = 0; l < L; ++l) {
+    const int ni = P.item_ptr[l + 1] - P.item_ptr[l], full = P.level_ptr[l + 1] - P.level_ptr[l] == P.dec_nf[l];
+    if (ni > P.dec_nitems[l] || (full && ni != P.dec_nitems[l])) return bad("level item count", l, ni, P.dec_nitems[l] + 1);
+  }
   // Dirichlet lists
   const Workspace W = workspace(S, Fc, P.n_crow);
   for (size_t d = 0; d < P.dir.size(); ++d)
@@ -549,9 +647,10 @@ namespace {
 
 int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
-SolveLevel solve_level(const Schedule& sc, int l, int nf) {
+// nf: the fronts the launch shape is decided for (the full plan's count); count: the fronts the launch covers
+SolveLevel solve_level(const Schedule& sc, int l, int nf, int count) {
   SolveLevel r{};
-  r.nf = nf;
+  r.nf = count;
   r.level_w = waves_for(sc.level_maxf[l]);
   // raised (up to solve_wmax) when the launch has too few workgroups to fill the chip -- the sparse passes and the
   // top levels, which are latency-bound: every wave more takes rows off each wave's chain
@@ -564,15 +663,17 @@ SolveLevel solve_level(const Schedule& sc, int l, int nf) {
 
 }  // namespace
 
-void schedule_reach(Schedule& sc, const std::vector<int32_t> (&reach_ptr)[2]) {
+void schedule_reach(Schedule& sc, const std::vector<int32_t> (&reach_ptr)[2], const std::vector<int32_t> (*decide)[2]) {
   const Knobs& k = sc.knobs;
   const int L = (int)sc.level_nf.size();
   const int64_t ng = sc.Fc / 64;
-  auto count = [&](int w, int l) { return reach_ptr[w].empty() ? 0 : reach_ptr[w][l + 1] - reach_ptr[w][l]; };
+  auto count_of = [&](const std::vector<int32_t>& r, int l) { return r.empty() ? 0 : r[l + 1] - r[l]; };
+  auto count = [&](int w, int l) { return count_of(reach_ptr[w], l); };
+  auto dec = [&](int w, int l) { return count_of(decide ? (*decide)[w] : reach_ptr[w], l); };
   sc.chain.assign(L, ChainLevel{});
   for (int w = 0; w < 2; ++w) sc.solve[SUBSET_REACH0 + w].resize(L);
   for (int l = 0; l < L; ++l) {
-    for (int w = 0; w < 2; ++w) sc.solve[SUBSET_REACH0 + w][l] = solve_level(sc, l, count(w, l));
+    for (int w = 0; w < 2; ++w) sc.solve[SUBSET_REACH0 + w][l] = solve_level(sc, l, dec(w, l), count(w, l));
     ChainLevel& c = sc.chain[l];
     const int maxns = sc.level_maxns[l];
     c.nf0 = count(0, l);
@@ -580,10 +681,11 @@ void schedule_reach(Schedule& sc, const std::vector<int32_t> (&reach_ptr)[2]) {
     c.nmax = std::max(c.nf0, c.nf1);
     if (c.nmax == 0) continue;
     c.nsum = c.nf0 + 3 * c.nf1;
-    c.split = solve_split(c.nsum, sc.Fc, k.split_target);
-    c.waves = solve_waves(waves_for(sc.level_maxf[l]), c.nmax, sc.Fc, k.solve_wmax);
+    const int dsum = dec(0, l) + 3 * dec(1, l), dmax = std::max(dec(0, l), dec(1, l));   // what the shape is decided for
+    c.split = solve_split(dsum, sc.Fc, k.split_target);
+    c.waves = solve_waves(waves_for(sc.level_maxf[l]), dmax, sc.Fc, k.solve_wmax);
     // the narrow forms need the update rows apart (split > 1) and the largest pivot block in LDS
-    const bool nar = c.split > 1 && c.nsum * ng < k.us2_nar && ls_nar_fits(maxns);
+    const bool nar = c.split > 1 && dsum * ng < k.us2_nar && ls_nar_fits(maxns);
     c.rows = nar ? ROWS_ZC : c.split > 1 ? ROWS_Z : ROWS_NONE;
     if (nar) c.RB = ceil_div(std::max(1, sc.level_maxf[l] - 1), LRC_SR);
     if (nar && k.ls_rl && maxns <= 16 * RL_WMAX) {   // k_lsolve_rl_z: at most 4 rows per lane slot
@@ -598,24 +700,27 @@ void schedule_reach(Schedule& sc, const std::vector<int32_t> (&reach_ptr)[2]) {
 }
 
 Schedule level_schedule(const Symbolic& S, const Plan& P, int64_t Fc, const Knobs& k,
-                        const std::vector<int32_t> (&reach_ptr)[2]) {
+                        const std::vector<int32_t> (&reach_ptr)[2], const std::vector<int32_t> (*decide)[2]) {
   Schedule sc;
   sc.Fc = Fc;
   sc.knobs = k;
   sc.sym = P.sym;
-  sc.level_maxns = P.level_maxns;
-  sc.level_maxf = S.level_maxf;
+  // the launch shapes are decided for the whole analysis' level geometry (a view keeps the full plan's decisions on
+  // the fronts it covers: the same kernel form, split and wave count per front, so the same arithmetic); the records'
+  // counts are the view's
+  sc.level_maxns = P.dec_maxns;
+  sc.level_maxf = P.dec_maxf;
   const int L = P.L;
   const int64_t ng = Fc / 64;
-  for (int l = 0; l < L; ++l) sc.level_nf.push_back(S.level_ptr[l + 1] - S.level_ptr[l]);
+  for (int l = 0; l < L; ++l) sc.level_nf.push_back(P.level_ptr[l + 1] - P.level_ptr[l]);
   sc.factor.assign(L, FactorLevel{});
   sc.pair.assign(L, PairLevel{});
   sc.solve[SUBSET_ALL].resize(L);
   for (int l = 0; l < L; ++l) {
-    const int nf = sc.level_nf[l], maxns = sc.level_maxns[l];
-    const SolveLevel all = sc.solve[SUBSET_ALL][l] = solve_level(sc, l, nf);
+    const int nf = P.dec_nf[l], maxns = sc.level_maxns[l];
+    const SolveLevel all = sc.solve[SUBSET_ALL][l] = solve_level(sc, l, nf, sc.level_nf[l]);
     FactorLevel& f = sc.factor[l];
-    f.nf = nf;
+    f.nf = sc.level_nf[l];
     f.maxns = maxns;
     f.fused0 = l == 0 && P.fused0 && k.front0;
     f.f0_small = f.fused0 ? P.f0_small : 0;
@@ -638,10 +743,10 @@ Schedule level_schedule(const Symbolic& S, const Plan& P, int64_t Fc, const Knob
     f.ntiles = P.tile_ptr[l + 1] - P.tile_ptr[l];
     f.off_small = maxns <= 8;
     // the software-pipelined L21 prefix on the launches with few waves (symmetric analyses, not the SMALL form)
-    f.off_pu = P.sym && !f.off_small && f.nitems * ng < k.off_pu_waves ? 3 : 2;
+    f.off_pu = P.sym && !f.off_small && P.dec_nitems[l] * ng < k.off_pu_waves ? 3 : 2;   // the full plan's item count
 
     PairLevel& p = sc.pair[l];
-    p.nf = nf;
+    p.nf = sc.level_nf[l];
     p.small = sc.level_maxf[l] <= k.us2_small;
     p.tiny = k.us2_tiny > 0 && maxns <= k.us2_tiny ? (maxns <= 4 ? 4 : 8) : 0;
     const bool nar = nf * ng < k.us2_nar;
@@ -662,7 +767,7 @@ Schedule level_schedule(const Symbolic& S, const Plan& P, int64_t Fc, const Knob
       p.waves = all.waves;
     }
   }
-  schedule_reach(sc, reach_ptr);
+  schedule_reach(sc, reach_ptr, decide);
   return sc;
 }
 
@@ -678,12 +783,19 @@ std::string check_schedule(const Symbolic& S, const Plan& P, const Schedule& sc)
     if ((int)v.size() != L) return "schedule levels";
   auto waves_ok = [](int w, int hi) { return w >= 1 && w <= hi; };
   for (int l = 0; l < L; ++l) {
-    const int nf = S.level_ptr[l + 1] - S.level_ptr[l], maxns = P.level_maxns[l], maxf = S.level_maxf[l];
+    // the records are decided for the analysis' level geometry, which bounds the view's
+    const int nf = P.level_ptr[l + 1] - P.level_ptr[l], maxns = P.dec_maxns[l], maxf = P.dec_maxf[l];
+    if (P.level_maxns[l] > maxns || P.level_maxf[l] > maxf || nf > P.dec_nf[l]) return bad("level geometry", l, P.level_maxns[l], maxns);
     const FactorLevel& f = sc.factor[l];
     const PairLevel& p = sc.pair[l];
     const ChainLevel& c = sc.chain[l];
     if (f.nf != nf || p.nf != nf || sc.solve[SUBSET_ALL][l].nf != nf) return bad("fronts", l, f.nf, nf);
     if (f.maxns != maxns) return bad("largest pivot block", l, f.maxns, maxns);
+    if (nf == 0) {           // a view without a front on this level: no record may launch
+      if (c.nmax != 0 || f.nasm != 0 || f.nitems != 0 || f.nblocks != 0 || f.ntiles != 0) return bad("empty level", l, c.nmax, 0);
+      for (const auto& v : sc.solve)
+        if (v[l].nf != 0) return bad("empty level", l, v[l].nf, 0);
+    }
     if (f.lds && (maxns > 64 || fac_lds_bytes(maxns) > LDS_BYTES)) return bad("A11 LDS", l, maxns, 64);
     if (f.fused0 && (l != 0 || !P.fused0 || f.f0_small != P.f0_small)) return bad("fused level", l, f.fused0, 0);
     if (f.G != 2 && f.G != 4 && f.G != 8) return bad("lane groups", l, f.G, 8);
@@ -703,8 +815,8 @@ std::string check_schedule(const Symbolic& S, const Plan& P, const Schedule& sc)
     };
     auto split_ok = [&](int split, bool pivots, int rows) {   // over every front of the level
       if (split < 1 || split > 16) return false;
-      for (int e = S.level_ptr[l]; e < S.level_ptr[l + 1]; ++e) {
-        const Front& F = S.fronts[S.level_fronts[e]];
+      for (int e = P.level_ptr[l]; e < P.level_ptr[l + 1]; ++e) {
+        const Front& F = S.fronts[P.level_fronts[e]];
         if (!(pivots ? covered(0, F.ns, rows, split) : covered(F.ns, F.f, rows, split))) return false;
       }
       return true;

@@ -100,7 +100,14 @@ constexpr int F0_NS = 4, F0_RM = 10;
 struct Plan {
   int L = 0;                             // levels
   bool sym = false;
+  // the fronts the plan covers, level by level: every front of the analysis, or (a view, build_plan's mask) whole
+  // trees of its elimination forest -- the levels keep their numbers, a level may hold no front
+  std::vector<char> active;              // per front (all 1 without a mask)
+  std::vector<int32_t> level_ptr, level_fronts, level_maxf;
   std::vector<int32_t> level_maxns;      // largest pivot block per level
+  // the level geometry of the whole analysis (every front, whatever the mask): what level_schedule decides the
+  // launch shapes for
+  std::vector<int32_t> dec_nf, dec_maxns, dec_maxf, dec_nitems;   // fronts, largest pivot block / front, L21 items
   std::vector<char> blk_front;           // front's Schur complement by the block kernel
   // Schur tiles (front, i0, j0, -) by level, per tile SCHUR_TILE first child sources, overflow ranges
   std::vector<I4> tiles;
@@ -148,8 +155,20 @@ struct Workspace {
 Workspace workspace(const Symbolic& S, int64_t Fc, int n_crow);
 
 // Builds the plan (blk_min: Knobs::blk_min); returns 0, or non-zero with err set (a front too large for the kernels,
-// int32 overflow)
-int build_plan(const Symbolic& S, int blk_min, Plan& P, std::string& err);
+// int32 overflow).  mask (per front, may be NULL: every front): the gather records of the factor classes, the level
+// lists and the level geometry over the masked fronts only -- a view of the plan; the mask must hold whole trees
+// (a front with its parent).  The Dirichlet lists, compressed rows / columns and contraction entries do not depend
+// on it.
+int build_plan(const Symbolic& S, int blk_min, Plan& P, std::string& err, const std::vector<char>* mask = nullptr);
+
+// The trees of the elimination forest that carry load ("Pruning"): per front 1 when its tree
+// holds a permuted row with a non-zero entry of rhs_perm (the right-hand side vector, permuted) or a coupled row of a
+// Dirichlet node whose entry of rhs_perm is non-zero (the analysis' coupling lists, by value), and the decoupled
+// Dirichlet nodes whose column reaches such a tree.  On the other trees the forward solution of the operator right-hand
+// side is exactly zero.
+std::vector<char> loaded_fronts(const Symbolic& S, const double* rhs_perm);
+// rows of `prows` on fronts of the mask (a reach restricted to a view)
+std::vector<int32_t> rows_in(const Symbolic& S, const std::vector<char>& mask, const std::vector<int32_t>& prows);
 
 // The fronts holding the given permuted rows and all their ancestors: per-front flags and the marked fronts
 // level by level (level order kept; ptr per level).  front_of_col: the front of each pivot column (permuted).
@@ -257,10 +276,14 @@ struct Schedule {
 template <class R> constexpr int schedule_cols() { return (int)(sizeof(R) / sizeof(int32_t)); }
 // Pure: the schedule of a solver with chunk Fc under the knobs k, for the reaches given by their per-level ranges
 // (reach_lists' ptr; an empty vector: no front reached)
+// decide (a view; NULL: reach_ptr): the full plan's reaches.  A view's records take every launch-shape decision as
+// the full plan takes it -- from the analysis' level geometry (Plan::dec_*) and the full reaches -- and only their
+// counts from the view, so each front it covers runs the arithmetic it runs under the full plan, in the same order
 Schedule level_schedule(const Symbolic& S, const Plan& P, int64_t Fc, const Knobs& k,
-                        const std::vector<int32_t> (&reach_ptr)[2]);
+                        const std::vector<int32_t> (&reach_ptr)[2], const std::vector<int32_t> (*decide)[2] = nullptr);
 // The records that depend on the reaches (chain, solve[SUBSET_REACH*]) again, after a reach changed
-void schedule_reach(Schedule& sc, const std::vector<int32_t> (&reach_ptr)[2]);
+void schedule_reach(Schedule& sc, const std::vector<int32_t> (&reach_ptr)[2],
+                    const std::vector<int32_t> (*decide)[2] = nullptr);
 // Every record against the kernels' limits (LDS sizes, rows per lane slot, wave counts, the row blocks and the
 // split parts covering every row once).  Returns "" or the first violation.
 std::string check_schedule(const Symbolic& S, const Plan& P, const Schedule& sc);
