@@ -209,8 +209,10 @@ PFR_API int pfr_set_prune(pfr_solver* s, int32_t on);
  * the adjoint on) and checks every index and record of both as pfr_solver_create's plan is checked (PFR_ERR_STATE and
  * pfr_last_error on a violation); sched_active / sched_rest / sched_full (may be NULL, capacity in bytes each): their
  * schedules and the full plan's with the same reaches, in pfr_symbolic_schedule's layout.  A view's records take every
- * launch-shape decision as the full plan takes it (from the whole analysis' level geometry and the full reaches) and
- * only their counts from the view: each front runs the same arithmetic in the same order with pruning on and off. */
+ * launch-shape decision as the full plan takes it (from the whole analysis' level geometry and the full reaches;
+ * fused0 from every level-0 front of the analysis: a view with a level-0 front runs it through k_front0 exactly when
+ * the full plan does) and only their counts from the view: each front runs the same arithmetic in the same order with
+ * pruning on and off. */
 PFR_API int pfr_symbolic_prune(const pfr_symbolic* sym, int32_t max_batch, const double* rhs, int32_t n_support,
                                const int32_t* index, int32_t* mask, int32_t* sched_active, int32_t* sched_rest,
                                int32_t* sched_full, int64_t capacity_bytes);

@@ -9,7 +9,9 @@
 // Pruning's views go through the same checks for every shape: with a load on one leaf row (the trees
 // pfr::loaded_fronts marks for it) the plan and schedule of the loaded trees and of the rest, their reaches the
 // load's and the support's rows on each.  `symbolic_asan --forest` runs all of it on a built-in forest of three
-// trees (load in the first, sensor rows in the first two) and prints "forest ok <plans checked>".
+// trees (load in the first, sensor rows in the first two) and prints "forest ok <plans checked>"; before that, on two
+// forests of two clique trees whose first tree's leaves fit the fused bottom level (fused_forest: the second tree's do
+// not / do too), it has both views follow the full plan's decision for level 0, loaded on either tree.
 //
 // Input file (little-endian): int32 n, int64 nnz, int32 colptr[n + 1], int32 rowind[nnz],
 // int32 n_last, int32 last[n_last].  Each further argument is one option set
@@ -73,8 +75,88 @@ std::string check_views(const pfr::Symbolic& S, const Views& V, int64_t Fc, cons
   return "";
 }
 
+// Two trees of cliques (of ms[k][i] nodes) fully coupled to a dense border of s[k] nodes each, the first tree's border
+// eliminated last: its leaves fit the fused bottom level (at most F0_NS pivots and F0_RM update rows).  `big`: the
+// second tree's leaves do not, so the full plan does not fuse level 0 and neither view may -- the bottom level is
+// decided for the whole analysis; otherwise both fit, and the full plan and both views fuse, each view listing its own
+// fronts.  Returns "" or the first violation; the views also go through check_views.
+std::string fused_forest(bool big) {
+  const std::vector<int> ms[2] = {{1, 2, 3, 4, 4}, big ? std::vector<int>{3, 6, 9} : std::vector<int>{2, 2, 4}};
+  const int s[2] = {10, big ? 12 : 6};
+  std::vector<std::vector<int32_t>> col;
+  int32_t border0 = 0;
+  for (int k = 0, o = 0; k < 2; ++k) {
+    int m_all = 0;
+    for (int m : ms[k]) m_all += m;
+    const int nb = m_all + s[k], b0 = o + m_all;
+    col.resize(o + nb);
+    for (int c0 = o, i = 0; i < (int)ms[k].size(); c0 += ms[k][i++])
+      for (int a = c0; a < c0 + ms[k][i]; ++a) {
+        for (int b = c0; b < c0 + ms[k][i]; ++b) col[a].push_back(b);
+        for (int b = b0; b < o + nb; ++b) col[a].push_back(b), col[b].push_back(a);
+      }
+    for (int a = b0; a < o + nb; ++a)
+      for (int b = b0; b < o + nb; ++b) col[a].push_back(b);
+    if (k == 0) border0 = b0;
+    o += nb;
+  }
+  std::vector<int32_t> colptr(1, 0), rowind;
+  for (auto& c : col) {
+    std::sort(c.begin(), c.end());
+    rowind.insert(rowind.end(), c.begin(), c.end());
+    colptr.push_back((int32_t)rowind.size());
+  }
+  const int n = (int)col.size();
+  pfr::SymbolicOptions o;
+  o.symmetric = 1;
+  for (int i = 0; i < s[0]; ++i) o.last.push_back(border0 + i);
+  pfr::Symbolic S;
+  if (pfr::analyse(n, (int64_t)rowind.size(), colptr.data(), rowind.data(), o, S) != 0) return S.error;
+  std::vector<int32_t> foc(S.n, -1), par;
+  for (size_t t = 0; t < S.fronts.size(); ++t) {
+    par.push_back(S.fronts[t].parent);
+    for (int a = 0; a < S.fronts[t].ns; ++a) foc[S.fronts[t].col0 + a] = (int32_t)t;
+  }
+  const int first1 = border0 + s[0];   // the second tree's first node
+  pfr::Plan P;
+  std::string err;
+  if (pfr::build_plan(S, 24, P, err)) return err;
+  if (P.fused0 != !big) return "full plan: fused bottom level";
+  for (int loaded = 0; loaded < 2; ++loaded) {
+    Views V;
+    std::string e = build_views(S, 24, S.iperm[loaded ? first1 : 0], {S.iperm[border0], S.iperm[n - 1]}, foc, par, V);
+    if (!e.empty()) return e;
+    // the view of the first tree alone holds only fronts that fit: it must still follow the full plan
+    int fit = 0, n0 = 0;
+    const pfr::Plan& first = V.P[loaded];
+    for (int e0 = first.level_ptr[0]; e0 < first.level_ptr[1]; ++e0, ++n0) {
+      const pfr::Front& F = S.fronts[first.level_fronts[e0]];
+      fit += F.ns <= pfr::F0_NS && F.f - F.ns <= pfr::F0_RM;
+    }
+    if (n0 == 0 || fit != n0) return "the first tree's leaves do not all fit the fused bottom level";
+    for (int side = 0; side < 2; ++side)
+      if (V.P[side].fused0 != P.fused0) return side == loaded ? "first tree's view: fused bottom level" : "second tree's view: fused bottom level";
+    if (P.fused0 && V.P[0].f0_front.size() + V.P[1].f0_front.size() != P.f0_front.size()) return "views do not partition the fused fronts";
+    for (int64_t Fc : {64, 512})
+      for (int front0 : {1, 0}) {
+        pfr::Knobs k = pfr::knobs_from_env(Fc);
+        k.front0 = front0;
+        e = check_views(S, V, Fc, k);
+        if (!e.empty()) return e;
+      }
+  }
+  return "";
+}
+
 // three tridiagonal blocks of 40, 33 and 21 nodes: a forest of three elimination trees
 int forest() {
+  for (int big = 0; big < 2; ++big) {
+    const std::string e = fused_forest(big != 0);
+    if (!e.empty()) {
+      printf("forest error fused bottom level (%s second tree): %s\n", big ? "large" : "small", e.c_str());
+      return 1;
+    }
+  }
   const int sizes[3] = {40, 33, 21};
   std::vector<int32_t> colptr(1, 0), rowind;
   for (int b = 0, o = 0; b < 3; o += sizes[b++])

@@ -197,49 +197,73 @@ int build_plan(const Symbolic& S, int blk_min, Plan& P, std::string& err, const 
   P.item_ptr.assign(1, 0);
   std::vector<int32_t> nzm, s1m;
   std::vector<std::pair<int32_t, int32_t>> morem;   // (a * f + b, id)
+  // the panel-region sources of front t: nzm / s1m (f x f, -1 none) and the sorted overflow list morem
+  auto panel_sources = [&](int t) {
+    const Front& F = S.fronts[t];
+    const int f = F.f, ns = F.ns;
+    nzm.assign((size_t)f * f, -1);
+    s1m.assign((size_t)f * f, -1);
+    morem.clear();
+    for (int a = 0; a < f; ++a) {
+      const int r = F.row0 + a;
+      const int width = a < ns ? f : ns;
+      for (int x = S.asm_ptr[r]; x < S.asm_ptr[r + 1]; ++x)
+        if (S.asm_col[x] < width) nzm[(size_t)a * f + S.asm_col[x]] = S.asm_nz[x];
+      for (int x = S.ea_ptr[r]; x < S.ea_ptr[r + 1]; ++x) {
+        const int src = S.ea_src[x];
+        const Front& C = S.fronts[S.row_front[src]];
+        const int32_t* rp = S.relpos.data() + C.row0;
+        for (int b = C.ns; b < C.f; ++b) {
+          const int pb = rp[b];
+          if (pb >= width) continue;
+          // symmetric: the child's update matrix holds its lower triangle only
+          const int ca = src - C.row0;
+          const int32_t id = (int32_t)(C.off + (sym && ca < b ? (int64_t)b * C.f + ca : (int64_t)ca * C.f + b));
+          int32_t& s1 = s1m[(size_t)a * f + pb];
+          if (s1 < 0)
+            s1 = id;
+          else
+            morem.emplace_back(a * f + pb, id);
+        }
+      }
+    }
+    std::sort(morem.begin(), morem.end());
+  };
+  // the fused bottom level (k_front0) is a decision for the whole analysis: every level-0 front, covered by this plan
+  // or not, within F0_NS pivots and F0_RM update rows and without child entries -- a view fuses its bottom level
+  // exactly when the full plan does (and lists only its own fronts)
+  std::vector<int32_t> rec0;
+  auto front0_ok = [&](int t) {   // after panel_sources(t); rec0: the front's records
+    const Front& F = S.fronts[t];
+    const int f = F.f, ns = F.ns;
+    bool ok = ns <= F0_NS && f - ns <= F0_RM && morem.empty();
+    rec0.clear();
+    for (int a = 0; a < f && ok; ++a)
+      for (int b = 0; b < std::min(a + 1, ns); ++b) {
+        ok = ok && s1m[(size_t)a * f + b] < 0;   // leaves: no child entries
+        rec0.push_back(nzm[(size_t)a * f + b]);
+      }
+    return ok;
+  };
   bool ok0 = sym;
+  for (int e = L > 0 ? S.level_ptr[0] : 0; ok0 && e < (L > 0 ? S.level_ptr[1] : 0); ++e) {
+    const int t = S.level_fronts[e];
+    if (P.active[t]) continue;   // the covered fronts are checked where their records are built
+    ok0 = S.fronts[t].ns <= F0_NS && S.fronts[t].f - S.fronts[t].ns <= F0_RM;
+    if (!ok0) break;
+    panel_sources(t);
+    ok0 = front0_ok(t);
+  }
   std::vector<std::pair<int32_t, std::vector<int32_t>>> f0;   // level-0 fronts: (front, records)
   for (int l = 0; l < L; ++l) {
     for (int e = P.level_ptr[l]; e < P.level_ptr[l + 1]; ++e) {
       const int t = P.level_fronts[e];
       const Front& F = S.fronts[t];
       const int f = F.f, ns = F.ns;
-      nzm.assign((size_t)f * f, -1);
-      s1m.assign((size_t)f * f, -1);
-      morem.clear();
-      for (int a = 0; a < f; ++a) {
-        const int r = F.row0 + a;
-        const int width = a < ns ? f : ns;
-        for (int x = S.asm_ptr[r]; x < S.asm_ptr[r + 1]; ++x)
-          if (S.asm_col[x] < width) nzm[(size_t)a * f + S.asm_col[x]] = S.asm_nz[x];
-        for (int x = S.ea_ptr[r]; x < S.ea_ptr[r + 1]; ++x) {
-          const int src = S.ea_src[x];
-          const Front& C = S.fronts[S.row_front[src]];
-          const int32_t* rp = S.relpos.data() + C.row0;
-          for (int b = C.ns; b < C.f; ++b) {
-            const int pb = rp[b];
-            if (pb >= width) continue;
-            // symmetric: the child's update matrix holds its lower triangle only
-            const int ca = src - C.row0;
-            const int32_t id = (int32_t)(C.off + (sym && ca < b ? (int64_t)b * C.f + ca : (int64_t)ca * C.f + b));
-            int32_t& s1 = s1m[(size_t)a * f + pb];
-            if (s1 < 0)
-              s1 = id;
-            else
-              morem.emplace_back(a * f + pb, id);
-          }
-        }
-      }
-      std::sort(morem.begin(), morem.end());
+      panel_sources(t);
       if (l == 0 && ok0) {
-        ok0 = ns <= F0_NS && f - ns <= F0_RM && morem.empty();
-        std::vector<int32_t> rec;
-        for (int a = 0; a < f && ok0; ++a)
-          for (int b = 0; b < std::min(a + 1, ns); ++b) {
-            ok0 = ok0 && s1m[(size_t)a * f + b] < 0;   // leaves: no child entries
-            rec.push_back(nzm[(size_t)a * f + b]);
-          }
-        if (ok0) f0.emplace_back(t, std::move(rec));
+        ok0 = front0_ok(t);
+        if (ok0) f0.emplace_back(t, rec0);
       }
       for (int a = 0; a < ns; ++a)
         for (int b = 0; b < (sym ? a + 1 : ns); ++b) {   // symmetric: A11's lower triangle only
@@ -558,6 +582,11 @@ std::string check_plan(const Symbolic& S, const Plan& P, int64_t Fc) {
     if ((int)P.f0_ptr.size() != n0 + 1 || P.f0_ptr[0] != 0 || P.f0_ptr[n0] != (int)P.f0_nz.size() ||
         n0 != P.level_ptr[1] - P.level_ptr[0] || P.f0_small < 0 || P.f0_small > n0)
       return "fused level 0 lists";
+    // decided for the whole analysis: every level-0 front fits, whether this plan covers it or not
+    for (int e = S.level_ptr[0]; e < S.level_ptr[1]; ++e) {
+      const Front& F = S.fronts[S.level_fronts[e]];
+      if (F.ns > F0_NS || F.f - F.ns > F0_RM) return bad("fused level 0 decided for the view alone", S.level_fronts[e], F.ns, F0_NS + 1);
+    }
     for (int i = 0; i < n0; ++i) {
       const int t = P.f0_front[i];
       if (t < 0 || t >= (int)S.fronts.size() || !P.active[t]) return bad("fused level 0 front", i, t, (int64_t)S.fronts.size());
@@ -569,6 +598,18 @@ std::string check_plan(const Symbolic& S, const Plan& P, int64_t Fc) {
     }
     for (size_t x = 0; x < P.f0_nz.size(); ++x)
       if (P.f0_nz[x] < -1 || P.f0_nz[x] >= S.nnz) return bad("fused level 0 nz", x, P.f0_nz[x], S.nnz);
+  } else if (P.sym && L > 0 && P.level_ptr[1] > P.level_ptr[0]) {
+    // ... and the other way round: a plan with level-0 fronts leaves them unfused only if some level-0 front of the
+    // analysis does not fit (one without children has no child entries)
+    bool fits = true;
+    std::vector<char> has_child(nfr, 0);
+    for (int t = 0; t < nfr; ++t)
+      if (S.fronts[t].parent >= 0) has_child[S.fronts[t].parent] = 1;
+    for (int e = S.level_ptr[0]; e < S.level_ptr[1] && fits; ++e) {
+      const Front& F = S.fronts[S.level_fronts[e]];
+      fits = F.ns <= F0_NS && F.f - F.ns <= F0_RM && !has_child[S.level_fronts[e]];
+    }
+    if (fits) return "level 0 not fused where the whole analysis' fronts fit";
   }
   // per-level ranges monotone and complete
   if ((int)P.tile_ptr.size() != L + 1 || (int)P.blk_ptr.size() != L + 1 || (int)P.item_ptr.size() != L + 1 ||

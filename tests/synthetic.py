@@ -74,10 +74,19 @@ class Pattern:
     border: np.ndarray        # the clique eliminated last (``last`` of the analysis)
     leaves: tuple             # indices into ``cliques`` of the leaf cliques
     dirichlet: np.ndarray
+    parts: tuple = ()         # a forest's components: (node offset, Pattern) each; empty on a connected pattern
 
     @property
     def nnz(self):
         return int(self.rows.size)
+
+    def components(self):
+        """[(leaf cliques, Dirichlet nodes, border, all nodes)] per connected component, in this pattern's numbering."""
+        out = []
+        for off, p in self.parts or ((0, self),):
+            out.append(([off + p.cliques[c] for c in p.leaves], off + p.dirichlet, off + p.border,
+                        np.arange(off, off + p.n)))
+        return out
 
     def dense(self, vals, dtype=None):
         A = np.zeros((self.n, self.n), dtype=dtype or np.asarray(vals).dtype)
@@ -149,6 +158,29 @@ def clique_tree(spec=TREE_SPEC, frac=0.5, n_dir=0, seed=0):
     return _finish(name, n, pairs, cliques, cliques[roots[0]], leaves, n_dir, rng)
 
 
+def forest(patterns, pin=0, name=None):
+    """The block-diagonal union of ``patterns`` as one Pattern: a forest of elimination trees, one connected component
+    (with its Dirichlet nodes) per pattern.  Nodes are offset and the entries kept in CSC order; cliques, leaves and
+    Dirichlet nodes are concatenated; ``border`` is component ``pin``'s, so an analysis with ``last=border`` pins that
+    component only (a ``last`` set spanning components would join the trees under one root front)."""
+    offs = np.concatenate([[0], np.cumsum([p.n for p in patterns])]).astype(np.int64)
+    rows = np.concatenate([p.rows.astype(np.int64) + o for p, o in zip(patterns, offs)])
+    cols = np.concatenate([p.cols.astype(np.int64) + o for p, o in zip(patterns, offs)])
+    order = np.lexsort((rows, cols))
+    rows, cols = rows[order], cols[order]
+    n = int(offs[-1])
+    colptr = np.zeros(n + 1, np.int64)
+    np.add.at(colptr, cols + 1, 1)
+    cliques, leaves = [], []
+    for p, o in zip(patterns, offs):
+        leaves += [len(cliques) + c for c in p.leaves]
+        cliques += [c + o for c in p.cliques]
+    dirichlet = np.concatenate([p.dirichlet + o for p, o in zip(patterns, offs)]).astype(np.int64)
+    return Pattern(name or " + ".join(p.name for p in patterns), n, rows.astype(np.int32), cols.astype(np.int32),
+                   np.cumsum(colptr).astype(np.int32), tuple(cliques), patterns[pin].border + offs[pin], tuple(leaves),
+                   dirichlet, tuple((int(o), p) for p, o in zip(patterns, offs)))
+
+
 # ----------------------------------------------------------------------------- dispatch classes
 def dispatch_classes(sym, Fc=64):
     """Per-level launch classes of an analysis for chunks of ``Fc`` frequencies, level 0 first: the front geometry
@@ -188,6 +220,58 @@ def dispatch_classes(sym, Fc=64):
             fused0=bool(fac["fused0"]),                                 # k_front0
             blk=blk))                                                   # 16 x 16 LDS Schur blocks
     return out
+
+
+def schedule_classes(sc):
+    """Per-level launch classes of one schedule (``Symbolic.schedule``, or a view's of ``Symbolic.prune`` /
+    ``Solver.schedule_active``), level 0 first, by the names of dispatch_classes; a level the view holds no front on
+    is None (nothing is launched there)."""
+    from plate_inverse_problem_amd._native import CHAIN_FORMS, CHAIN_ROWS, PAIR_FORMS, PAIR_UPD
+    out = []
+    for lv in range(sc["factor"].size):
+        fac, pair, chain, sol = (sc[k][lv] for k in ("factor", "pair", "chain", "solve_all"))
+        if fac["nf"] == 0:
+            out.append(None)
+            continue
+        d = dict(nf=int(fac["nf"]), fused0=bool(fac["fused0"]), f0_small=int(fac["f0_small"]),
+                 fac_lds_auto=bool(fac["lds"]), fac_big=int(fac["G"]) > 2, G=int(fac["G"]), off_pu=int(fac["off_pu"]),
+                 blk=int(fac["nblocks"]) > 0, tiles=int(fac["ntiles"]) > 0, pair=PAIR_FORMS[pair["form"]],
+                 pair_upd=PAIR_UPD[pair["upd"]], tiny=int(pair["tiny"]), split_L=int(sol["split_L"]),
+                 split_U=int(sol["split_U"]), nf0=int(chain["nf0"]), nf1=int(chain["nf1"]))
+        if chain["nmax"] > 0:      # the bottom-up chain runs on the levels a reach holds a front on
+            d.update(chain=CHAIN_FORMS[chain["form"]], rows=CHAIN_ROWS[chain["rows"]])
+        out.append(d)
+    return out
+
+
+def class_line(d):
+    """One level of schedule_classes as the line the tests' tables hold: the front count, the factor classes that are
+    on (fused0, lds, G<lane groups>, blk, tiles, pu<L21 prefix>), pair form / update part, chain form / update rows;
+    "-" for a level the view holds no front on."""
+    if d is None:
+        return "-"
+    s = [str(d["nf"])] + [k for k, on in (("fused0", d["fused0"]), ("lds", d["fac_lds_auto"])) if on] + [f"G{d['G']}"]
+    s += [k for k in ("blk", "tiles") if d[k]] + [f"pu{d['off_pu']}", d["pair"] + "/" + d["pair_upd"]]
+    return " ".join(s + [d.get("chain", "none") + "/" + d.get("rows", "none")])
+
+
+# the schedule's columns that count a view's own records; every other column is a launch decision, which a view takes
+# as the full plan takes it (include/pfr.h, pfr_set_prune)
+SCHEDULE_COUNTS = {"factor": ("nf", "f0_small", "nasm", "nitems", "nblocks", "ntiles"), "pair": ("nf",),
+                   "chain": ("nf0", "nf1", "nmax", "nsum"), "solve_all": ("nf",), "solve_reach0": ("nf",),
+                   "solve_reach1": ("nf",)}
+
+
+def schedule_disagreements(view, full):
+    """[(table, column, level)] where a view's schedule differs from the full plan's in a column that is not a count,
+    on the levels the view (the reach, for the reach-dependent tables) holds a front on."""
+    bad = []
+    for name, skip in SCHEDULE_COUNTS.items():
+        lv = view[name]["nmax" if name == "chain" else "nf"] > 0
+        for col in view[name].dtype.names:
+            if col not in skip:
+                bad += [(name, col, int(l)) for l in np.nonzero(lv & (view[name][col] != full[name][col]))[0]]
+    return bad
 
 
 # ----------------------------------------------------------------------------- values
@@ -242,8 +326,13 @@ class Operator:
         return a
 
 
-def make_operator(pat: Pattern, n_stiff=12, seed=0, dense_rhs=False, support=None, weak_bits=0):
-    """``weak_bits`` > 0: the weak-pivot variant -- the diagonal entries of every S_k and of M at the first node of
+def make_operator(pat: Pattern, n_stiff=12, seed=0, dense_rhs=False, support=None, weak_bits=0, load=None):
+    """``load`` (default: component 0): where the right-hand side is non-zero -- a tuple of component indices of a
+    forest (on each the first three nodes of its first two leaf cliques and its first Dirichlet node, as on a connected
+    pattern), or an ndarray of nodes.  ``support``: the functional's rows (default: 8 of the border; a forest is given
+    rows on every component -- on an unloaded one they see x = 0, and only the adjoint is non-zero there).
+
+    ``weak_bits`` > 0: the weak-pivot variant -- the diagonal entries of every S_k and of M at the first node of
     every leaf clique times 2^-weak_bits (still exact in fp64).  The matrix keeps cond_2 <= COND_MAX (the node's
     couplings stay O(1), asserted by check_cond as for every matrix), but the static diagonal pivot there is tiny
     and the elimination grows by ~2^weak_bits: the unrefined static-order solves lose that many bits, one refinement
@@ -296,6 +385,16 @@ def make_operator(pat: Pattern, n_stiff=12, seed=0, dense_rhs=False, support=Non
     rhs = np.zeros(n)
     if dense_rhs:
         rhs[:] = 0.5 + rng.random(n)
+    elif isinstance(load, np.ndarray):
+        rhs[load] = 0.5 + rng.random(load.size)
+    elif load is not None:
+        comps = pat.components()
+        for k in load:
+            leaf_cliques, dirs = comps[k][:2]
+            for nodes in leaf_cliques[:2]:
+                rhs[nodes[:min(3, nodes.size)]] = 0.5 + rng.random(min(3, nodes.size))
+            if dirs.size:
+                rhs[dirs[0]] = 0.7
     else:
         for c in pat.leaves[:2]:
             nodes = pat.cliques[c]
@@ -800,21 +899,88 @@ GENERAL_SHAPES = {
 }
 
 
+# Forests: block-diagonal unions of the shapes above, for the views of pruning (include/pfr.h, pfr_set_prune: the trees
+# the load does not reach are left out of the sweeps' plan).  (components, pinned component): the analysis' ``last`` is
+# the pinned component's border.  The smallest unions whose views reach each launch class
+# (tests/test_synthetic_forest_cpu.py lists which).  G: a second fused-bottom-level shape beside F0.
+_G = lambda: clique_border((1, 2, 3, 4, 4), 6, n_dir=2, seed=1)      # noqa: E731
+FORESTS = {
+    "AC": (("A", "C"), 0),
+    "ETF0": (("E", "T", "F0"), 0),
+    "BFA4": (("B", "F", "A4"), 0),
+    "FA8": (("F", "A8"), 0),       # F first: without ``last`` its root amalgamates to 225 pivots
+    "F0F0": (("F0", "F0"), 0),
+    "F0T": (("F0", "T"), 0),
+    "F0G": (("F0", _G), 0),
+    "A4A4": (("A4", "A4"), 0),
+    "A8A8": (("A8", "A8"), 0),
+    "DA8T": (("D", "A8", "T"), 2),  # the pinned component not first in node order
+}
+
+
+# the loaded components of the GPU cases (tests/test_gpu_synthetic_prune.py), per forest
+FOREST_LOADS = {
+    "AC": ((0,), (1,)), "ETF0": ((0,), (1,), (2,)), "BFA4": ((0, 2),), "FA8": ((0,), (1,)), "F0F0": ((0,), (1,)),
+    "F0G": ((0,), (1,)), "A4A4": ((0,),), "A8A8": ((1,),), "DA8T": ((2,), (0,)),
+}
+FOREST_CASES = [(f, load) for f in FOREST_LOADS for load in FOREST_LOADS[f]]
+
+
+def forest_id(forest_name, load):
+    return forest_name + "-load" + "".join(str(k) for k in load)
+
+
+# the launch-knob variants of tests/test_gpu_synthetic.py::KNOBS on the forests that hold the matching shape
+_RL_ENVS = ({"PFR_US2_RL": "0"}, {"PFR_LS_RL": "0"}, {"PFR_US2_RL": "0", "PFR_LS_RL": "0"}, {"PFR_US2_NAR": "0"},
+            {"PFR_US2_NAR": "1000000000"})
+_WIDE_ENV = {"PFR_US2_NAR": "0", "PFR_SOLVE_SPLIT": "0"}
+FOREST_KNOBS = (
+    [("F0G", (0,), {"PFR_FRONT0": "0"})]
+    + [(f, load, e) for f, load in (("AC", (1,)), ("FA8", (0,))) for e in _RL_ENVS]
+    + [("AC", (0,), {"PFR_SCHUR_BLK_MIN": v}) for v in ("0", "4")]
+    + [(f, load, dict(_WIDE_ENV, **e)) for f, load in (("A4A4", (0,)), ("A8A8", (1,)))
+       for e in ({}, {"PFR_US2_TINY": "0"}, {"PFR_US2_TINY": "4"})]
+)
+
+
+def knob_id(forest_name, load, env):
+    return forest_id(forest_name, load) + "-" + ",".join(f"{k[4:]}={v}" for k, v in env.items())
+
+
 @functools.lru_cache(maxsize=None)
 def pattern(shape, general=False) -> Pattern:
+    if shape in FORESTS and not general:
+        parts, pin = FORESTS[shape]
+        return forest([SHAPES[p]() if isinstance(p, str) else p() for p in parts], pin=pin, name=shape)
     return (GENERAL_SHAPES if general else SHAPES)[shape]()
 
 
+def forest_support(pat: Pattern):
+    """Sensor rows on every component of a forest: three nodes of its border and the first node of its first leaf
+    clique (outside the root front)."""
+    return np.sort(np.concatenate([np.concatenate([border[[0, 2, 5]], leaf_cliques[0][:1]])
+                                   for leaf_cliques, _, border, _ in pat.components()]))
+
+
 @functools.lru_cache(maxsize=None)
-def case(shape, n_stiff=12, dense_rhs=False, spread=False, general=False, weak_bits=0):
-    """(pattern, operator) of a shape id; ``spread``: the functional support over two leaf cliques and the border
-    (for an analysis without ``last``)."""
+def case(shape, n_stiff=12, dense_rhs=False, spread=False, general=False, weak_bits=0, load=None, seed=0):
+    """(pattern, operator) of a shape or forest id; ``spread``: the functional support over two leaf cliques and the
+    border (for an analysis without ``last``); ``load``: a tuple of component indices of a forest (make_operator)."""
     pat = pattern(shape, general)
     support = None
     if spread:
         lv = pat.leaves
         support = np.concatenate([pat.cliques[lv[0]][:2], pat.cliques[lv[-1]][:2], pat.border[[0, 7, 19, 40]]])
-    return pat, make_operator(pat, n_stiff=n_stiff, dense_rhs=dense_rhs, support=support, weak_bits=weak_bits)
+    elif pat.parts:
+        support = forest_support(pat)
+    return pat, make_operator(pat, n_stiff=n_stiff, seed=seed, dense_rhs=dense_rhs, support=support,
+                              weak_bits=weak_bits, load=load)
+
+
+def component_rows(pat: Pattern, comps):
+    """The nodes (caller numbering) of the components ``comps`` of a forest."""
+    parts = pat.components()
+    return np.concatenate([parts[k][3] for k in comps]) if len(comps) else np.zeros(0, np.int64)
 
 
 @functools.lru_cache(maxsize=None)

@@ -23,9 +23,10 @@ COND_EVERY = 13        # check_cond on every 13th of the sweep's frequencies (10
 
 
 @functools.lru_cache(maxsize=None)
-def members(shape, n_members=3, n_stiff=12, seed=0):
-    """The base operator of ``sy.case(shape)`` and ``n_members`` member operators (a tuple)."""
-    _, op = sy.case(shape, n_stiff=n_stiff)
+def members(shape, n_members=3, n_stiff=12, seed=0, load=None):
+    """The base operator of ``sy.case(shape)`` (``load``: of a forest, the loaded components) and ``n_members`` member
+    operators (a tuple)."""
+    _, op = sy.case(shape, n_stiff=n_stiff, load=load)
     rng = np.random.default_rng(7000 + seed)
     out = []
     for p in range(n_members):

@@ -72,8 +72,9 @@ def _t(a, dtype=None):
 LOSS_ID = dict(_native.LOSS_IDS, NONE=_native.LOSS_NONE, COTANGENT=_native.LOSS_COTANGENT)
 
 
-def make_solver(op, sym, max_batch=64):
-    """A solver with the operator-form state of ``op`` set, as Problem._Engine sets it.  Returns (solver, K)."""
+def make_solver(op, sym, max_batch=64, prune=None):
+    """A solver with the operator-form state of ``op`` set, as Problem._Engine sets it.  Returns (solver, K).
+    ``prune``: pfr_set_prune with that value (None: never called, the C ABI's default -- off)."""
     sv = _native.Solver(sym, 0, max_batch)
     sv.set_stiffness(_t(op.S.T), op.e)                                        # (nnz, n_stiff)
     K = torch.empty(op.pat.nnz, dtype=torch.complex128, device=DEV)
@@ -81,6 +82,8 @@ def make_solver(op, sym, max_batch=64):
     sv.set_operator(torch.view_as_real(K), _t(op.M))
     sv.set_rhs(op.rhs, op.beta, op.mass_sum)
     sv.set_functional(op.sup, op.a3, op.ts)
+    if prune is not None:
+        sv.set_prune(prune)
     return sv, K
 
 

@@ -179,6 +179,45 @@ def test_view_takes_the_full_plan_launch_decisions(ortho):
                     assert np.array_equal(view[name][col][lv], full[name][col][lv]), (name, col)
 
 
+def _assert_views_agree(act, rest, full):
+    for view in (act, rest):
+        for name, skip in COUNTS.items():
+            lv = view[name]["nmax" if name == "chain" else "nf"] > 0
+            for col in view[name].dtype.names:
+                if col not in skip:
+                    assert np.array_equal(view[name][col][lv], full[name][col][lv]), (name, col)
+
+
+@pytest.mark.parametrize("forest", ["F0F0", "F0T"])
+@pytest.mark.parametrize("loaded", [0, 1])
+def test_fused_bottom_level_is_the_full_plans(forest, loaded):
+    """Forests of tests/synthetic.py whose first tree's leaves all fit the fused bottom level (k_front0) and whose second
+    tree's do not: the full plan does not fuse level 0, and neither view may, whichever tree the load is on -- the
+    bottom level is decided for the whole analysis, a view only lists its own fronts."""
+    import synthetic as sy
+    pat, op = sy.case(forest, load=(loaded,))
+    sym = sy.symbolic(forest)
+    for Fc in (64, FC):
+        mask, act, rest, full = sym.prune(Fc, op.rhs, op.sup)
+        assert 0 < mask.sum() < mask.size
+        assert not full["factor"]["fused0"].any()
+        assert not act["factor"]["fused0"].any() and not rest["factor"]["fused0"].any()
+        _assert_views_agree(act, rest, full)
+
+
+def test_deep_tree_takes_the_full_plan_launch_decisions(ortho):
+    """ny = 6 on the deep tree (leaf 10,000, tests/test_gpu_prune.py::test_views_with_empty_levels): the bending trees'
+    leaves all fit the fused bottom level, an in-plane leaf of 6 pivots does not -- no view fuses level 0."""
+    p, rows, cols, vals, *_ = ortho
+    colptr = np.zeros(p.mat_size + 1, np.int64)
+    np.add.at(colptr, cols.astype(np.int64) + 1, 1)
+    sym = _native.Symbolic(p.mat_size, np.cumsum(colptr).astype(np.int32), rows, leaf_size=10000, symmetric=True)
+    mask, act, rest, full = sym.prune(FC, p.vec, _support(p))
+    assert 0 < mask.sum() < mask.size and full["factor"]["maxns"][0] > 4
+    assert not full["factor"]["fused0"].any() and not act["factor"]["fused0"].any()
+    _assert_views_agree(act, rest, full)
+
+
 def test_rank_block_shape_takes_the_full_plan_launch_decisions():
     """C3 on the 512-frequency tree (leaf 2,000, chunk 512: C4's rank block), where the loaded trees' L21 item counts
     fall below the pipelined-prefix threshold on levels whose full counts do not: the prefix, like every other shape,
