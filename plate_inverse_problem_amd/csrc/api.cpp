@@ -5,7 +5,6 @@
 #include <algorithm>
 #include <array>
 #include <cmath>
-#include <functional>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -15,6 +14,7 @@
 using pfr::DevPattern;
 using pfr::Front;
 using pfr::Symbolic;
+using pfr::Walk;
 
 struct pfr_symbolic {
   Symbolic S;
@@ -349,14 +349,8 @@ void reset_timing(pfr_solver* s) { s->n_tev = 0; }
 // operators popK and the chunk's part of the table
 pfr::ChunkOp chunk_op(const pfr_solver* s, const double2* popK = nullptr, const pfr::PopArgs* pop = nullptr,
                       int64_t q0 = 0) {
-  pfr::ChunkOp op;
-  op.K = pop ? popK : s->K;
-  op.M = s->M;
-  op.freqs = s->freqs;
-  op.rhsP = s->rhsP;
-  op.beta_re = s->beta_re;
-  op.beta_im = s->beta_im;
-  op.mass_sum = s->mass_sum;
+  pfr::ChunkOp op{.K = pop ? popK : s->K, .M = s->M, .freqs = s->freqs, .rhsP = s->rhsP, .beta_re = s->beta_re,
+                 .beta_im = s->beta_im, .mass_sum = s->mass_sum};
   if (pop) {
     op.pop = *pop;
     op.pop.member += q0 / 64;
@@ -366,18 +360,14 @@ pfr::ChunkOp chunk_op(const pfr_solver* s, const double2* popK = nullptr, const 
 
 // kernel right-hand sides: the operator's (RHS 0) and a permuted vector (RHS 2)
 pfr::RhsArgs rhs_operator(const pfr::ChunkOp& op) {
-  pfr::RhsArgs r;
-  r.rhsP = op.rhsP;
-  r.beta_re = op.beta_re;
-  r.beta_im = op.beta_im;
-  r.mass_sum = op.mass_sum;
-  r.freqs = op.freqs;
-  return r;
+  return {.rhsP = op.rhsP, .beta_re = op.beta_re, .beta_im = op.beta_im, .mass_sum = op.mass_sum, .freqs = op.freqs};
 }
-pfr::RhsArgs rhs_vector(const double2* G) {
-  pfr::RhsArgs r;
-  r.G = G;
-  return r;
+pfr::RhsArgs rhs_vector(const double2* G) { return {.G = G}; }
+
+// pruning (pfr_set_prune): the operator-form sweeps walk the loaded trees' view; the refinement modes keep the full
+// one (their corrections solve right-hand sides that are not the operator's)
+bool sweeps_pruned(const pfr_solver* s) {
+  return s->act && !(s->check_mode & (PFR_CHECK_REFINE | PFR_CHECK_REFINE_ADJ));
 }
 
 // bytes of a host table to the device on stream st (stage slot `slot`); *dev: the device copy
@@ -406,8 +396,8 @@ int stage_upload(pfr_solver* s, int slot, const void* src, size_t bytes, void** 
 }
 
 // v (here and below): the view whose fronts the pass walks -- *s for every front
-int factor_all(pfr_solver* s, const SolverView& v, const pfr::ChunkOp& op, int mode, const double2* data, int64_t ds,
-               int nvalid, hipStream_t st) {
+int factor_all(pfr_solver* s, const SolverView& v, const pfr::ChunkOp& op, pfr::Mat mode, const double2* data,
+               int64_t ds, int nvalid, hipStream_t st) {
   const int L = (int)s->level_ptr.size() - 1;
   const int ngroups = (int)(s->Fc / 64);
   const bool kt = (s->timing & 2) && s->n_tev < (int)s->tev.size() && !s->tev[s->n_tev].kev.empty();
@@ -420,7 +410,7 @@ int factor_all(pfr_solver* s, const SolverView& v, const pfr::ChunkOp& op, int m
     const pfr::FactorLevel& r = v.sched.factor[l];
     const int32_t* lvl = v.d_level_fronts + v.level_ptr[l];
     mark(l, 0);
-    if (r.fused0 && mode == 0) {
+    if (r.fused0 && mode == pfr::MAT_OPERATOR) {
       if (kt) s->tev[s->n_tev].f0 = true;
       // the bottom level's leaf fronts in one pass (k_front0): A11, L21 and update block per frequency in registers
       pfr::launch_front0(s->P, v.d_f0_front, r, v.d_f0_ptr, v.d_f0_nz, ngroups, s->F, s->Fc, op, s->flags, st);
@@ -451,14 +441,15 @@ int factor_all(pfr_solver* s, const SolverView& v, const pfr::ChunkOp& op, int m
   return PFR_OK;
 }
 
-// which: 0 L, 1 U, 2 U^T, 3 L^T ; bottom-up for 0/2, top-down for 1/3
-// subset (0 forward rhs, 1 loss adjoint, -1 none): bottom-up passes visit only the reached
+// one triangular pass (pfr::Tri): bottom-up for L and U^T, top-down for U and L^T
+// subset (the rhs reach, the support's, or every front): bottom-up passes visit only the reached
 // fronts; top-down passes treat the pivot values of unreached fronts as zero
-int solve_all(pfr_solver* s, const SolverView& v, const pfr::ChunkOp& op, int which, int rhs_mode, const pfr::RhsArgs& rd,
-              const double2* Yin, double2* Out, hipStream_t st, int subset = -1, const int* glist = nullptr) {
+int solve_all(pfr_solver* s, const SolverView& v, const pfr::ChunkOp& op, pfr::Tri which, pfr::Rhs rhs_mode,
+              const pfr::RhsArgs& rd, const double2* Yin, double2* Out, hipStream_t st, pfr::Reach subset = pfr::REACH_ALL,
+              const int* glist = nullptr) {
   const int L = (int)s->level_ptr.size() - 1;
   const int ngroups = glist ? pfr::REFINE_CAP : (int)(s->Fc / 64);
-  const bool up = (which == 0 || which == 2);
+  const bool up = (which == pfr::TRI_L || which == pfr::TRI_UT);
   const int* reach = subset >= 0 ? v.d_reach[subset] : nullptr;
   for (int t = 0; t < L; ++t) {
     int l = up ? t : L - 1 - t;
@@ -474,17 +465,8 @@ int solve_all(pfr_solver* s, const SolverView& v, const pfr::ChunkOp& op, int wh
 }
 
 pfr::DirArgs dir_desc(const pfr_solver* s, const pfr::ChunkOp& op) {
-  pfr::DirArgs d;
-  d.dir = s->d_dir;
-  d.crow = s->d_crow;
-  d.cptr = s->d_cptr_dir;
-  d.ce = s->d_ce;
-  d.dptr = s->d_dptr;
-  d.de = s->d_de;
-  d.K = op.K;
-  d.M = op.M;
-  d.freqs = op.freqs;
-  return d;
+  return {.dir = s->d_dir, .crow = s->d_crow, .cptr = s->d_cptr_dir, .ce = s->d_ce, .dptr = s->d_dptr, .de = s->d_de,
+          .K = op.K, .M = op.M, .freqs = op.freqs};
 }
 // the adjoint's Dirichlet rows (k_dirichlet_post) over the nodes on the view's fronts
 pfr::DirArgs post_desc(const pfr_solver* s, const SolverView& v, const pfr::ChunkOp& op) {
@@ -495,41 +477,41 @@ pfr::DirArgs post_desc(const pfr_solver* s, const SolverView& v, const pfr::Chun
   return d;
 }
 
-// A x = b on the chunk's factors, x -> Out (permuted).  rhs_mode 0: operator right-hand side
-// (rd.rhsP ...); 2: vector rd.G (overwritten in symmetric mode).  Symmetric mode: Dirichlet
+// A x = b on the chunk's factors, x -> Out (permuted).  RHS_OPERATOR: operator right-hand side
+// (rd.rhsP ...); RHS_VECTOR: vector rd.G (overwritten in symmetric mode).  Symmetric mode: Dirichlet
 // columns moved to the right-hand side first, then L and U = diag(U) L^T.
-int forward_solve(pfr_solver* s, const SolverView& v, const pfr::ChunkOp& op, int rhs_mode, pfr::RhsArgs rd, double2* Out,
-                  hipStream_t st, int subset = -1) {
+int forward_solve(pfr_solver* s, const SolverView& v, const pfr::ChunkOp& op, pfr::Rhs rhs_mode, pfr::RhsArgs rd,
+                  double2* Out, hipStream_t st, pfr::Reach subset = pfr::REACH_ALL) {
   int rc;
   if (s->sym) {
     const pfr::DirArgs dd = dir_desc(s, op);
-    if (rhs_mode == 0) {
-      pfr::launch_dirichlet_rhs(0, dd, op.pop, s->n_crow, rd, nullptr, s->Bc, s->Fc, st);
+    if (rhs_mode == pfr::RHS_OPERATOR) {
+      pfr::launch_dirichlet_rhs(pfr::RHS_OPERATOR, dd, op.pop, s->n_crow, rd, nullptr, s->Bc, s->Fc, st);
       rd.cslot = s->d_cslot;
       rd.Bc = s->Bc;
-      if (s->n_crow > 0) rhs_mode = 3;
+      if (s->n_crow > 0) rhs_mode = pfr::RHS_OPERATOR_DIR;
     } else {
-      pfr::launch_dirichlet_rhs(2, dd, op.pop, s->n_crow, rd, const_cast<double2*>(rd.G), nullptr, s->Fc, st);
+      pfr::launch_dirichlet_rhs(pfr::RHS_VECTOR, dd, op.pop, s->n_crow, rd, const_cast<double2*>(rd.G), nullptr, s->Fc, st);
     }
   }
-  if ((rc = solve_all(s, v, op, 0, rhs_mode, rd, nullptr, s->Y, st, subset))) return rc;
-  return solve_all(s, v, op, 1, 0, rd, s->Y, Out, st, subset);
+  if ((rc = solve_all(s, v, op, pfr::TRI_L, rhs_mode, rd, nullptr, s->Y, st, subset))) return rc;
+  return solve_all(s, v, op, pfr::TRI_U, pfr::RHS_OPERATOR, rd, s->Y, Out, st, subset);
 }
 
 // A^T l = g (g = rg.G, permuted), l -> Out.  Symmetric mode: the decoupled matrix is symmetric,
 // so L and U = diag(U) L^T again, then the Dirichlet rows of l are corrected.
 int adjoint_solve(pfr_solver* s, const SolverView& v, const pfr::ChunkOp& op, const pfr::RhsArgs& rg, double2* Out,
-                  hipStream_t st, int subset = -1, const int* glist = nullptr) {
+                  hipStream_t st, pfr::Reach subset = pfr::REACH_ALL, const int* glist = nullptr) {
   int rc;
   if (s->sym) {
-    if ((rc = solve_all(s, v, op, 0, 2, rg, nullptr, s->Y, st, subset, glist)) ||
-        (rc = solve_all(s, v, op, 1, 0, rg, s->Y, Out, st, subset, glist)))
+    if ((rc = solve_all(s, v, op, pfr::TRI_L, pfr::RHS_VECTOR, rg, nullptr, s->Y, st, subset, glist)) ||
+        (rc = solve_all(s, v, op, pfr::TRI_U, pfr::RHS_OPERATOR, rg, s->Y, Out, st, subset, glist)))
       return rc;
     pfr::launch_dirichlet_post(post_desc(s, v, op), op.pop, v.post_n, Out, s->Fc, st, glist);
     return PFR_OK;
   }
-  if ((rc = solve_all(s, v, op, 2, 2, rg, nullptr, s->Y, st, subset))) return rc;
-  return solve_all(s, v, op, 3, 0, rg, s->Y, Out, st, subset);
+  if ((rc = solve_all(s, v, op, pfr::TRI_UT, pfr::RHS_VECTOR, rg, nullptr, s->Y, st, subset))) return rc;
+  return solve_all(s, v, op, pfr::TRI_LT, pfr::RHS_OPERATOR, rg, s->Y, Out, st, subset);
 }
 
 // Row lists and buffers of the functional-from-bottom-up path (allocated on first use, lists rebuilt
@@ -575,7 +557,7 @@ int fn_setup(pfr_solver* s, SolverView& v) {
 
 // forward bottom-up over the rhs reach (slice 0) and L w_k = a_k over the support reach (slices 1-3),
 // one launch chain
-int fn_bottom_up(pfr_solver* s, const SolverView& v, const pfr::ChunkOp& op, int rhs_mode, const pfr::RhsArgs& rf,
+int fn_bottom_up(pfr_solver* s, const SolverView& v, const pfr::ChunkOp& op, pfr::Rhs rhs_mode, const pfr::RhsArgs& rf,
                  hipStream_t st) {
   const int L = (int)s->level_ptr.size() - 1;
   const int ngroups = (int)(s->Fc / 64);
@@ -609,8 +591,9 @@ int sym_top_down_support(pfr_solver* s, const SolverView& v, hipStream_t st) {
   const int L = (int)s->level_ptr.size() - 1;
   const int ngroups = (int)(s->Fc / 64);
   for (int l = L - 1; l >= 0; --l) {
-    pfr::launch_solve(1, 0, true, s->P, v.d_reach_fronts[1] + v.reach_ptr[1][l], v.sched.solve[pfr::SUBSET_REACH1][l],
-                      ngroups, s->F, s->Fc, s->WV, pfr::RhsArgs(), pfr::PopArgs(), s->Y, s->X, v.d_reach[0], st);
+    pfr::launch_solve(pfr::TRI_U, pfr::RHS_OPERATOR, true, s->P, v.d_reach_fronts[1] + v.reach_ptr[1][l],
+                      v.sched.solve[pfr::SUBSET_REACH1][l], ngroups, s->F, s->Fc, s->WV, pfr::RhsArgs(), pfr::PopArgs(), s->Y,
+                      s->X, v.d_reach[0], st);
   }
   LAUNCH_TRY();
   return PFR_OK;
@@ -644,52 +627,25 @@ int set_reach(pfr_solver* s, SolverView& v, int which, const std::vector<int32_t
   return PFR_OK;
 }
 
-// Backward error of the solution X (permuted, frequency-minor) of the original system (which = 0:
-// A x = b over the rows, 1: A^T l = g over the columns); mode 0 operator form, 1 explicit batch
-// (data, ds, nvalid); rhs as launch_residual (0 operator, 1 explicit B, 2 vector G).  Sets the
-// chunk's flags and the caller's berr slots (q0 < 0: no berr output).  R != NULL: only the residual
-// b - A x is written there (the refinement step), nothing is checked.
-void check_solution(pfr_solver* s, const SolverView& v, const pfr::ChunkOp& op, int which, int mode, int rhs, const pfr::RhsArgs& rd,
-                    const double2* data, int64_t ds, int nvalid, const double2* X, double2* R, int64_t q0, hipStream_t st,
-                    const double2* Mu = nullptr, bool check = true, bool contract = false, const int* glist = nullptr) {
-  pfr::ResidArgs d;
-  d.ptr = which == 0 ? s->d_rptr : s->d_cptr;
-  d.idx = which == 0 ? s->d_ridx : s->d_cidx;
-  d.nzs = which == 0 ? s->d_rnz : s->d_cnz;
-  d.n = s->n;
-  d.K = op.K;
-  d.M = op.M;
-  d.freqs = op.freqs;
-  d.data = data;
-  d.data_stride = ds;
-  d.nvalid = nvalid;
-  d.rhsP = rd.rhsP;
-  d.beta_re = rd.beta_re;
-  d.beta_im = rd.beta_im;
-  d.mass_sum = rd.mass_sum;
-  d.B = rd.B;
-  d.b_stride = rd.b_stride;
-  d.perm = s->P.perm;
-  d.G = rd.G;
-  d.walk = v.d_walk;
-  d.glist = glist;
-  if (contract) {   // the gradient contraction fused into the forward walk: stiffness values nz-major, kpart out
-    d.se = s->stiff;
-    d.kpart = s->kpart;
-  }
-  const int n_stiff = contract ? s->n_stiff : 0;
-  if (R) {   // refinement residual only: no maxima, no flags
-    pfr::launch_residual(mode, rhs, d, n_stiff, s->res_unroll, op.pop, X, s->Fc, R, nullptr, st);
-    return;
-  }
-  // Mu: the forward walk also accumulates the functional correction's dot products (s->cpart);
-  // check = false: only those (no backward error)
-  pfr::launch_residual(mode, rhs, d, n_stiff, s->res_unroll, op.pop, X, s->Fc, nullptr, check ? s->d_berr_acc : nullptr,
-                       st, Mu, Mu ? s->cpart : nullptr);
-  if (!check) return;
+// a residual walk (launch.hpp): a checked one finishes into the chunk's flags and the caller's berr slots, the correction's
+// dot products go to s->cpart, the fused contraction to s->kpart (a walk into R has neither: no maxima, no flags)
+void run_walk(pfr_solver* s, const SolverView& v, const pfr::ChunkOp& op, const Walk& w, int nvalid, hipStream_t st) {
+  const bool fwd = w.sys == Walk::FORWARD;
+  // w.contract: the gradient contraction fused into the forward walk -- stiffness values nz-major, kpart out
+  const pfr::ResidArgs d{.ptr = fwd ? s->d_rptr : s->d_cptr, .idx = fwd ? s->d_ridx : s->d_cidx,
+                         .nzs = fwd ? s->d_rnz : s->d_cnz, .n = s->n, .K = op.K, .M = op.M, .freqs = op.freqs,
+                         .data = w.data, .data_stride = w.ds, .nvalid = nvalid, .rhsP = w.rd.rhsP,
+                         .beta_re = w.rd.beta_re, .beta_im = w.rd.beta_im, .mass_sum = w.rd.mass_sum, .B = w.rd.B,
+                         .b_stride = w.rd.b_stride, .perm = s->P.perm, .G = w.rd.G, .walk = v.d_walk,
+                         .se = w.contract ? s->stiff : nullptr, .kpart = w.contract ? s->kpart : nullptr,
+                         .glist = w.glist};
+  const int n_stiff = w.contract ? s->n_stiff : 0;
+  pfr::launch_residual(w.mat, w.rhs, d, n_stiff, s->res_unroll, op.pop, w.X, s->Fc, w.R, w.check ? s->d_berr_acc : nullptr,
+                       st, w.Mu, w.Mu ? s->cpart : nullptr);
+  if (!w.check) return;
   pfr::launch_berr_finish(s->d_berr_acc, s->Fc, nvalid, s->check_tol,
-                          which == 0 ? PFR_FLAG_BACKWARD_ERROR : PFR_FLAG_BACKWARD_ERROR_ADJ, s->flags,
-                          q0 >= 0 ? s->berr_out : nullptr, q0, which, st);
+                          fwd ? PFR_FLAG_BACKWARD_ERROR : PFR_FLAG_BACKWARD_ERROR_ADJ, s->flags,
+                          w.q0 >= 0 ? s->berr_out : nullptr, w.q0, w.sys, st);
 }
 
 // s_{q,k} partials of sum_nz S_k(nz) lam[row] x[col] over the union pattern's distinct entries
@@ -1195,8 +1151,8 @@ int complete_adjoint(pfr_solver* s) {
   }
   const int timing = s->timing;
   s->timing = 0;
-  rc = factor_all(s, *s->comp, s->last_op, 0, nullptr, 0, (int)s->Fc, s->last_st);
-  if (rc == PFR_OK) rc = adjoint_solve(s, *s->comp, s->last_op, rhs_vector(s->G), s->XA, s->last_st, 1);
+  rc = factor_all(s, *s->comp, s->last_op, pfr::MAT_OPERATOR, nullptr, 0, (int)s->Fc, s->last_st);
+  if (rc == PFR_OK) rc = adjoint_solve(s, *s->comp, s->last_op, rhs_vector(s->G), s->XA, s->last_st, pfr::REACH_SUPPORT);
   s->timing = timing;
   s->comp_done = true;
   s->unl_dirty = true;
@@ -1283,10 +1239,8 @@ int pfr_last_kernel_timings(const pfr_solver* s, double* ms, int64_t* launches) 
 int pfr_solver_alg_bytes(const pfr_solver* s, int64_t* bytes) {
   if (!s || !bytes) return fail(PFR_ERR_ARG, "null argument");
   for (int i = 0; i < pfr::NKC; ++i) bytes[i] = 0;
-  // what the operator-form sweeps launch under the current check mode (the refinement modes keep the full plan)
-  const SolverView& v = s->act && !(s->check_mode & (PFR_CHECK_REFINE | PFR_CHECK_REFINE_ADJ))
-                            ? *s->act
-                            : static_cast<const SolverView&>(*s);
+  // what the operator-form sweeps launch under the current check mode
+  const SolverView& v = sweeps_pruned(s) ? *s->act : static_cast<const SolverView&>(*s);
   for (int l = 0; l + 1 < (int)s->level_ptr.size(); ++l)
     for (int i = 0; i < pfr::NKC; ++i) bytes[i] += v.lev_bytes[l][i];
   return PFR_OK;
@@ -1298,10 +1252,7 @@ int pfr_solver_solve_bytes(const pfr_solver* s, int64_t* bytes) {
   // bottom-up pass of rhs w), upper_r[w] = U11 + U12 of those fronts, upper / lower_all = every front
   int64_t lower[2] = {0, 0}, upper_r[2] = {0, 0}, upper = 0, lower_all = 0, lower_union = 0, sup_rows = 0;
   const bool refine = (s->check_mode & PFR_CHECK_REFINE) != 0;
-  // the fronts the sweeps walk: the loaded trees under pruning (the refinement modes keep the full view)
-  const SolverView& v = s->act && !(s->check_mode & (PFR_CHECK_REFINE | PFR_CHECK_REFINE_ADJ))
-                            ? *s->act
-                            : static_cast<const SolverView&>(*s);
+  const SolverView& v = sweeps_pruned(s) ? *s->act : static_cast<const SolverView&>(*s);   // the fronts the sweeps walk
   int64_t nrows = 0;
   for (size_t t = 0; t < s->front_ns.size(); ++t) {
     if (!v.active[t]) continue;
@@ -1478,234 +1429,302 @@ int pfr_set_functional(pfr_solver* s, int32_t n_support, const int32_t* index, c
 
 namespace {
 // What a sweep senses: the magnitude fr (the default) or the complex response H along a real axis (pfr_sweep_complex).
-// A value of the call, never solver state: sweep_launches writes it into the chunk's FunctionalArgs.
+// A value of the call, never solver state: functional_args writes it into the sweep's FunctionalArgs.
 struct Response {
   bool cpx = false;
   double axis[3] = {0.0, 0.0, 1.0};
 };
 
-// The launches of one sweep (pfr_sweep after its argument checks), direct or under stream capture.
-// jc_dev != NULL (pfr_jacobian_sweep; loss_type = pfr::LOSS_UNIT, scale 1, no ref / loss / w): the reverse sweep of
-// a unit cotangent per frequency whose contraction stays per frequency -- the walk's kpart (or k_contract_q's, where
-// the walk has not formed it) finished by k_jac_finish into the rows of jc instead of k_reduce_q / k_contract_eg +
-// k_reduce into w.
-// pop != NULL (pfr_population_sweep): lane group g of the sweep belongs to pop->member[g] and reads the operator
-// popK + pop->member[g] * pop->nnz (chunk_op).
-// resp.cpx (pfr_sweep_complex / pfr_jacobian_sweep_complex): fr_dev holds complex H, loss_type is a PFR_LOSS_C* id,
-// pfr::LOSS_UNIT or PFR_LOSS_NONE, and the functional kernels run in their CPX forms (seed kept in s->h0); every
+// What one sweep call asks for: every pfr_*sweep* entry point fills one after its argument checks.
+// jc != NULL (the Jacobian forms; loss_type = pfr::LOSS_UNIT, scale 1, no ref / loss / w): the reverse sweep of a unit
+// cotangent per frequency whose contraction stays per frequency -- the walk's kpart (or k_contract_q's, where the walk
+// has not formed it) finished by k_jac_finish into the rows of jc instead of k_reduce_q / k_contract_eg + k_reduce into w.
+// pop.member != NULL (pfr_population_sweep): lane group g belongs to pop.member[g] and reads the operator popK +
+// pop.member[g] * pop.nnz (chunk_op).  resp.cpx (the complex sweeps): response holds complex H, loss_type is a PFR_LOSS_C*
+// id, pfr::LOSS_UNIT or PFR_LOSS_NONE, and the functional kernels run in their CPX forms (seed kept in s->h0); every
 // launch after them takes G, fcoef and mscale as it does for the magnitude.
-int sweep_launches(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_t loss_type, const double* ref_dev,
-                   double scale, double* fr_dev, double* loss_dev, double* w_dev, int32_t* flags_dev, hipStream_t st,
-                   bool fresh, double2* jc_dev = nullptr, const double2* popK = nullptr,
-                   const pfr::PopArgs* pop = nullptr, const Response& resp = Response{}) {
-  const bool reverse = loss_type != PFR_LOSS_NONE;
-  double* const fr_out = resp.cpx ? nullptr : fr_dev;
-  const bool jac = jc_dev != nullptr;
-  reset_timing(s);
-  const int64_t Fc = s->Fc;
-  const bool refine = (s->check_mode & PFR_CHECK_REFINE) != 0;
-  // functional correction: the adjoint of fr is solved in every sweep (in a loss sweep it IS the loss
-  // adjoint up to one scalar per frequency) and the forward residual walk adds Re(mu^T r) to fr
-  const bool correct = (s->check_mode & PFR_CHECK_CORRECT) != 0;
-  const bool adj = reverse || correct;                 // an adjoint solve runs
-  const bool paired = s->sym && adj && !refine;        // one top-down pass for both solutions
-  const bool fwd_late = paired || correct;             // forward residual walk after the adjoint
-  const bool fn_fast = paired && s->fn_dot;            // functional from the bottom-up passes
-  // pruning (pfr_set_prune): the loaded trees' view; the refinement modes keep the full one (their corrections solve
-  // right-hand sides that are not the operator's)
-  const bool pruned = s->act && !(s->check_mode & (PFR_CHECK_REFINE | PFR_CHECK_REFINE_ADJ));
-  SolverView& v = pruned ? *s->act : static_cast<SolverView&>(*s);
-  if (pruned && s->unl_dirty) {   // rows of the unloaded trees: exact zeros, written here and by no pruned sweep
+struct SweepSpec {
+  int32_t nfreq = 0;
+  const double* freqs = nullptr;
+  int32_t loss_type = PFR_LOSS_NONE;
+  const double* ref = nullptr;
+  double scale = 1.0;
+  double* response = nullptr;           // fr per frequency, or the complex H (resp.cpx)
+  double *loss = nullptr, *w = nullptr;
+  double2* jc = nullptr;
+  int32_t* flags = nullptr;
+  bool fresh = false;                   // the caller's outputs initialised by the first chunk (pfr_sweep_fresh)
+  const double2* popK = nullptr;
+  pfr::PopArgs pop;
+  Response resp;
+  double* fr() const { return resp.cpx ? nullptr : response; }   // where the magnitude kernels write fr
+};
+
+// Every control-flow decision of a sweep, made once before the chunk loop (sweep_passes); the phases derive none
+struct SweepPasses {
+  bool reverse = false;      // a loss (or unit) cotangent is pulled back
+  bool correct = false;      // functional correction: the adjoint of fr is solved in every sweep (in a loss sweep it IS
+                             // the loss adjoint up to one scalar per frequency) and the forward walk adds Re(mu^T r) to fr
+  bool adj = false;          // an adjoint solve runs
+  bool refine = false;       // one refinement step of each solve (PFR_CHECK_REFINE)
+  bool paired = false;       // one top-down pass for both solutions
+  bool fwd_late = false;     // forward residual walk after the adjoint
+  bool fn_fast = false;      // functional from the bottom-up passes
+  bool pruned = false;       // on the loaded trees' view (sweeps_pruned)
+  bool jac = false;          // the contraction stays per frequency (spec.jc)
+  bool cwalk = false;        // the gradient contraction rides on the forward residual walk (loss sweeps with the correction)
+  bool refine_adj = false;   // selective adjoint refinement of the groups next to a resonance (PFR_CHECK_REFINE_ADJ)
+  bool scorr = false;        // the solve-error scale of the cotangent (k_correct_finish): t_q = mu^T rhsP in, m_q t_q out
+  // the backward-error checks: forward -- after the forward solve, on the correction walk or after the adjoint -- and adjoint
+  bool check_fwd_early = false, check_fwd_walk = false, check_fwd_after = false, check_adj = false;
+};
+
+SweepPasses sweep_passes(const pfr_solver* s, const SweepSpec& sp) {
+  SweepPasses p;
+  p.reverse = sp.loss_type != PFR_LOSS_NONE;
+  p.jac = sp.jc != nullptr;
+  p.refine = (s->check_mode & PFR_CHECK_REFINE) != 0;
+  p.correct = (s->check_mode & PFR_CHECK_CORRECT) != 0;
+  p.adj = p.reverse || p.correct;
+  p.paired = s->sym && p.adj && !p.refine;
+  p.fwd_late = p.paired || p.correct;
+  p.fn_fast = p.paired && s->fn_dot;
+  p.pruned = sweeps_pruned(s);
+  p.cwalk = p.reverse && p.correct && s->contract_walk && (s->n_stiff == 12 || s->n_stiff == 18);
+  p.refine_adj =
+      p.reverse && p.correct && p.cwalk && p.fn_fast && !sp.resp.cpx && (s->check_mode & PFR_CHECK_REFINE_ADJ);
+  p.scorr = p.reverse && p.correct && s->scale_corr;
+  const bool want_f = p.fwd_late && (s->check_mode & PFR_CHECK_FORWARD);
+  p.check_fwd_early = !p.paired && !p.fwd_late && (s->check_mode & PFR_CHECK_FORWARD);
+  p.check_fwd_walk = want_f && p.correct;
+  p.check_fwd_after = want_f && !p.correct;
+  p.check_adj = p.adj && (s->check_mode & PFR_CHECK_ADJOINT) != 0;
+  return p;
+}
+
+// One chunk of a sweep: first frequency, count, stream, the operator's right-hand side, the functional the call asks for
+struct Chunk {
+  int64_t q0 = 0;
+  int nv = 0;
+  hipStream_t st = nullptr;
+  pfr::RhsArgs rd;
+  pfr::FunctionalArgs fa{};
+};
+
+pfr::FunctionalArgs functional_args(const pfr_solver* s, const SweepSpec& sp) {
+  pfr::FunctionalArgs fa = s->fn;
+  fa.loss_type = sp.loss_type != PFR_LOSS_NONE ? sp.loss_type : -1;
+  fa.ref = reinterpret_cast<const double2*>(sp.ref);
+  fa.scale = sp.scale;
+  if (sp.resp.cpx) {
+    fa.cpx = 1;
+    std::copy(sp.resp.axis, sp.resp.axis + 3, fa.axis);
+    fa.h_out = reinterpret_cast<double2*>(sp.response);
+  }
+  return fa;
+}
+// seed mode of the functional kernels: the response of this solve kept for k_correct_finish
+pfr::FunctionalArgs seeded(const pfr_solver* s, pfr::FunctionalArgs f) {
+  f.cpx ? (void)(f.h0 = s->h0) : (void)(f.fr0 = s->fr0);
+  return f;
+}
+
+// The view a call walks, and the unloaded trees' rows of X / XA: zeroed here, kept by pruned sweeps, dirty after others
+SolverView& begin_on_view(pfr_solver* s, bool pruned, hipStream_t st) {
+  if (pruned && s->unl_dirty) {
     for (const auto& r : s->unl_rows) {
-      pfr::launch_zero(s->X + (int64_t)r.first * Fc, (int64_t)(r.second - r.first) * Fc, st);
-      pfr::launch_zero(s->XA + (int64_t)r.first * Fc, (int64_t)(r.second - r.first) * Fc, st);
+      pfr::launch_zero(s->X + (int64_t)r.first * s->Fc, (int64_t)(r.second - r.first) * s->Fc, st);
+      pfr::launch_zero(s->XA + (int64_t)r.first * s->Fc, (int64_t)(r.second - r.first) * s->Fc, st);
     }
     s->unl_dirty = false;
   } else if (!pruned && s->act) {
     s->unl_dirty = true;
   }
   s->last_pruned = pruned;
-  s->last_adj = adj;
-  s->last_st = st;
-  if (fn_fast)
-    if (int rc0 = fn_setup(s, v)) return rc0;
-  if (resp.cpx && correct && !s->h0)
-    if (int rc0 = s->alloc(&s->h0, Fc)) return rc0;
-  // seed mode of the functional kernels: the response of this solve kept for k_correct_finish
-  auto seed = [&](pfr::FunctionalArgs& f) { resp.cpx ? (void)(f.h0 = s->h0) : (void)(f.fr0 = s->fr0); };
-  bool used[5] = {true, true, true, adj, adj};
-  for (int64_t q0 = 0; q0 < nfreq; q0 += Fc) {
-    const int nv = (int)std::min<int64_t>(Fc, nfreq - q0);
-    if (fresh && q0 == 0)      // the caller's outputs initialised here (pfr_sweep_fresh)
-      pfr::launch_chunk_start(s->freqs, freqs_dev + q0, nv, Fc, s->flags, st, loss_dev, w_dev,
-                              reverse && w_dev ? 2 * s->n_stiff : 0, flags_dev, s->berr_out, nfreq);
+  return pruned ? *s->act : static_cast<SolverView&>(*s);
+}
+
+// The phases of one chunk, split at the timing records.  The factorisation (paired: the operator rhs's Dirichlet move first):
+int phase_factor(pfr_solver* s, SolverView& v, const pfr::ChunkOp& op, const SweepPasses& ps, const SweepSpec&,
+                 const Chunk& c) {
+  if (ps.paired)
+    pfr::launch_dirichlet_rhs(pfr::RHS_OPERATOR, dir_desc(s, op), op.pop, s->n_crow, c.rd, nullptr, s->Bc, s->Fc, c.st);
+  return factor_all(s, v, op, pfr::MAT_OPERATOR, nullptr, 0, c.nv, c.st);
+}
+
+// The forward solve.  Paired (symmetric mode with an adjoint): the bottom-up pass and the top-down pass only over the loss
+// support's fronts -- one combined top-down pass follows (sym_top_down_pair); otherwise the full forward solve
+int phase_forward(pfr_solver* s, SolverView& v, const pfr::ChunkOp& op, const SweepPasses& ps, const SweepSpec&,
+                  const Chunk& c) {
+  int rc;
+  if (ps.paired) {
+    const pfr::Rhs rhs = s->n_crow > 0 ? pfr::RHS_OPERATOR_DIR : pfr::RHS_OPERATOR;
+    pfr::RhsArgs rf = c.rd;   // the operator's, with the Dirichlet corrections (phase_factor) in their slots
+    rf.cslot = s->d_cslot;
+    rf.Bc = s->Bc;
+    if (ps.fn_fast) return fn_bottom_up(s, v, op, rhs, rf, c.st);
+    if ((rc = solve_all(s, v, op, pfr::TRI_L, rhs, rf, nullptr, s->Y, c.st, pfr::REACH_RHS))) return rc;
+    return sym_top_down_support(s, v, c.st);
+  }
+  if ((rc = forward_solve(s, v, op, pfr::RHS_OPERATOR, c.rd, s->X, c.st, pfr::REACH_RHS))) return rc;
+  if (ps.refine) {
+    // one refinement step on the same factors: r = b - A x (into G), A d = r (into XA), x += d
+    run_walk(s, v, op, Walk::residual(Walk::FORWARD, pfr::RHS_OPERATOR, c.rd, s->X, s->G), c.nv, c.st);
+    if ((rc = forward_solve(s, v, op, pfr::RHS_VECTOR, rhs_vector(s->G), s->XA, c.st))) return rc;
+    pfr::launch_axpy_vec(s->X, s->XA, (int64_t)s->n * s->Fc, c.st);
+  }
+  if (ps.check_fwd_early)
+    run_walk(s, v, op, Walk::checked(Walk::FORWARD, pfr::RHS_OPERATOR, c.rd, s->X, c.q0), c.nv, c.st);
+  return PFR_OK;
+}
+
+void phase_functional(pfr_solver* s, SolverView& v, const pfr::ChunkOp&, const SweepPasses& ps, const SweepSpec& sp,
+                      const Chunk& c) {
+  const int64_t Fc = s->Fc;
+  if (ps.adj) pfr::launch_zero(s->G, (int64_t)s->n * Fc, c.st);
+  if (ps.fn_fast) {
+    const double2* Yk[3] = {s->Y2, s->YVk, s->YVk + (int64_t)s->n * Fc};
+    pfr::launch_fn_dot(v.d_fn_rows, v.n_fn_rows, s->F, s->Y, Yk, Fc, s->fn_parts, c.st);
+    pfr::launch_functional_fn(ps.correct ? seeded(s, c.fa) : c.fa, s->fn_parts, Fc, c.nv, c.q0,
+                              ps.correct ? nullptr : sp.fr(), ps.correct ? nullptr : s->loss_terms, s->G, s->fcoef, c.st);
+  } else if (ps.correct) {   // fr of this solve kept, G = d fr / d x
+    pfr::launch_functional(seeded(s, c.fa), s->X, Fc, c.nv, c.q0, nullptr, nullptr, s->G, c.st);
+  } else {
+    pfr::launch_functional(c.fa, s->X, Fc, c.nv, c.q0, sp.fr(), s->loss_terms, s->G, c.st);
+  }
+}
+
+// the adjoint for the seed in G (ps.adj)
+int phase_adjoint(pfr_solver* s, SolverView& v, const pfr::ChunkOp& op, const SweepPasses& ps, const SweepSpec&,
+                  const Chunk& c) {
+  int rc;
+  const int64_t Fc = s->Fc;
+  const pfr::RhsArgs rg = rhs_vector(s->G);
+  if (ps.fn_fast) {
+    double2* Yk[3] = {s->Y2, s->YVk, s->YVk + (int64_t)s->n * Fc};
+    pfr::launch_fn_combine(v.d_sup_rows, v.n_sup_rows, s->fcoef, Yk, Fc, c.st);
+    if ((rc = sym_top_down_pair(s, v, c.st, true))) return rc;
+    pfr::launch_dirichlet_post(post_desc(s, v, op), op.pop, v.post_n, s->XA, Fc, c.st);
+    // the correction fr(x) + Re(mu^T r) needs fr OF the solution x whose residual r is walked (the
+    // dot product's fr has its own rounding error, which the correction does not see): fr0 from x
+    if (ps.correct) pfr::launch_functional(seeded(s, c.fa), s->X, Fc, c.nv, c.q0, nullptr, nullptr, nullptr, c.st);
+  } else if (ps.paired) {
+    if ((rc = solve_all(s, v, op, pfr::TRI_L, pfr::RHS_VECTOR, rg, nullptr, s->Y2, c.st, pfr::REACH_SUPPORT)) ||
+        (rc = sym_top_down_pair(s, v, c.st)))
+      return rc;
+    pfr::launch_dirichlet_post(post_desc(s, v, op), op.pop, v.post_n, s->XA, Fc, c.st);
+  } else {
+    if ((rc = adjoint_solve(s, v, op, rg, s->XA, c.st, pfr::REACH_SUPPORT))) return rc;
+    if (ps.refine) {
+      // l += A^{-T} (g - A^T l): residual into Y2, correction into XR
+      run_walk(s, v, op, Walk::residual(Walk::ADJOINT, pfr::RHS_VECTOR, rg, s->XA, s->Y2), c.nv, c.st);
+      if ((rc = adjoint_solve(s, v, op, rhs_vector(s->Y2), s->XR, c.st))) return rc;
+      pfr::launch_axpy_vec(s->XA, s->XR, (int64_t)s->n * Fc, c.st);
+    }
+  }
+  return PFR_OK;
+}
+
+// after the adjoint (ps.adj): the walks, the correction, the contraction and the finish into the caller's outputs
+int phase_finish(pfr_solver* s, SolverView& v, const pfr::ChunkOp& op, const SweepPasses& ps, const SweepSpec& sp,
+                 const Chunk& c) {
+  int rc;
+  const int64_t Fc = s->Fc, q0 = c.q0;
+  const int nv = c.nv;
+  hipStream_t st = c.st;
+  if (ps.correct) {
+    // the forward residual walk: backward error (when checked) + the correction's dot products, then the corrected
+    // fr (the CPX form reads the solve's H in h0), its loss terms and the per-frequency cotangent scales
+    run_walk(s, v, op, Walk::correction(c.rd, s->X, s->XA, ps.check_fwd_walk, q0, ps.cwalk), nv, st);
+    if (ps.scorr) pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st);
+    pfr::launch_correct_finish(sp.resp.cpx ? seeded(s, c.fa) : c.fa, s->fr0, s->cpart, pfr::residual_parts(s->n), Fc, nv,
+                               q0, sp.fr(), s->loss_terms, s->mscale, op, st, ps.refine_adj ? s->gind : nullptr,
+                               ps.scorr ? s->tq : nullptr);
+  }
+  if (ps.refine_adj) {
+    // the listed groups (largest first-order fr error estimates above the tolerance, at most REFINE_CAP; there the
+    // unrefined solves' first-order error dominates the gradient):
+    // mu += A^-T (G - A^T mu) with the fr seed G = d fr / d x of THIS x (k_functional seed mode; the adjoint
+    // was solved for the seed of the bottom-up dot products, whose rounding differs), then their correction
+    // dot products and gradient contraction again with the refined mu, and their fr / m_q
+    pfr::launch_select_groups(s->gind, (int)(Fc / 64), s->refine_tol, s->glist, st);
+    if (!s->Gx) {
+      if ((rc = s->alloc(&s->Gx, s->ws.nvec))) return rc;
+      HIP_TRY(hipMemsetAsync(s->Gx, 0, (size_t)s->n * Fc * 16, st));   // only the support rows are ever written
+    }
+    pfr::launch_functional(seeded(s, c.fa), s->X, Fc, nv, q0, nullptr, nullptr, s->Gx, st);
+    run_walk(s, v, op, Walk::residual(Walk::ADJOINT, pfr::RHS_VECTOR, rhs_vector(s->Gx), s->XA, s->XR).on_groups(s->glist),
+             nv, st);
+    if ((rc = adjoint_solve(s, v, op, rhs_vector(s->XR), s->Y2, st, pfr::REACH_ALL, s->glist))) return rc;
+    pfr::launch_axpy_vec(s->XA, s->Y2, (int64_t)s->n * Fc, st, s->glist, Fc);
+    run_walk(s, v, op, Walk::correction(c.rd, s->X, s->XA, false, q0, true).on_groups(s->glist), nv, st);
+    if (ps.scorr) pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st);
+    pfr::launch_correct_finish(c.fa, s->fr0, s->cpart, pfr::residual_parts(s->n), Fc, nv, q0, sp.fr(), s->loss_terms,
+                               s->mscale, op, st, nullptr, ps.scorr ? s->tq : nullptr);
+  }
+  const double2* msc = ps.correct ? s->mscale : nullptr;
+  if (ps.jac) {
+    // the walk's kpart is final here (the refined groups redone above); without the walk k_contract_q forms it
+    if (!ps.cwalk) pfr::launch_contract_q(s->d_uent, s->n_uent, s->d_se, s->n_stiff, s->XA, s->X, s->n, Fc, s->kpart, st);
+  } else if (ps.cwalk)
+    pfr::launch_reduce_q(s->kpart, pfr::residual_parts(s->n), s->n_stiff, msc, nv, Fc, s->partial, st);
+  else if (ps.reverse)
+    pfr::launch_contract_eg(s->d_uent, s->n_uent, s->d_se, s->n_stiff, s->XA, s->X, Fc, nv, s->partial, st, msc);
+  // the checks as row / column walks of the original pattern (k_residual)
+  if (ps.check_fwd_after) run_walk(s, v, op, Walk::checked(Walk::FORWARD, pfr::RHS_OPERATOR, c.rd, s->X, q0), nv, st);
+  if (ps.check_adj)
+    run_walk(s, v, op, Walk::checked(Walk::ADJOINT, pfr::RHS_VECTOR, rhs_vector(s->G), s->XA, q0), nv, st);
+  if (ps.reverse) {
+    if (!ps.scorr) pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st, msc);
+    if (ps.jac)
+      pfr::launch_jac_finish(s->kpart, ps.cwalk ? pfr::residual_parts(s->n) : pfr::contract_q_parts(s->n, s->n_uent),
+                             s->n_stiff, msc, s->tq, s->e, nv, Fc, sp.jc + q0 * s->n_stiff, st);
     else
-      pfr::launch_chunk_start(s->freqs, freqs_dev + q0, nv, Fc, s->flags, st);
-    if (int rc0 = begin_chunk(s)) return rc0;
+      pfr::launch_reduce(s->partial, ps.cwalk ? (int)(Fc / 64) : pfr::contract_eg_parts(s->n_uent), s->n_stiff, s->tq,
+                         s->e, s->loss_terms, nv, Fc, reinterpret_cast<double2*>(sp.w), sp.loss, st);
+  }
+  return PFR_OK;
+}
+
+// The launches of one sweep (an entry point after its checks), direct or under stream capture
+int sweep_launches(pfr_solver* s, const SweepSpec& sp, hipStream_t st) {
+  const SweepPasses ps = sweep_passes(s, sp);
+  reset_timing(s);
+  const int64_t Fc = s->Fc;
+  SolverView& v = begin_on_view(s, ps.pruned, st);
+  s->last_adj = ps.adj;
+  s->last_st = st;
+  int rc;
+  // buffers and row lists allocated on first use (never under capture: a sweep's first run is direct)
+  if (ps.fn_fast && (rc = fn_setup(s, v))) return rc;
+  if (sp.resp.cpx && ps.correct && !s->h0 && (rc = s->alloc(&s->h0, Fc))) return rc;
+  if ((ps.cwalk || ps.jac) && !s->kpart && (rc = s->alloc(&s->kpart, s->ws.kpart))) return rc;
+  const bool used[5] = {true, true, true, ps.adj, ps.adj};
+  Chunk c{.st = st, .fa = functional_args(s, sp)};
+  for (c.q0 = 0; c.q0 < sp.nfreq; c.q0 += Fc) {
+    c.nv = (int)std::min<int64_t>(Fc, sp.nfreq - c.q0);
+    if (sp.fresh && c.q0 == 0)      // the caller's outputs initialised here (pfr_sweep_fresh)
+      pfr::launch_chunk_start(s->freqs, sp.freqs + c.q0, c.nv, Fc, s->flags, st, sp.loss, sp.w,
+                              ps.reverse && sp.w ? 2 * s->n_stiff : 0, sp.flags, s->berr_out, sp.nfreq);
+    else
+      pfr::launch_chunk_start(s->freqs, sp.freqs + c.q0, c.nv, Fc, s->flags, st);
+    if ((rc = begin_chunk(s))) return rc;
     record(s, 0, st);
-    const pfr::ChunkOp op = chunk_op(s, popK, pop, q0);
+    const pfr::ChunkOp op = chunk_op(s, sp.popK, sp.pop.member ? &sp.pop : nullptr, c.q0);
     s->last_op = op;
     s->comp_done = false;
-    const pfr::DirArgs dd = dir_desc(s, op);
-    const pfr::RhsArgs rd = rhs_operator(op);
-    pfr::RhsArgs rf = rd;
-    int rc;
-    if (paired) {
-      pfr::launch_dirichlet_rhs(0, dd, op.pop, s->n_crow, rd, nullptr, s->Bc, s->Fc, st);
-      rf.cslot = s->d_cslot;
-      rf.Bc = s->Bc;
-      if ((rc = factor_all(s, v, op, 0, nullptr, 0, nv, st))) return rc;
-      record(s, 1, st);   // the forward bottom-up pass belongs to the solve phases (sptrsv_roofline)
-      if (fn_fast) {
-        if ((rc = fn_bottom_up(s, v, op, s->n_crow > 0 ? 3 : 0, rf, st))) return rc;
-      } else if ((rc = solve_all(s, v, op, 0, s->n_crow > 0 ? 3 : 0, rf, nullptr, s->Y, st, 0))) {
-        return rc;
-      }
-    } else {
-      rc = factor_all(s, v, op, 0, nullptr, 0, nv, st);
-      if (rc) return rc;
-      record(s, 1, st);
-    }
-    // symmetric mode with an adjoint: forward top-down only over the loss support's fronts, then one
-    // combined top-down pass (sym_top_down_pair); otherwise the full forward solve first
-    if (paired) {
-      if (!fn_fast && (rc = sym_top_down_support(s, v, st))) return rc;
-    } else {
-      if ((rc = forward_solve(s, v, op, 0, rd, s->X, st, 0))) return rc;
-      if (refine) {
-        // one refinement step on the same factors: r = b - A x (into G), A d = r (into XA), x += d
-        check_solution(s, v, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, s->G, q0, st);
-        if ((rc = forward_solve(s, v, op, 2, rhs_vector(s->G), s->XA, st))) return rc;
-        pfr::launch_axpy_vec(s->X, s->XA, (int64_t)s->n * Fc, st);
-      }
-      if (!fwd_late && (s->check_mode & PFR_CHECK_FORWARD))
-        check_solution(s, v, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st);
-    }
+    c.rd = rhs_operator(op);
+    if ((rc = phase_factor(s, v, op, ps, sp, c))) return rc;
+    record(s, 1, st);
+    if ((rc = phase_forward(s, v, op, ps, sp, c))) return rc;
     record(s, 2, st);
-    pfr::FunctionalArgs fa = s->fn;
-    fa.loss_type = reverse ? loss_type : -1;
-    fa.ref = reinterpret_cast<const double2*>(ref_dev);
-    fa.scale = scale;
-    if (resp.cpx) {
-      fa.cpx = 1;
-      std::copy(resp.axis, resp.axis + 3, fa.axis);
-      fa.h_out = reinterpret_cast<double2*>(fr_dev);
-    }
-    if (adj) pfr::launch_zero(s->G, (int64_t)s->n * Fc, st);
-    if (fn_fast) {
-      const double2* Yk[3] = {s->Y2, s->YVk, s->YVk + (int64_t)s->n * Fc};
-      pfr::launch_fn_dot(v.d_fn_rows, v.n_fn_rows, s->F, s->Y, Yk, Fc, s->fn_parts, st);
-      pfr::FunctionalArgs fs = fa;
-      if (correct) seed(fs);
-      pfr::launch_functional_fn(fs, s->fn_parts, Fc, nv, q0, correct ? nullptr : fr_out, correct ? nullptr : s->loss_terms,
-                                s->G, s->fcoef, st);
-    } else if (correct) {
-      pfr::FunctionalArgs fs = fa;
-      seed(fs);                 // fr of this solve kept, G = d fr / d x
-      pfr::launch_functional(fs, s->X, Fc, nv, q0, nullptr, nullptr, s->G, st);
-    } else {
-      pfr::launch_functional(fa, s->X, Fc, nv, q0, fr_out, s->loss_terms, s->G, st);
-    }
+    phase_functional(s, v, op, ps, sp, c);
     record(s, 3, st);
-    if (adj) {
-      const pfr::RhsArgs rg = rhs_vector(s->G);
-      if (fn_fast) {
-        double2* Yk[3] = {s->Y2, s->YVk, s->YVk + (int64_t)s->n * Fc};
-        pfr::launch_fn_combine(v.d_sup_rows, v.n_sup_rows, s->fcoef, Yk, Fc, st);
-        if ((rc = sym_top_down_pair(s, v, st, true))) return rc;
-        pfr::launch_dirichlet_post(post_desc(s, v, op), op.pop, v.post_n, s->XA, s->Fc, st);
-        if (correct) {
-          // the correction fr(x) + Re(mu^T r) needs fr OF the solution x whose residual r is walked (the
-          // dot product's fr has its own rounding error, which the correction does not see): fr0 from x
-          pfr::FunctionalArgs fs = fa;
-          seed(fs);
-          pfr::launch_functional(fs, s->X, Fc, nv, q0, nullptr, nullptr, nullptr, st);
-        }
-      } else if (paired) {
-        if ((rc = solve_all(s, v, op, 0, 2, rg, nullptr, s->Y2, st, 1)) || (rc = sym_top_down_pair(s, v, st))) return rc;
-        pfr::launch_dirichlet_post(post_desc(s, v, op), op.pop, v.post_n, s->XA, s->Fc, st);
-      } else {
-        if ((rc = adjoint_solve(s, v, op, rg, s->XA, st, 1))) return rc;
-        if (refine) {
-          // l += A^{-T} (g - A^T l): residual into Y2, correction into XR
-          check_solution(s, v, op, 1, 0, 2, rg, nullptr, 0, nv, s->XA, s->Y2, q0, st);
-          if ((rc = adjoint_solve(s, v, op, rhs_vector(s->Y2), s->XR, st))) return rc;
-          pfr::launch_axpy_vec(s->XA, s->XR, (int64_t)s->n * Fc, st);
-        }
-      }
-      record(s, 4, st);
-      bool want_f = fwd_late && (s->check_mode & PFR_CHECK_FORWARD);
-      bool want_a = (s->check_mode & PFR_CHECK_ADJOINT) != 0;
-      // the gradient contraction rides on the forward residual walk (loss sweeps with the correction)
-      const bool cwalk = reverse && correct && s->contract_walk &&
-                         (s->n_stiff == 12 || s->n_stiff == 18);
-      if ((cwalk || jac) && !s->kpart) {
-        if ((rc = s->alloc(&s->kpart, s->ws.kpart))) return rc;
-      }
-      // selective adjoint refinement (PFR_CHECK_REFINE_ADJ): the groups next to a resonance, where the unrefined
-      // solves' first-order error dominates the gradient, get one refinement step of mu
-      const bool refine_adj =
-          reverse && correct && cwalk && fn_fast && !resp.cpx && (s->check_mode & PFR_CHECK_REFINE_ADJ);
-      // the solve-error scale of the cotangent (k_correct_finish): t_q = mu^T rhsP in, m_q t_q out
-      const bool scorr = reverse && correct && s->scale_corr;
-      if (correct) {
-        // the forward residual walk: backward error (when checked) + the correction's dot products,
-        // then the corrected fr, its loss terms and the per-frequency cotangent scales
-        check_solution(s, v, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st, s->XA, want_f, cwalk);
-        want_f = false;
-        if (scorr) pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st);
-        pfr::FunctionalArgs fc = fa;
-        if (resp.cpx) fc.h0 = s->h0;    // the CPX form reads the solve's H there (the magnitude's fr0 is an argument)
-        pfr::launch_correct_finish(fc, s->fr0, s->cpart, pfr::residual_parts(s->n), Fc, nv, q0, fr_out, s->loss_terms,
-                                   s->mscale, op, st, refine_adj ? s->gind : nullptr, scorr ? s->tq : nullptr);
-      }
-      if (refine_adj) {
-        // the listed groups (largest first-order fr error estimates above the tolerance, at most REFINE_CAP):
-        // mu += A^-T (G - A^T mu) with the fr seed G = d fr / d x of THIS x (k_functional seed mode; the adjoint
-        // was solved for the seed of the bottom-up dot products, whose rounding differs), then their correction
-        // dot products and gradient contraction again with the refined mu, and their fr / m_q
-        pfr::launch_select_groups(s->gind, (int)(Fc / 64), s->refine_tol, s->glist, st);
-        if (!s->Gx) {
-          if ((rc = s->alloc(&s->Gx, s->ws.nvec))) return rc;
-          HIP_TRY(hipMemsetAsync(s->Gx, 0, (size_t)s->n * Fc * 16, st));   // only the support rows are ever written
-        }
-        pfr::FunctionalArgs fs = fa;
-        fs.fr0 = s->fr0;
-        pfr::launch_functional(fs, s->X, Fc, nv, q0, nullptr, nullptr, s->Gx, st);
-        check_solution(s, v, op, 1, 0, 2, rhs_vector(s->Gx), nullptr, 0, nv, s->XA, s->XR, q0, st, nullptr, false, false,
-                       s->glist);
-        if ((rc = adjoint_solve(s, v, op, rhs_vector(s->XR), s->Y2, st, -1, s->glist))) return rc;
-        pfr::launch_axpy_vec(s->XA, s->Y2, (int64_t)s->n * Fc, st, s->glist, Fc);
-        check_solution(s, v, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st, s->XA, false, true, s->glist);
-        if (scorr) pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st);
-        pfr::launch_correct_finish(fa, s->fr0, s->cpart, pfr::residual_parts(s->n), Fc, nv, q0, fr_out, s->loss_terms,
-                                   s->mscale, op, st, nullptr, scorr ? s->tq : nullptr);
-      }
-      const double2* msc = correct ? s->mscale : nullptr;
-      if (jac) {
-        // the walk's kpart is final here (the refined groups redone above); without the walk k_contract_q forms it
-        if (!cwalk) pfr::launch_contract_q(s->d_uent, s->n_uent, s->d_se, s->n_stiff, s->XA, s->X, s->n, Fc, s->kpart, st);
-      } else if (cwalk)
-        pfr::launch_reduce_q(s->kpart, pfr::residual_parts(s->n), s->n_stiff, msc, nv, Fc, s->partial, st);
-      else if (reverse)
-        pfr::launch_contract_eg(s->d_uent, s->n_uent, s->d_se, s->n_stiff, s->XA, s->X, Fc, nv, s->partial, st, msc);
-      // the checks as row / column walks of the original pattern (k_residual)
-      if (want_f) check_solution(s, v, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st);
-      if (want_a) check_solution(s, v, op, 1, 0, 2, rg, nullptr, 0, nv, s->XA, nullptr, q0, st);
-      if (reverse) {
-        if (!scorr) pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st, msc);
-        if (jac)
-          pfr::launch_jac_finish(s->kpart, cwalk ? pfr::residual_parts(s->n) : pfr::contract_q_parts(s->n, s->n_uent),
-                                 s->n_stiff, msc, s->tq, s->e, nv, Fc, jc_dev + q0 * s->n_stiff, st);
-        else
-          pfr::launch_reduce(s->partial, cwalk ? (int)(Fc / 64) : pfr::contract_eg_parts(s->n_uent), s->n_stiff, s->tq,
-                             s->e, s->loss_terms, nv, Fc, reinterpret_cast<double2*>(w_dev), loss_dev, st);
-      }
-    } else {
-      record(s, 4, st);
-    }
+    if (ps.adj && (rc = phase_adjoint(s, v, op, ps, sp, c))) return rc;
+    record(s, 4, st);
+    if (ps.adj && (rc = phase_finish(s, v, op, ps, sp, c))) return rc;
     record(s, 5, st);
-    if (flags_dev) pfr::launch_flags_merge(s->flags, nv, flags_dev + q0, st);
+    if (sp.flags) pfr::launch_flags_merge(s->flags, c.nv, sp.flags + c.q0, st);
     LAUNCH_TRY();
     if ((rc = finish_timing(s, used))) return rc;
   }
@@ -1719,45 +1738,52 @@ uint64_t key_bits(T v) {
   std::memcpy(&b, &v, sizeof(T));
   return b;
 }
-}  // namespace
 
-extern "C" {
+// The state a sweep needs, refused in this order: the operator (own_K, a population sweep: the mass matrix alone), the
+// rhs, the functional and -- no_stiff != NULL: the refusal's text -- the stiffness matrices
+int sweep_ready(const pfr_solver* s, const char* no_stiff = nullptr, bool own_K = false) {
+  if (!own_K && (!s->K || !s->M)) return fail(PFR_ERR_STATE, "operator not set (pfr_set_operator)");
+  if (own_K && !s->M) return fail(PFR_ERR_STATE, "mass matrix not set (pfr_set_operator)");
+  if (!s->has_rhs) return fail(PFR_ERR_STATE, "rhs not set (pfr_set_rhs)");
+  if (!s->has_fn) return fail(PFR_ERR_STATE, "functional not set (pfr_set_functional)");
+  if (no_stiff && !s->stiff) return fail(PFR_ERR_STATE, no_stiff);
+  return PFR_OK;
+}
 
-namespace {
+// a sweep that is never captured, and the loss sweeps' graph is not replayed past it: the next loss sweep runs directly
+void never_captured(pfr_solver* s) { s->drop_graph(), s->gkey_valid = false; }
+
 int sweep_impl(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_t loss_type, const double* ref_dev,
                double scale, double* fr_dev, double* loss_dev, double* w_dev, int32_t* flags_dev, void* stream,
                bool fresh) {
   if (!s || nfreq <= 0 || !freqs_dev) return fail(PFR_ERR_ARG, "bad sweep arguments");
-  if (!s->K || !s->M) return fail(PFR_ERR_STATE, "operator not set (pfr_set_operator)");
-  if (!s->has_rhs) return fail(PFR_ERR_STATE, "rhs not set (pfr_set_rhs)");
-  if (!s->has_fn) return fail(PFR_ERR_STATE, "functional not set (pfr_set_functional)");
+  if (int rc = sweep_ready(s)) return rc;
   const bool reverse = loss_type != PFR_LOSS_NONE;
   if (reverse && (loss_type < 0 || loss_type > PFR_LOSS_COTANGENT || !ref_dev))
     return fail(PFR_ERR_ARG, "bad loss type / missing ref");
   if (reverse && (!s->stiff || !w_dev)) return fail(PFR_ERR_STATE, "reverse pass needs pfr_set_stiffness and w_dev");
   HIP_TRY(hipSetDevice(s->device));
   hipStream_t st = (hipStream_t)stream;
-  auto direct = [&] { return sweep_launches(s, nfreq, freqs_dev, loss_type, ref_dev, scale, fr_dev, loss_dev, w_dev,
-                                            flags_dev, st, fresh); };
+  const SweepSpec sp{.nfreq = nfreq, .freqs = freqs_dev, .loss_type = loss_type, .ref = ref_dev, .scale = scale,
+                     .response = fr_dev, .loss = loss_dev, .w = w_dev, .flags = flags_dev, .fresh = fresh};
   // per-launch timing events are host work between the launches: never under a graph
-  if (!s->graph_mode || s->graph_off || s->timing) return direct();
-  const std::array<uint64_t, 14> key = {s->gen * 2 + (fresh ? 1 : 0), key_bits(s->check_mode), key_bits(s->check_tol),
-                                        key_bits(s->berr_out),
-                                        key_bits(nfreq), key_bits(freqs_dev), key_bits(loss_type), key_bits(ref_dev),
-                                        key_bits(scale), key_bits(fr_dev), key_bits(loss_dev), key_bits(w_dev),
-                                        key_bits(flags_dev), key_bits(st)};
+  if (!s->graph_mode || s->graph_off || s->timing) return sweep_launches(s, sp, st);
+  const std::array<uint64_t, 14> key = {
+      s->gen * 2 + (sp.fresh ? 1 : 0), key_bits(s->check_mode), key_bits(s->check_tol), key_bits(s->berr_out),
+      key_bits(sp.nfreq), key_bits(sp.freqs), key_bits(sp.loss_type), key_bits(sp.ref), key_bits(sp.scale),
+      key_bits(sp.response), key_bits(sp.loss), key_bits(sp.w), key_bits(sp.flags), key_bits(st)};
   if (!s->gkey_valid || key != s->gkey) {
     // a new sweep configuration: run it directly (its first run also makes the lazy allocations and uploads,
     // which a capture must not contain); the same configuration again is captured
     s->drop_graph();
     s->gkey = key;
     s->gkey_valid = true;
-    return direct();
+    return sweep_launches(s, sp, st);
   }
   if (!s->gexec) {
     hipGraph_t g = nullptr;
     HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    const int rc = direct();
+    const int rc = sweep_launches(s, sp, st);
     const hipError_t e = hipStreamEndCapture(st, &g);
     hipGraphExec_t x = nullptr;
     if (rc == PFR_OK && e == hipSuccess && g && hipGraphInstantiate(&x, g, nullptr, nullptr, 0) == hipSuccess) {
@@ -1768,7 +1794,7 @@ int sweep_impl(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_t lo
       if (g) (void)hipGraphDestroy(g);
       (void)hipGetLastError();
       s->graph_off = true;
-      return direct();
+      return sweep_launches(s, sp, st);
     }
   }
   s->comp_done = false;
@@ -1776,7 +1802,26 @@ int sweep_impl(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_t lo
   ++s->graph_launches;
   return PFR_OK;
 }
+
+// the argument checks the two complex sweeps share; then never captured, on the solver's device
+int complex_sweep_begin(pfr_solver* s, int32_t nfreq, const double* freqs_dev, const double* axis, bool reverse,
+                        Response* resp) {
+  if (!s || nfreq <= 0 || !freqs_dev || !axis) return fail(PFR_ERR_ARG, "bad complex sweep arguments");
+  if (!(std::isfinite(axis[0]) && std::isfinite(axis[1]) && std::isfinite(axis[2])) ||
+      (axis[0] == 0.0 && axis[1] == 0.0 && axis[2] == 0.0))
+    return fail(PFR_ERR_ARG, "sensing axis zero or not finite");
+  if (s->check_mode & PFR_CHECK_REFINE_ADJ)
+    return fail(PFR_ERR_ARG, "PFR_CHECK_REFINE_ADJ does not apply to the complex response");
+  if (int rc = sweep_ready(s, reverse ? "reverse pass needs pfr_set_stiffness" : nullptr)) return rc;
+  resp->cpx = true;
+  std::copy(axis, axis + 3, resp->axis);
+  never_captured(s);
+  HIP_TRY(hipSetDevice(s->device));
+  return PFR_OK;
+}
 }  // namespace
+
+extern "C" {
 
 int pfr_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_t loss_type, const double* ref_dev,
               double scale, double* fr_dev, double* loss_dev, double* w_dev, int32_t* flags_dev, void* stream) {
@@ -1793,39 +1838,13 @@ int64_t pfr_sweep_graph_launches(const pfr_solver* s) { return s ? s->graph_laun
 int pfr_jacobian_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, double* fr_dev, double* jc_dev,
                        int32_t* flags_dev, void* stream) {
   if (!s || nfreq <= 0 || !freqs_dev || !jc_dev) return fail(PFR_ERR_ARG, "bad jacobian sweep arguments");
-  if (!s->K || !s->M) return fail(PFR_ERR_STATE, "operator not set (pfr_set_operator)");
-  if (!s->has_rhs) return fail(PFR_ERR_STATE, "rhs not set (pfr_set_rhs)");
-  if (!s->has_fn) return fail(PFR_ERR_STATE, "functional not set (pfr_set_functional)");
-  if (!s->stiff) return fail(PFR_ERR_STATE, "jacobian sweep needs pfr_set_stiffness");
-  // never captured, and the loss sweeps' graph is not replayed past it: the next loss sweep runs directly
-  s->drop_graph();
-  s->gkey_valid = false;
+  if (int rc = sweep_ready(s, "jacobian sweep needs pfr_set_stiffness")) return rc;
+  never_captured(s);
   HIP_TRY(hipSetDevice(s->device));
-  return sweep_launches(s, nfreq, freqs_dev, pfr::LOSS_UNIT, nullptr, 1.0, fr_dev, nullptr, nullptr, flags_dev,
-                        (hipStream_t)stream, false, reinterpret_cast<double2*>(jc_dev));
+  const SweepSpec sp{.nfreq = nfreq, .freqs = freqs_dev, .loss_type = pfr::LOSS_UNIT, .response = fr_dev,
+                     .jc = reinterpret_cast<double2*>(jc_dev), .flags = flags_dev};
+  return sweep_launches(s, sp, (hipStream_t)stream);
 }
-
-namespace {
-// the argument checks the two complex sweeps share; the loss sweeps' graph is dropped as pfr_jacobian_sweep does
-int complex_sweep_begin(pfr_solver* s, int32_t nfreq, const double* freqs_dev, const double* axis, bool reverse,
-                        Response* resp) {
-  if (!s || nfreq <= 0 || !freqs_dev || !axis) return fail(PFR_ERR_ARG, "bad complex sweep arguments");
-  if (!(std::isfinite(axis[0]) && std::isfinite(axis[1]) && std::isfinite(axis[2])) ||
-      (axis[0] == 0.0 && axis[1] == 0.0 && axis[2] == 0.0))
-    return fail(PFR_ERR_ARG, "sensing axis zero or not finite");
-  if (s->check_mode & PFR_CHECK_REFINE_ADJ)
-    return fail(PFR_ERR_ARG, "PFR_CHECK_REFINE_ADJ does not apply to the complex response");
-  if (!s->K || !s->M) return fail(PFR_ERR_STATE, "operator not set (pfr_set_operator)");
-  if (!s->has_rhs) return fail(PFR_ERR_STATE, "rhs not set (pfr_set_rhs)");
-  if (!s->has_fn) return fail(PFR_ERR_STATE, "functional not set (pfr_set_functional)");
-  if (reverse && !s->stiff) return fail(PFR_ERR_STATE, "reverse pass needs pfr_set_stiffness");
-  resp->cpx = true;
-  std::copy(axis, axis + 3, resp->axis);
-  s->drop_graph();
-  s->gkey_valid = false;
-  return PFR_OK;
-}
-}  // namespace
 
 int pfr_sweep_complex(pfr_solver* s, int32_t nfreq, const double* freqs_dev, const double* axis, int32_t loss_type,
                       const double* ref_dev, double scale, double* h_dev, double* loss_dev, double* w_dev,
@@ -1836,9 +1855,9 @@ int pfr_sweep_complex(pfr_solver* s, int32_t nfreq, const double* freqs_dev, con
   if (reverse && s && !w_dev) return fail(PFR_ERR_STATE, "reverse pass needs w_dev");
   Response resp;
   if (int rc = complex_sweep_begin(s, nfreq, freqs_dev, axis, reverse, &resp)) return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  return sweep_launches(s, nfreq, freqs_dev, loss_type, ref_dev, scale, h_dev, loss_dev, w_dev, flags_dev,
-                        (hipStream_t)stream, fresh != 0, nullptr, nullptr, nullptr, resp);
+  const SweepSpec sp{.nfreq = nfreq, .freqs = freqs_dev, .loss_type = loss_type, .ref = ref_dev, .scale = scale,
+                     .response = h_dev, .loss = loss_dev, .w = w_dev, .flags = flags_dev, .fresh = fresh != 0, .resp = resp};
+  return sweep_launches(s, sp, (hipStream_t)stream);
 }
 
 int pfr_jacobian_sweep_complex(pfr_solver* s, int32_t nfreq, const double* freqs_dev, const double* axis, double* h_dev,
@@ -1846,9 +1865,9 @@ int pfr_jacobian_sweep_complex(pfr_solver* s, int32_t nfreq, const double* freqs
   if (!jc_dev) return fail(PFR_ERR_ARG, "bad jacobian sweep arguments");
   Response resp;
   if (int rc = complex_sweep_begin(s, nfreq, freqs_dev, axis, true, &resp)) return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  return sweep_launches(s, nfreq, freqs_dev, pfr::LOSS_UNIT, nullptr, 1.0, h_dev, nullptr, nullptr, flags_dev,
-                        (hipStream_t)stream, false, reinterpret_cast<double2*>(jc_dev), nullptr, nullptr, resp);
+  const SweepSpec sp{.nfreq = nfreq, .freqs = freqs_dev, .loss_type = pfr::LOSS_UNIT, .response = h_dev,
+                     .jc = reinterpret_cast<double2*>(jc_dev), .flags = flags_dev, .resp = resp};
+  return sweep_launches(s, sp, (hipStream_t)stream);
 }
 
 int pfr_combine_batch(pfr_solver* s, int32_t n_members, const double* coef, double* Kpop_dev, void* stream) {
@@ -1876,13 +1895,8 @@ int pfr_population_sweep(pfr_solver* s, int32_t nlane, const double* freqs_dev, 
   // ranks the groups of a chunk against each other: a member's result would depend on its neighbours
   if (s->check_mode & PFR_CHECK_REFINE_ADJ)
     return fail(PFR_ERR_ARG, "population sweep: PFR_CHECK_REFINE_ADJ is not supported");
-  if (!s->M) return fail(PFR_ERR_STATE, "mass matrix not set (pfr_set_operator)");
-  if (!s->has_rhs) return fail(PFR_ERR_STATE, "rhs not set (pfr_set_rhs)");
-  if (!s->has_fn) return fail(PFR_ERR_STATE, "functional not set (pfr_set_functional)");
-  if (jc_dev && !s->stiff) return fail(PFR_ERR_STATE, "population jacobian sweep needs pfr_set_stiffness");
-  // never captured, and the loss sweeps' graph is not replayed past it (as pfr_jacobian_sweep)
-  s->drop_graph();
-  s->gkey_valid = false;
+  if (int rc = sweep_ready(s, jc_dev ? "population jacobian sweep needs pfr_set_stiffness" : nullptr, true)) return rc;
+  never_captured(s);
   HIP_TRY(hipSetDevice(s->device));
   hipStream_t st = (hipStream_t)stream;
   // the group table padded to whole chunks (the lanes past nlane of a short last chunk run too, on repeated
@@ -1895,13 +1909,12 @@ int pfr_population_sweep(pfr_solver* s, int32_t nlane, const double* freqs_dev, 
   std::memcpy(tab.data() + off_beta, beta, (size_t)n_members * 16);
   void* d_tab = nullptr;
   if (int rc = stage_upload(s, 1, tab.data(), tab.size(), &d_tab, st)) return rc;
-  pfr::PopArgs pa;
-  pa.member = static_cast<const int32_t*>(d_tab);
-  pa.beta = reinterpret_cast<const double2*>(static_cast<const char*>(d_tab) + off_beta);
-  pa.nnz = s->nnz;
-  return sweep_launches(s, nlane, freqs_dev, jc_dev ? pfr::LOSS_UNIT : PFR_LOSS_NONE, nullptr, 1.0, fr_dev, nullptr,
-                        nullptr, flags_dev, st, false, reinterpret_cast<double2*>(jc_dev),
-                        reinterpret_cast<const double2*>(Kpop_dev), &pa);
+  const double2* d_beta = reinterpret_cast<const double2*>(static_cast<const char*>(d_tab) + off_beta);
+  const SweepSpec sp{.nfreq = nlane, .freqs = freqs_dev, .loss_type = jc_dev ? pfr::LOSS_UNIT : PFR_LOSS_NONE,
+                     .response = fr_dev, .jc = reinterpret_cast<double2*>(jc_dev), .flags = flags_dev,
+                     .popK = reinterpret_cast<const double2*>(Kpop_dev),
+                     .pop = {.member = static_cast<const int32_t*>(d_tab), .beta = d_beta, .nnz = s->nnz}};
+  return sweep_launches(s, sp, st);
 }
 
 int pfr_stream_order(void* waiter, void* signaller) {
@@ -1925,18 +1938,19 @@ int pfr_hessian_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int
   ++s->gen;
   if (loss_type < PFR_LOSS_MSE || loss_type > PFR_LOSS_MSE_LOG_AFC)
     return fail(PFR_ERR_ARG, "hessian sweep needs a loss type (MSE, RMSE, MSE_AFC, MSE_LOG_AFC)");
-  if (!s->K || !s->M) return fail(PFR_ERR_STATE, "operator not set (pfr_set_operator)");
-  if (!s->has_rhs) return fail(PFR_ERR_STATE, "rhs not set (pfr_set_rhs)");
-  if (!s->has_fn) return fail(PFR_ERR_STATE, "functional not set (pfr_set_functional)");
-  if (!s->stiff) return fail(PFR_ERR_STATE, "pfr_set_stiffness not called");
+  if (int rc0 = sweep_ready(s, "pfr_set_stiffness not called")) return rc0;
   HIP_TRY(hipSetDevice(s->device));
   hipStream_t st = (hipStream_t)stream;
   reset_timing(s);
   const int64_t Fc = s->Fc, n = s->n;
-  SolverView& v = *s;                   // the tangent solves' right-hand sides are not the operator's: every front
-  if (s->act) s->unl_dirty = true;
-  s->last_pruned = false;
+  // the tangent solves' right-hand sides are not the operator's: every front
+  SolverView& v = begin_on_view(s, false, st);
   int rc;
+  // the first-order part as the loss sweep's phases where they launch the same: unpaired, unrefined, unchecked
+  const SweepSpec sp{.nfreq = nfreq, .freqs = freqs_dev, .loss_type = loss_type, .ref = ref_dev, .scale = scale,
+                     .loss = loss_dev, .w = w_dev, .flags = flags_dev};
+  const SweepPasses ps{.reverse = true, .correct = (s->check_mode & PFR_CHECK_CORRECT) != 0, .adj = true};
+  Chunk ck{.st = st, .fa = functional_args(s, sp)};
   if (!s->DX && ((rc = s->alloc(&s->DX, n * Fc)) || (rc = s->alloc(&s->DL, n * Fc)))) return rc;
   if (s->n_kdir < n_dir) {
     if ((rc = s->alloc(&s->Kdir, (int64_t)n_dir * s->nnz))) return rc;   // previous block stays owned
@@ -1958,37 +1972,28 @@ int pfr_hessian_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int
     pfr::launch_combine(s->stiff, s->n_stiff, s->nnz, c, s->Kdir + (int64_t)i * s->nnz, st);
   }
   double2* H = reinterpret_cast<double2*>(h_dev);
-  for (int64_t q0 = 0; q0 < nfreq; q0 += Fc) {
-    const int nv = (int)std::min<int64_t>(Fc, nfreq - q0);
+  for (int64_t& q0 = ck.q0; q0 < nfreq; q0 += Fc) {
+    const int nv = ck.nv = (int)std::min<int64_t>(Fc, nfreq - q0);
     pfr::launch_chunk_start(s->freqs, freqs_dev + q0, nv, Fc, s->flags, st);
     const pfr::ChunkOp op = chunk_op(s);
-    if ((rc = factor_all(s, v, op, 0, nullptr, 0, nv, st))) return rc;
-    // forward solve, loss, adjoint, gradient partials (as pfr_sweep)
-    const pfr::RhsArgs rd = rhs_operator(op);
-    if ((rc = forward_solve(s, v, op, 0, rd, s->X, st, 0))) return rc;
-    pfr::FunctionalArgs fa = s->fn;
-    fa.loss_type = loss_type;
-    fa.ref = reinterpret_cast<const double2*>(ref_dev);
-    fa.scale = scale;
+    ck.rd = rhs_operator(op);
+    // factorisation, forward solve, loss, adjoint, gradient partials
+    if ((rc = phase_factor(s, v, op, ps, sp, ck)) || (rc = phase_forward(s, v, op, ps, sp, ck))) return rc;
     HIP_TRY(hipMemsetAsync(s->G, 0, (size_t)n * Fc * 16, st));
     const pfr::RhsArgs rg = rhs_vector(s->G);
-    if (s->check_mode & PFR_CHECK_CORRECT) {
-      // as pfr_sweep: the adjoint of fr, the corrected fr's loss terms and cotangent scales, then
-      // lambda = m_q mu in place -- loss and gradient equal the corrected loss sweep's
-      pfr::FunctionalArgs fs = fa;
-      fs.fr0 = s->fr0;
-      pfr::launch_functional(fs, s->X, Fc, nv, q0, nullptr, nullptr, s->G, st);
-      if ((rc = adjoint_solve(s, v, op, rg, s->XA, st, 1))) return rc;
-      check_solution(s, v, op, 0, 0, 0, rd, nullptr, 0, nv, s->X, nullptr, q0, st, s->XA, false);
+    // with the correction the seed mode, as pfr_sweep: the adjoint of fr, the corrected fr's loss terms and cotangent
+    // scales, then lambda = m_q mu in place -- loss and gradient equal the corrected loss sweep's
+    pfr::launch_functional(ps.correct ? seeded(s, ck.fa) : ck.fa, s->X, Fc, nv, q0, nullptr,
+                           ps.correct ? nullptr : s->loss_terms, s->G, st);
+    if ((rc = phase_adjoint(s, v, op, ps, sp, ck))) return rc;
+    if (ps.correct) {
+      run_walk(s, v, op, Walk::correction(ck.rd, s->X, s->XA, false, q0, false), nv, st);
       // the loss sweep's cotangent, solve-error scale included (k_correct_finish): its gradient is the loss sweep's
       if (s->scale_corr) pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st);
-      pfr::launch_correct_finish(fa, s->fr0, s->cpart, pfr::residual_parts(s->n), Fc, nv, q0, nullptr, s->loss_terms,
+      pfr::launch_correct_finish(ck.fa, s->fr0, s->cpart, pfr::residual_parts(s->n), Fc, nv, q0, nullptr, s->loss_terms,
                                  s->mscale, op, st, nullptr, s->scale_corr ? s->tq : nullptr);
       pfr::launch_scale_vec(s->XA, s->mscale, s->n, Fc, st);
       // the second-order seeds G (k_functional_tangent) are formed from fa, not the seed mode
-    } else {
-      pfr::launch_functional(fa, s->X, Fc, nv, q0, nullptr, s->loss_terms, s->G, st);
-      if ((rc = adjoint_solve(s, v, op, rg, s->XA, st, 1))) return rc;
     }
     contract_rows(s, s->XA, s->X, nv, st);
     pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st);
@@ -2000,9 +2005,9 @@ int pfr_hessian_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int
     for (int i = 0; i < n_dir; ++i) {
       const double2* Kd = s->Kdir + (int64_t)i * s->nnz;
       pfr::launch_tangent_spmv(s->d_rptr, s->d_ridx, s->d_rnz, (int)n, Kd, s->X, Fc, s->rhsP, beta[i], s->G, 0, st);
-      if ((rc = forward_solve(s, v, op, 2, rg, s->DX, st))) return rc;
+      if ((rc = forward_solve(s, v, op, pfr::RHS_VECTOR, rg, s->DX, st))) return rc;
       HIP_TRY(hipMemsetAsync(s->G, 0, (size_t)n * Fc * 16, st));
-      pfr::launch_functional_tangent(fa, s->X, s->DX, Fc, nv, q0, s->G, st);
+      pfr::launch_functional_tangent(ck.fa, s->X, s->DX, Fc, nv, q0, s->G, st);
       pfr::launch_tangent_spmv(s->d_cptr, s->d_cidx, s->d_cnz, (int)n, Kd, s->XA, Fc, nullptr, make_double2(0, 0),
                                s->G, 1, st);
       if ((rc = adjoint_solve(s, v, op, rg, s->DL, st))) return rc;
@@ -2036,9 +2041,8 @@ int pfr_solve_multi(pfr_solver* s, int32_t batch, int32_t nrhs, const double* da
   hipStream_t st = (hipStream_t)stream;
   reset_timing(s);
   const int64_t Fc = s->Fc;
-  SolverView& v = *s;                   // a caller's matrices: every front (a general analysis: no view exists;
-  if (s->act) s->unl_dirty = true;      // kept right should that ever change)
-  s->last_pruned = false;
+  // a caller's matrices: every front (a general analysis: no view exists; kept right should that ever change)
+  SolverView& v = begin_on_view(s, false, st);
   const double2* data = reinterpret_cast<const double2*>(data_dev);
   const double2* B = reinterpret_cast<const double2*>(b_dev);
   double2* Xo = reinterpret_cast<double2*>(x_dev);
@@ -2050,40 +2054,36 @@ int pfr_solve_multi(pfr_solver* s, int32_t batch, int32_t nrhs, const double* da
     record(s, 0, st);
     // padded lanes repeat the last valid item (stride 0 broadcast handled by the kernel's clamp)
     const pfr::ChunkOp op = chunk_op(s);   // explicit matrices: K and the rhs may be unset, none of it is read
-    int rc = factor_all(s, v, op, 1, data + q0 * data_stride, data_stride, nv, st);
+    int rc = factor_all(s, v, op, pfr::MAT_BATCH, data + q0 * data_stride, data_stride, nv, st);
     if (rc) return rc;
     record(s, 1, st);
     // every right-hand side of the chunk on the same factors (reference mode 4
     // refactorises per right-hand side, InnerState.h:289-305)
     for (int32_t r = 0; r < nrhs; ++r) {
-      pfr::RhsArgs rd;
-      rd.B = B + r * b_rhs_stride + q0 * b_stride;
-      rd.b_stride = b_stride;
-      rd.nvalid = nv;
-      if (!transpose) {
-        if ((rc = solve_all(s, v, op, 0, 1, rd, nullptr, s->Y, st))) return rc;
-        if ((rc = solve_all(s, v, op, 1, 1, rd, s->Y, s->X, st))) return rc;
-      }
+      const pfr::RhsArgs rd{.B = B + r * b_rhs_stride + q0 * b_stride, .b_stride = b_stride, .nvalid = nv};
+      const pfr::Tri up = transpose ? pfr::TRI_UT : pfr::TRI_L, down = transpose ? pfr::TRI_LT : pfr::TRI_U;
+      const auto solve = [&] {   // the bottom-up and the top-down pass of the system solved: L, U or U^T, L^T
+        const int e = solve_all(s, v, op, up, pfr::RHS_BATCH, rd, nullptr, s->Y, st);
+        return e ? e : solve_all(s, v, op, down, pfr::RHS_BATCH, rd, s->Y, s->X, st);
+      };
+      if (!transpose && (rc = solve())) return rc;
       if (r == 0) {
         record(s, 2, st);
         record(s, 3, st);
       }
-      if (transpose) {
-        if ((rc = solve_all(s, v, op, 2, 1, rd, nullptr, s->Y, st))) return rc;
-        if ((rc = solve_all(s, v, op, 3, 1, rd, s->Y, s->X, st))) return rc;
-      }
-      const int which = transpose ? 1 : 0;
+      if (transpose && (rc = solve())) return rc;
+      const Walk::Sys which = transpose ? Walk::ADJOINT : Walk::FORWARD;
       const double2* dq = data + q0 * data_stride;
       if (s->check_mode & PFR_CHECK_REFINE) {
         // x += A^{-1} (b - A x) (or the transposed system) on the same factors
-        check_solution(s, v, op, which, 1, 1, rd, dq, data_stride, nv, s->X, s->G, r == 0 ? q0 : -1, st);
+        run_walk(s, v, op, Walk::residual(which, pfr::RHS_BATCH, rd, s->X, s->G).on_batch(dq, data_stride), nv, st);
         const pfr::RhsArgs rr = rhs_vector(s->G);
-        if ((rc = solve_all(s, v, op, transpose ? 2 : 0, 2, rr, nullptr, s->Y, st))) return rc;
-        if ((rc = solve_all(s, v, op, transpose ? 3 : 1, 0, rr, s->Y, s->XA, st))) return rc;
+        if ((rc = solve_all(s, v, op, up, pfr::RHS_VECTOR, rr, nullptr, s->Y, st))) return rc;
+        if ((rc = solve_all(s, v, op, down, pfr::RHS_OPERATOR, rr, s->Y, s->XA, st))) return rc;
         pfr::launch_axpy_vec(s->X, s->XA, (int64_t)s->n * Fc, st);
       }
       if (s->check_mode & (transpose ? PFR_CHECK_ADJOINT : PFR_CHECK_FORWARD))
-        check_solution(s, v, op, which, 1, 1, rd, dq, data_stride, nv, s->X, nullptr, r == 0 ? q0 : -1, st);
+        run_walk(s, v, op, Walk::checked(which, pfr::RHS_BATCH, rd, s->X, r == 0 ? q0 : -1).on_batch(dq, data_stride), nv, st);
       pfr::launch_unpermute(s->P.perm, s->n, s->X, Fc, nv, Xo + r * x_rhs_stride + q0 * s->n, st);
     }
     record(s, 4, st);

@@ -3728,7 +3728,7 @@ void launch_schur_blk(const DevPattern& P, const int4* blocks, int nblocks, cons
   LAUNCH((k_schur_sym_blk<4, 1, 16>), dim3(nblocks, ngroups), dim3(64 * 16), st, P, blocks, nblocks, bg1, bgxp, bgx, F, Fc);
 }
 
-void launch_assemble(int mode, const int4* recs, int nrec, const int* xptr, const int2* xl, int ngroups, double2* F,
+void launch_assemble(Mat mode, const int4* recs, int nrec, const int* xptr, const int2* xl, int ngroups, double2* F,
                      int64_t Fc, const ChunkOp& op, const double2* data, int64_t ds, int nvalid, hipStream_t st) {
   if (nrec <= 0) return;
   dispatch([&](auto md, auto pop) {
@@ -3775,7 +3775,7 @@ void launch_front0(const DevPattern& P, const int* fl, const FactorLevel& r, con
   part(std::integral_constant<int, F0_NS>{}, r.f0_small, r.nf - r.f0_small);
 }
 
-void launch_offdiag(int mode, const DevPattern& P, const int4* items, const FactorLevel& r, const int2* orec,
+void launch_offdiag(Mat mode, const DevPattern& P, const int4* items, const FactorLevel& r, const int2* orec,
                     const int* oxp, const int2* ox, int ngroups, double2* F, int64_t Fc, const ChunkOp& op,
                     const double2* data, int64_t ds, int nvalid, hipStream_t st) {
   const int nitems = r.nitems;
@@ -3790,16 +3790,16 @@ void launch_offdiag(int mode, const DevPattern& P, const int4* items, const Fact
   }, pick<0, 1>(mode), flag(r.off_small), pick<2, 3>(mode == 0 ? r.off_pu : 2), flag(mode == 0 && op.pop.member));
 }
 
-void launch_solve(int which, int rhs_mode, bool sym, const DevPattern& P, const int* lvl, const SolveLevel& r, int ngroups,
+void launch_solve(Tri which, Rhs rhs_mode, bool sym, const DevPattern& P, const int* lvl, const SolveLevel& r, int ngroups,
                   const double2* F, int64_t Fc, double2* WV, const RhsArgs& R, const PopArgs& pop, const double2* Yin,
                   double2* Out, const int* reach, hipStream_t st, const int* glist) {
-  const int nfronts = r.nf, split = which == 0 ? r.split_L : which == 1 ? r.split_U : 1;
+  const int nfronts = r.nf, split = which == TRI_L ? r.split_L : which == TRI_U ? r.split_U : 1;
   if (nfronts <= 0) return;
   dim3 g(nfronts, ngroups), b(64 * r.waves);
   const dim3 gs(nfronts * split, ngroups), bs(64 * SPLIT_W);
   const int rs = split > 1;
   switch (which) {
-    case 0:  // L solve (split > 1: the update rows by k_lsolve_rows over `split` workgroups per front)
+    case TRI_L:  // L solve (split > 1: the update rows by k_lsolve_rows over `split` workgroups per front)
       // a population sweep's operator right-hand side (rhs_mode 0 / 3): the POP forms, with the member's beta
       dispatch([&](auto rh, auto pp) {
         if constexpr (rhs_op(CV(rh)) || !CV(pp))
@@ -3808,13 +3808,13 @@ void launch_solve(int which, int rhs_mode, bool sym, const DevPattern& P, const 
       }, pick<0, 1, 2, 3>(rhs_mode), flag(pop.member && rhs_op(rhs_mode)));
       if (rs) LAUNCH(k_lsolve_rows, gs, bs, st, P, lvl, F, Fc, WV, split, glist);
       break;
-    case 1:  // U solve (split > 1: the pivot rows' update part first, by k_usolve_upd)
+    case TRI_U:  // U solve (split > 1: the pivot rows' update part first, by k_usolve_upd)
       with_bool(sym, [&](auto sy) {
         if (rs) LAUNCH(k_usolve_upd<CV(sy)>, gs, bs, st, P, lvl, F, Fc, WV, Yin, Out, reach, split, glist);
         LAUNCH(k_usolve_level<CV(sy)>, g, b, st, P, lvl, F, Fc, WV, Yin, Out, reach, rs, glist);
       });
       break;
-    case 2:  // U^T solve
+    case TRI_UT:  // U^T solve
       with_int<0, 1, 2>(rhs_mode, [&](auto rh) {
         LAUNCH(k_utsolve_level<CV(rh)>, g, b, st, P, lvl, F, Fc, WV, R, Out, reach);
       });
@@ -3825,7 +3825,7 @@ void launch_solve(int which, int rhs_mode, bool sym, const DevPattern& P, const 
   }
 }
 
-void launch_lsolve_multi(int rhs_mode, const DevPattern& P, int nslices, const int* const* lvl, const ChainLevel& r,
+void launch_lsolve_multi(Rhs rhs_mode, const DevPattern& P, int nslices, const int* const* lvl, const ChainLevel& r,
                          int ngroups, const double2* F, int64_t Fc, double2* const* WV, const RhsArgs* rd,
                          const PopArgs& pop, double2* const* Y, const int* const* reach, hipStream_t st) {
   LSlices S{};
@@ -3935,7 +3935,7 @@ void launch_tangent_spmv(const int* ptr, const int* idx, const int* nzs, int nro
 }
 
 
-void launch_residual(int mode, int rhs, const ResidArgs& a, int n_stiff, int unroll, const PopArgs& pop, const double2* X,
+void launch_residual(Mat mode, Rhs rhs, const ResidArgs& a, int n_stiff, int unroll, const PopArgs& pop, const double2* X,
                      int64_t Fc, double2* R, double* acc, hipStream_t st, const double2* Mu, double2* cpart) {
   if (pop.member && mode != 0) return;                   // explicit batches have no population form
   // the variant: mode 0 walks rhs 0 or 2, mode 1 rhs 1 or 2
@@ -4063,7 +4063,7 @@ void launch_matvec(const int* colptr, const int* rowind, int n, const double2* d
          batch);
 }
 
-void launch_dirichlet_rhs(int src, const DirArgs& d, const PopArgs& pop, int n_crow, const RhsArgs& r, double2* G,
+void launch_dirichlet_rhs(Rhs src, const DirArgs& d, const PopArgs& pop, int n_crow, const RhsArgs& r, double2* G,
                           double2* Bc, int64_t Fc, hipStream_t st) {
   if (n_crow <= 0) return;
   dispatch([&](auto sr, auto pp) {

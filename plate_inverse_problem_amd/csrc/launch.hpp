@@ -18,6 +18,16 @@ struct ChunkOp {
   PopArgs pop;
 };
 
+// The integer codes of the launchers by name.  The values are the kernels' template values (MODE, RHS) and the
+// solver's reach indices: a launcher maps an enumerator to the instantiation, the kernels keep their int parameters.
+enum Tri { TRI_L = 0, TRI_U = 1, TRI_UT = 2, TRI_LT = 3 };   // triangular pass: L, U^T bottom-up; U, L^T top-down
+// right-hand-side source: the operator's, an explicit batch B, a permuted vector G, the operator's with the
+// Dirichlet corrections in their slots (symmetric mode with coupled rows)
+enum Rhs { RHS_OPERATOR = 0, RHS_BATCH = 1, RHS_VECTOR = 2, RHS_OPERATOR_DIR = 3 };
+// the fronts a solve visits: all, the rhs reach, the functional support's reach (SolverView::d_reach)
+enum Reach { REACH_ALL = -1, REACH_RHS = 0, REACH_SUPPORT = 1 };
+enum Mat { MAT_OPERATOR = 0, MAT_BATCH = 1 };                // matrix source: the chunk operator, an explicit batch
+
 // the first launch configuration refused since the last call (a kernel's dynamic LDS size), NULL: none; the
 // refused launch was skipped
 const char* launch_refused();
@@ -27,9 +37,9 @@ void launch_combine(const double* stiff, int n_stiff, int64_t nnz, const CoefPac
 // bitwise launch_combine's K
 void launch_combine_batch(const double* stiff, int n_stiff, int64_t nnz, const double2* coef, int n_members,
                           double2* K, hipStream_t st);
-// mode 0: the operator op (a population sweep's: every 64-lane group assembled from its member's K; so too in
-// launch_front0 / launch_offdiag); mode 1: the explicit batch (data, ds, nvalid)
-void launch_assemble(int mode, const int4* recs, int nrec, const int* xptr, const int2* xl, int ngroups, double2* F,
+// MAT_OPERATOR: the operator op (a population sweep's: every 64-lane group assembled from its member's K; so too in
+// launch_front0 / launch_offdiag); MAT_BATCH: the explicit batch (data, ds, nvalid)
+void launch_assemble(Mat mode, const int4* recs, int nrec, const int* xptr, const int2* xl, int ngroups, double2* F,
                      int64_t Fc, const ChunkOp& op, const double2* data, int64_t ds, int nvalid, hipStream_t st);
 // The launchers of a tree level take the level's record of the solver's schedule (plan.hpp: FactorLevel, PairLevel,
 // ChainLevel, SolveLevel) and only map it to a kernel instantiation, grid and block.
@@ -45,7 +55,7 @@ void launch_front0(const DevPattern& P, const int* fl, const FactorLevel& r, con
                    int ngroups, double2* F, int64_t Fc, const ChunkOp& op, int* flags, hipStream_t st);
 // L21 rows (and U12 columns in general mode) of a level's items; r.off_pu 3: the software-pipelined prefix
 // (operator-form launches)
-void launch_offdiag(int mode, const DevPattern& P, const int4* items, const FactorLevel& r, const int2* orec,
+void launch_offdiag(Mat mode, const DevPattern& P, const int4* items, const FactorLevel& r, const int2* orec,
                     const int* oxp, const int2* ox, int ngroups, double2* F, int64_t Fc, const ChunkOp& op,
                     const double2* data, int64_t ds, int nvalid, hipStream_t st);
 // Schur complement A22 -= L21 U12 for a level's tile list (TM x TN = 4 x 4 tiles)
@@ -54,20 +64,19 @@ void launch_schur(bool sym, const DevPattern& P, const int4* tiles, int ntiles, 
 // symmetric mode, large update blocks: 16 x 16 blocks, operands staged in LDS per workgroup
 void launch_schur_blk(const DevPattern& P, const int4* blocks, int nblocks, const int* bg1, const int* bgxp,
                       const int2* bgx, int ngroups, double2* F, int64_t Fc, hipStream_t st);
-// which: 0 = L (bottom-up), 1 = U (top-down), 2 = U^T (bottom-up), 3 = L^T (top-down)
 // r.split_L / r.split_U > 1 (L and U solves): the update part of every front (L: the update rows; U: the pivot rows'
 // products with the update-row solution) runs first / last over that many workgroups of SPLIT_W waves per
 // (front, frequency group) -- the top levels' few fronts otherwise pull their L21 blocks through one CU each
 // glist (may be NULL): the groups to solve, REFINE_CAP of them (-1: none), indexed by grid row (pass
 // ngroups = REFINE_CAP); the selective adjoint refinement's solves
-// pop (the chunk operator's): a population sweep's L solve of the operator rhs (rhs_mode 0 / 3) takes its POP form
-void launch_solve(int which, int rhs_mode, bool sym, const DevPattern& P, const int* lvl, const SolveLevel& r, int ngroups,
+// pop (the chunk operator's): a population sweep's L solve of the operator rhs (RHS_OPERATOR / _DIR) takes its POP form
+void launch_solve(Tri which, Rhs rhs_mode, bool sym, const DevPattern& P, const int* lvl, const SolveLevel& r, int ngroups,
                   const double2* F, int64_t Fc, double2* WV, const RhsArgs& rd, const PopArgs& pop, const double2* Yin,
                   double2* Out, const int* reach, hipStream_t st, const int* glist = nullptr);
 // nslices (<= 4) bottom-up L solves as one chain of launches (blockIdx.z = slice; slice z: the fronts
-// lvl[z][0 .. r.nf0 or r.nf1), its work vectors WV[z], rhs rd[z] (rhs_mode 0 or 3 for every slice), solution Y[z]);
+// lvl[z][0 .. r.nf0 or r.nf1), its work vectors WV[z], rhs rd[z] (RHS_OPERATOR or _DIR for every slice), solution Y[z]);
 // pop (population sweep): slice 0's rhs with the member's beta
-void launch_lsolve_multi(int rhs_mode, const DevPattern& P, int nslices, const int* const* lvl, const ChainLevel& r,
+void launch_lsolve_multi(Rhs rhs_mode, const DevPattern& P, int nslices, const int* const* lvl, const ChainLevel& r,
                          int ngroups, const double2* F, int64_t Fc, double2* const* WV, const RhsArgs* rd,
                          const PopArgs& pop, double2* const* Y, const int* const* reach, hipStream_t st);
 // functional from the bottom-up passes: partial dot products (FN_PARTS x 3 x Fc), the functional / loss
@@ -110,23 +119,23 @@ void launch_contract_q(const int4* ent, int nent, const double* se, int n_stiff,
                        int n, int64_t Fc, double2* kpart, hipStream_t st);
 void launch_jac_finish(const double2* kpart, int nparts, int n_stiff, const double2* msc, const double2* t_q,
                        const CoefPack& e, int nvalid, int64_t Fc, double2* jc, hipStream_t st);
-// symmetric mode: forward right-hand-side corrections (src 0: operator rhs -> Bc; src 2: G in
+// symmetric mode: forward right-hand-side corrections (RHS_OPERATOR: operator rhs -> Bc; RHS_VECTOR: G in
 // place) and the adjoint's Dirichlet rows (X in place); pop (population sweep): K and the rhs scale of the
 // group's member
-void launch_dirichlet_rhs(int src, const DirArgs& d, const PopArgs& pop, int n_crow, const RhsArgs& rd, double2* G,
+void launch_dirichlet_rhs(Rhs src, const DirArgs& d, const PopArgs& pop, int n_crow, const RhsArgs& rd, double2* G,
                           double2* Bc, int64_t Fc, hipStream_t st);
 void launch_dirichlet_post(const DirArgs& d, const PopArgs& pop, int n_dir, double2* X, int64_t Fc, hipStream_t st,
                            const int* glist = nullptr);
 // Backward-error check: the original system's rows (forward) or columns (adjoint) in the permuted
-// numbering, A = K - omega^2 M (mode 0) or the explicit batch (mode 1); rhs 0 operator, 1 explicit
-// B, 2 vector G.  The per-frequency componentwise backward error accumulates in acc (max, zero on
+// numbering, A = K - omega^2 M (MAT_OPERATOR) or the explicit batch (MAT_BATCH); rhs RHS_OPERATOR, RHS_BATCH or
+// RHS_VECTOR.  The per-frequency componentwise backward error accumulates in acc (max, zero on
 // entry); acc == NULL: only the residual is written to R.
-// n_stiff (12 or 18, with a.se / a.kpart; else 0): the gradient contraction fused into the forward walk (mode 0,
-// rhs 0, Mu != NULL).  unroll: entries per gather batch of the adjoint check walk (4 or 8; the same bits).
-// pop (population sweep, mode 0): K and beta of the group's member.
-// Mu != NULL (mode 0, rhs 0): also the functional-correction dot products sum_p Mu_p r_p, one partial
+// n_stiff (12 or 18, with a.se / a.kpart; else 0): the gradient contraction fused into the forward walk (MAT_OPERATOR,
+// RHS_OPERATOR, Mu != NULL).  unroll: entries per gather batch of the adjoint check walk (4 or 8; the same bits).
+// pop (population sweep, MAT_OPERATOR): K and beta of the group's member.
+// Mu != NULL (MAT_OPERATOR, RHS_OPERATOR): also the functional-correction dot products sum_p Mu_p r_p, one partial
 // per workgroup and frequency in cpart (residual_parts(n) x Fc), summed by launch_correct_finish
-void launch_residual(int mode, int rhs, const ResidArgs& a, int n_stiff, int unroll, const PopArgs& pop, const double2* X,
+void launch_residual(Mat mode, Rhs rhs, const ResidArgs& a, int n_stiff, int unroll, const PopArgs& pop, const double2* X,
                      int64_t Fc, double2* R, double* acc, hipStream_t st, const double2* Mu = nullptr,
                      double2* cpart = nullptr);
 // partial[t * n_stiff + k] = sum_{q in tile t} msc[q] sum_b kpart[b][k][q] (msc NULL: 1; tiles of 64
@@ -140,6 +149,37 @@ void launch_reduce_q(const double2* kpart, int nparts, int n_stiff, const double
 void launch_correct_finish(const FunctionalArgs& A, const double* fr0, const double2* cpart, int nparts, int64_t Fc,
                            int nvalid, int64_t q0, double* fr_out, double* loss_terms, double2* mscale,
                            const ChunkOp& op, hipStream_t st, double* gind = nullptr, double2* tq = nullptr);
+// One residual walk as a value: which system of the original matrix, which matrix and right-hand side, the solution X
+// (permuted, frequency-minor), which groups, and exactly one of three outputs.  Built by residual, checked or
+// correction (+ on_batch / on_groups); the solver maps it to launch_residual and launch_berr_finish.
+struct Walk {
+  enum Sys { FORWARD = 0, ADJOINT = 1 };   // A x = b over the rows; A^T l = g over the columns
+  Sys sys = FORWARD;
+  Mat mat = MAT_OPERATOR;                // the chunk operator, or the explicit batch (data, ds)
+  const double2* data = nullptr;
+  int64_t ds = 0;
+  Rhs rhs = RHS_OPERATOR;                // operator, explicit B or vector G, in rd
+  RhsArgs rd;
+  const double2* X = nullptr;
+  const int* glist = nullptr;            // the groups walked (REFINE_CAP of them; NULL: every group)
+  double2* R = nullptr;                  // output 1: the residual b - A x (a refinement step); nothing is checked
+  bool check = false;                    // output 2: the backward error -> the chunk's flags and (q0 >= 0) the caller's
+  int64_t q0 = -1;                       //           berr slots from q0 on
+  const double2* Mu = nullptr;           // output 3: the functional correction's dot products with Mu, with `check`
+  bool contract = false;                 //           too if asked, and with the gradient contraction fused in
+  static Walk residual(Sys sys, Rhs rhs, const RhsArgs& rd, const double2* X, double2* R) {
+    return {.sys = sys, .rhs = rhs, .rd = rd, .X = X, .R = R};
+  }
+  static Walk checked(Sys sys, Rhs rhs, const RhsArgs& rd, const double2* X, int64_t q0) {
+    return {.sys = sys, .rhs = rhs, .rd = rd, .X = X, .check = true, .q0 = q0};
+  }
+  // the forward walk of the operator system (rd: the operator's rhs)
+  static Walk correction(const RhsArgs& rd, const double2* X, const double2* Mu, bool check, int64_t q0, bool contract) {
+    return {.rd = rd, .X = X, .check = check, .q0 = q0, .Mu = Mu, .contract = contract};
+  }
+  Walk& on_batch(const double2* d, int64_t stride) { mat = MAT_BATCH; data = d; ds = stride; return *this; }
+  Walk& on_groups(const int* g) { glist = g; return *this; }
+};
 // glist[0 .. REFINE_CAP): the groups with the largest indicators above tol, largest first, -1 past them
 void launch_select_groups(const double* gind, int ngroups, double tol, int* glist, hipStream_t st);
 // flags |= flag where acc[q] > tol (or not finite); acc cleared
