@@ -21,6 +21,7 @@ import json
 import os
 import warnings
 import weakref
+from types import SimpleNamespace
 from typing import Callable
 
 import numpy as np
@@ -108,6 +109,14 @@ class _LaneThread:
         self._th.join()
 
 
+# (kind of sweep, sensing axis given) -> (the _native.Solver method of a lane's call, its keyword for the response);
+# a new kind of sweep is one more row here and one public _Engine method that states its request (_lane_request)
+_LANE_CALLS = {("sweep", False): ("sweep", "fr"), ("sweep", True): ("sweep_complex", "h"),
+               ("jacobian", False): ("jacobian_sweep", "fr"), ("jacobian", True): ("jacobian_sweep_complex", "h"),
+               ("population", False): ("population_sweep", "fr"), ("hessian", False): ("hessian_sweep", None)}
+_NO_ARGS = {}
+
+
 class _Engine:
     """Device state of one Problem: symbolic analysis, operator data and ``lanes``
     solvers, each with its own workspace and HIP stream.  A sweep splits its
@@ -149,7 +158,7 @@ class _Engine:
                             max_ns=int(env("PFR_MAX_NS")) if env("PFR_MAX_NS") else None,
                             md_delta=int(env("PFR_MD_DELTA")) if env("PFR_MD_DELTA") else None)
         self._leaf_env = int(env("PFR_LEAF_SIZE")) if env("PFR_LEAF_SIZE") else None
-        self._syms = {}
+        self._syms, self.sym = {}, None
         self._use_symbolic(n_freqs)
         self._lanes_req = int(os.environ.get("PFR_LANES", "2")) if lanes is None else int(lanes)
         self._lane_freqs = max(64, int(os.environ.get("PFR_LANE_FREQS", "256")))   # frequencies per lane at least
@@ -159,6 +168,8 @@ class _Engine:
         self.n_lanes = 0
         self._seeded = False
         self._sized_for = set()
+        self._step_bufs, self._step_views = {}, {}      # loss_step's buffers and lane request: one shape at a time
+        self._kidx_dev = (None, None)                   # expand's index on the device it was last used on
         # the coefficient matrices contracted for the gradient: all 18, or the 12 of A and D when the
         # coupling coefficients B vanish identically (mid-plane symmetric materials: dB/dtheta = 0, so
         # their gradient partials are exactly zero and need not be formed)
@@ -219,7 +230,7 @@ class _Engine:
         leaf = self.leaf_size_for(n_freqs)
         if leaf not in self._syms:
             self._syms[leaf] = _native.Symbolic(*self._sym_args, leaf_size=leaf, **self._sym_kw)
-        changed = getattr(self, "sym", None) is not self._syms[leaf]
+        changed = self.sym is not self._syms[leaf]
         self.sym = self._syms[leaf]
         self.stats = self.sym.stats()
         return changed
@@ -249,7 +260,7 @@ class _Engine:
         free += sum(self.sym.workspace_bytes(sv.max_batch) + (n * sv.max_batch * 16 if self._seeded else 0)
                     for sv in self.solvers)
         per64 = self.sym.workspace_bytes(64)
-        if getattr(self, "check_mode", 0) & _native.PFR_CHECK_REFINE_ADJ:
+        if self.check_mode & _native.PFR_CHECK_REFINE_ADJ:
             per64 += n * 64 * 16     # the refinement's fr seed vector (n x Fc), allocated on first use
         cap = max(64, min(4096, int(0.85 * free / n_lanes / per64) * 64))
         n_chunks = -(-per_lane // cap)
@@ -340,7 +351,7 @@ class _Engine:
         # the index on the device once: a per-call host->device copy of it blocked the host until the
         # sweep had finished, so the small kernels after the sweep were only enqueued then
         key = str(v.device)
-        if getattr(self, "_kidx_dev", (None, None))[0] != key:
+        if self._kidx_dev[0] != key:
             self._kidx_dev = (key, torch.as_tensor(self.kidx, device=v.device))
         out[..., self._kidx_dev[1]] = v
         return out
@@ -422,41 +433,120 @@ class _Engine:
             with torch.cuda.device(self.device), torch.cuda.stream(st):
                 call(sv, lo, hi, bufs)
 
-        err = None
-        if len(jobs) > 1 and self._pool is not None:
-            # lanes 1.. on their threads, lane 0 on this thread meanwhile (one thread handoff less before the
-            # first launch: the GPU idles from the previous step's result until then)
-            for t, j in zip(self._pool, jobs[1:]):
-                t.submit(lane, j)
-            if _HT is not None:
-                _HT("submitted")
-            try:
-                lane(jobs[0])
-            except Exception as e:           # noqa: BLE001 -- re-raised once every lane is joined
-                err = e
-            errs = [t.result() for t, _ in zip(self._pool, jobs[1:])]   # every lane has issued its work (or failed) ...
-            errs = [e for e in errs if e is not None]
-            err = err if err is not None else (errs[0] if errs else None)
-        else:
-            for j in jobs:
+        errs, waiting, mine = [], [], jobs
+        try:
+            if len(jobs) > 1 and self._pool is not None:
+                # lanes 1.. on their threads, lane 0 on this thread meanwhile (one thread handoff less before the
+                # first launch: the GPU idles from the previous step's result until then)
+                mine = jobs[:1]
+                for t, j in zip(self._pool, jobs[1:]):
+                    t.submit(lane, j)
+                    waiting.append(t)
+                if _HT is not None:
+                    _HT("submitted")
+            for j in mine:
                 try:
                     lane(j)
                 except Exception as e:       # noqa: BLE001 -- re-raised once every lane is joined
-                    err = e
+                    errs.append(e)
                     break
-        for i, _, st, _, _, bufs in jobs:    # ... and the current stream is ordered after all of them
-            _native.stream_order(cur_h, st.cuda_stream)
-            for b in bufs:
-                if b is not None:
-                    b.record_stream(cur)
-        if err is not None:
-            raise err
+        finally:
+            # whatever this thread's lane raised -- a BaseException such as KeyboardInterrupt passes through here --
+            # every submitted lane's result is collected (left in its queue it would answer the NEXT call's wait,
+            # before that call's lane had issued anything): every lane has issued its work (or failed) ...
+            errs += [e for e in [t.result() for t in waiting] if e is not None]
+            for i, _, st, _, _, bufs in jobs:    # ... and the current stream is ordered after all of them
+                _native.stream_order(cur_h, st.cuda_stream)
+                for b in bufs:
+                    if b is not None:
+                        b.record_stream(cur)
+        if errs:
+            raise errs[0]
         if lane_bufs is not None:
             return
         for _, _, st, _, _, bufs in jobs:
             for a, b in zip(accum, bufs):
                 if a is not None and b is not a:
                     a.add_(b)
+
+    def _lane_request(self, kind, n, per_freq, axis=None, resp=None, berr=None, per_group=None, own=None, **fixed):
+        """A sweep request as what each lane calls: ``(Solver method, {lo: (the lane's rows of berr, its keyword
+        arguments)})`` over the lanes that sweep some of ``n`` frequencies.  ``kind`` and whether a sensing ``axis`` (3
+        real numbers) is given pick the method (``_LANE_CALLS``).  This is the one place the per-frequency tensors --
+        ``per_freq`` by the method's names, the response ``resp`` (float64, or complex128 with an axis) under the
+        method's name for it, ``berr`` (n, 2); None stays None -- are cut into the lanes' ``[lo:hi]`` blocks, and
+        ``per_group``'s host arrays (a population's member table) into their entries per 64-frequency group; the
+        ``fixed`` arguments go to every lane as they are.  ``own`` (names, one buffer list per lane): the lanes'
+        accumulators are the caller's; the arguments are then complete, with them and the lane's stream handle
+        (``loss_step``, which keeps the request across steps: cutting costs host time on the turnaround)."""
+        method, resp_name = _LANE_CALLS[kind, axis is not None]
+        if resp is not None:
+            per_freq = {**per_freq, resp_name: resp if axis is None else torch.view_as_real(resp)}
+        if axis is not None:
+            fixed["axis"] = axis
+        cut = lambda t, lo, hi: None if t is None else t[lo:hi]              # noqa: E731
+        lanes = {}
+        for i, (lo, hi) in enumerate(self._split(n)):
+            if hi > lo:
+                kw = {**{k: cut(t, lo, hi) for k, t in per_freq.items()}, **fixed,
+                      **{k: a[lo // 64:(hi + 63) // 64] for k, a in (per_group or {}).items()}}
+                if own is not None:
+                    kw.update(zip(own[0], own[1][i]), stream=self.streams[i].cuda_stream)
+                lanes[lo] = (cut(berr, lo, hi), kw)
+        return method, lanes
+
+    def _sweep_lanes(self, request, n, accum, mode=None, lane_bufs=None):
+        """Run a ``_lane_request`` on every lane -- every sweep of the engine goes through here.  ``accum`` ({name:
+        tensor}) is accumulated over the lanes by ``_run``, unless the request came with the caller's own per-lane
+        buffers ``lane_bufs``: the lanes then issue native work only (``_run``'s ``raw``).  A lane with rows of
+        ``berr`` has its backward errors pointed at them, its solver checked in ``mode`` (default: the engine's), for
+        this call only."""
+        method, lanes = request
+        mode = self.check_mode if mode is None else mode
+        if mode & _native.PFR_CHECK_REFINE_ADJ and method != "hessian_sweep":
+            self._seeded = True        # the lanes allocate their refinement seed vectors in this sweep
+        names = tuple(accum)
+
+        def call(sv, lo, hi, bufs, stream=None):
+            vb, kw = lanes[lo]
+            if vb is not None:
+                sv.set_check(mode, self.check_tol, vb)
+            try:
+                getattr(sv, method)(**kw, **(_NO_ARGS if lane_bufs is not None else dict(zip(names, bufs))))
+            finally:
+                if vb is not None:
+                    sv.set_check(self.check_mode, self.check_tol)
+        if lane_bufs is None:
+            self._run(call, n, [accum[k] for k in names])
+        else:
+            self._run(call, n, None, lane_bufs=lane_bufs, raw=True)
+
+    def outputs(self, n, dtype=torch.float64, jc=False):
+        """``(response, flags, berr, jc)`` of an ``n``-frequency sweep, on the device: the response (n,) of ``dtype``
+        (float64: fr, complex128: H; None: none), the status flags (int32, zero), the backward errors (n, 2) (NaN:
+        not checked) and, when asked, the Jacobian rows (n, n_stiff) complex (else None)."""
+        dev = self.device
+        return (None if dtype is None else torch.empty(n, dtype=dtype, device=dev),
+                torch.zeros(n, dtype=torch.int32, device=dev),
+                torch.full((n, 2), float('nan'), dtype=torch.float64, device=dev),
+                torch.empty((n, self.n_stiff), dtype=torch.complex128, device=dev) if jc else None)
+
+    def accumulators(self):
+        """``(loss (1,) float64, w (n_stiff,) complex128)``, zero on the device: what a loss sweep accumulates into."""
+        return (torch.zeros(1, dtype=torch.float64, device=self.device),
+                torch.zeros(self.n_stiff, dtype=torch.complex128, device=self.device))
+
+    def record(self, flags, berr, flagged=None):
+        """A finished sweep's backward errors and flags become ``last_berr`` and ``last_flags`` (host; RuntimeWarning
+        for the flagged frequencies, ``_check_flags``).  ``flagged``: their number where the caller has it on the
+        host already -- the flags are copied only when it is not zero."""
+        self.last_berr = berr
+        if flags is None:
+            self.last_flags = None
+        elif flagged is not None and not flagged:
+            self.last_flags = np.zeros(flags.numel(), np.int32)
+        else:
+            self.last_flags = _check_flags(flags)
 
     def loss_step(self, freqs, loss_type, ref, scale, axis=None):
         """One loss + gradient sweep with the step buffers reused across calls (the optimiser / bench loop:
@@ -467,7 +557,7 @@ class _Engine:
         the magnitude fr): the loss of the complex response along it (``Solver.sweep_complex``, a LOSS_C* id)."""
         n = freqs.numel()
         key = (n, self.n_lanes, id(self.solvers[0]))
-        b = self._step_bufs.get(key) if hasattr(self, "_step_bufs") else None
+        b = self._step_bufs.get(key)
         L, m = self.n_lanes, 2 + 2 * self.n_stiff
         if b is None:
             # the lanes' loss / w slots (float64) and the flags (int32) in one device buffer: one device->host
@@ -482,31 +572,18 @@ class _Engine:
         acc, lanes, flags, berr, raw, host, done = b
         # no fills here: every lane's sweep initialises its loss / w slots, flags and backward errors in its first
         # kernel (pfr_sweep_fresh)
-        # the lanes' views of this step's tensors, made once per (buffers, freqs, ref): slicing costs host time
-        # on the step-to-step turnaround
-        vkey = (key, freqs.data_ptr(), ref.data_ptr(), freqs.numel())
-        views = self._step_views.get(vkey) if hasattr(self, "_step_views") else None
+        # the step's lane request, made once per (buffers, freqs, ref, loss, scale, axis): cutting the tensors and
+        # putting a lane's arguments together costs host time on the step-to-step turnaround
+        vkey = (key, freqs.data_ptr(), ref.data_ptr(), freqs.numel(), loss_type, scale,
+                axis if axis is None else tuple(axis))
+        views = self._step_views.get(vkey)
         if views is None:
-            views = {lo: (berr[lo:hi], freqs[lo:hi], ref[lo:hi], flags[lo:hi]) for lo, hi in self._split(n)}
             ran = [hi > lo for lo, hi in self._split(n)]
-            views["_act"] = None if all(ran) else np.nonzero(ran)[0]
+            views = (self._lane_request("sweep", n, dict(freqs=freqs, ref=ref, flags=flags), axis=axis, berr=berr,
+                                        own=(("loss", "w"), lanes), loss_type=loss_type, scale=scale, fresh=True),
+                     None if all(ran) else np.nonzero(ran)[0])
             self._step_views = {vkey: views}
-
-        def call(sv, lo, hi, bufs, stream):
-            vb, vf, vr, vfl = views[lo]
-            sv.set_check(self.check_mode, self.check_tol, vb)
-            try:
-                if axis is None:
-                    sv.sweep(vf, loss_type, ref=vr, scale=scale, loss=bufs[0], w=bufs[1], flags=vfl, fresh=True,
-                             stream=stream)
-                else:
-                    sv.sweep_complex(vf, axis, loss_type, ref=vr, scale=scale, loss=bufs[0], w=bufs[1], flags=vfl,
-                                     fresh=True, stream=stream)
-            finally:
-                sv.set_check(self.check_mode, self.check_tol)
-        if self.check_mode & _native.PFR_CHECK_REFINE_ADJ:
-            self._seeded = True
-        self._run(call, n, None, lane_bufs=lanes, raw=True)
+        self._sweep_lanes(views[0], n, (), lane_bufs=lanes)
         # the result into pinned memory and the host polling for it: a blocking copy returned ~85 us after the copy
         # had finished on the GPU (the host thread woken from its sleep, gpurun_out/tl/timeline.txt) -- GPU idle
         # before the next step's first launch.  PFR_STEP_WAIT=block: the blocking copy.
@@ -521,10 +598,9 @@ class _Engine:
         else:
             hb = raw.cpu().numpy()
         h = hb[:8 * L * m].view(np.float64).reshape(L, m)
-        self.last_flags_host = hb[8 * L * m:].view(np.int32).copy()
         # summed over the lanes that swept (a lane with no frequencies ran nothing: its slot was never initialised);
         # a lane's slot: loss, (unused), then its n_stiff partials as complex pairs
-        act = views["_act"]
+        act = views[1]
         tot = h[act].sum(axis=0) if act is not None else h.sum(axis=0)
         wk = tot[2:].view(np.complex128)
         if wk.size == 18:
@@ -533,64 +609,30 @@ class _Engine:
             w = np.zeros(18, dtype=np.complex128)
             w[self.kidx] = wk
         self.last_berr = berr
-        return float(tot[0]), w, flags, int(np.count_nonzero(self.last_flags_host))
+        return float(tot[0]), w, flags, int(np.count_nonzero(hb[8 * L * m:].view(np.int32)))
 
     def sweep(self, freqs, loss_type=_native.LOSS_NONE, ref=None, scale=1.0, fr=None, loss=None, w=None,
               flags=None, berr=None, axis=None):
         """``Solver.sweep`` over all lanes (fr / flags / berr (F, 2) written in place, loss / w
         accumulated).  ``axis`` (3 real numbers): ``Solver.sweep_complex`` instead, ``fr`` a complex128 tensor that
         receives the response H along the axis and ``loss_type`` one of the LOSS_C* ids."""
-        if self.check_mode & _native.PFR_CHECK_REFINE_ADJ:
-            self._seeded = True        # the lanes allocate their refinement seed vectors in this sweep
-
-        def call(sv, lo, hi, bufs):
-            if berr is not None:
-                sv.set_check(self.check_mode, self.check_tol, berr[lo:hi])
-            try:
-                if axis is None:
-                    sv.sweep(freqs[lo:hi], loss_type, ref=None if ref is None else ref[lo:hi], scale=scale,
-                             fr=None if fr is None else fr[lo:hi], loss=bufs[0], w=bufs[1],
-                             flags=None if flags is None else flags[lo:hi])
-                else:
-                    sv.sweep_complex(freqs[lo:hi], axis, loss_type, ref=None if ref is None else ref[lo:hi],
-                                     scale=scale, h=None if fr is None else torch.view_as_real(fr[lo:hi]),
-                                     loss=bufs[0], w=bufs[1], flags=None if flags is None else flags[lo:hi])
-            finally:
-                if berr is not None:
-                    sv.set_check(self.check_mode, self.check_tol)
-        self._run(call, freqs.numel(), [loss, w])
+        n = freqs.numel()
+        self._sweep_lanes(self._lane_request("sweep", n, dict(freqs=freqs, ref=ref, flags=flags), axis=axis, resp=fr,
+                                             berr=berr, loss_type=loss_type, scale=scale), n, dict(loss=loss, w=w))
 
     def hessian_sweep(self, freqs, loss_type, ref, scale, dcoef, loss=None, w=None, h=None, flags=None):
-        def call(sv, lo, hi, bufs):
-            sv.hessian_sweep(freqs[lo:hi], loss_type, ref[lo:hi], scale, dcoef, loss=bufs[0], w=bufs[1],
-                             h=bufs[2], flags=None if flags is None else flags[lo:hi])
-        self._run(call, freqs.numel(), [loss, w, h])
+        n = freqs.numel()
+        self._sweep_lanes(self._lane_request("hessian", n, dict(freqs=freqs, ref=ref, flags=flags), loss_type=loss_type,
+                                             scale=scale, dcoef=dcoef), n, dict(loss=loss, w=w, h=h))
 
     def jacobian_sweep(self, freqs, jc, fr=None, flags=None, berr=None, axis=None):
         """``Solver.jacobian_sweep`` over all lanes: every lane writes its own rows of ``jc`` (F, n_stiff) complex
         (and of fr / flags / berr (F, 2)); nothing is accumulated.  Sets ``last_berr`` and ``last_flags``.
         ``axis`` (3 real numbers): ``Solver.jacobian_sweep_complex``, ``fr`` a complex128 tensor for H."""
-        if self.check_mode & _native.PFR_CHECK_REFINE_ADJ:
-            self._seeded = True        # as sweep: the lanes allocate their refinement seed vectors
-
-        def call(sv, lo, hi, bufs):
-            if berr is not None:
-                sv.set_check(self.check_mode, self.check_tol, berr[lo:hi])
-            try:
-                if axis is None:
-                    sv.jacobian_sweep(freqs[lo:hi], torch.view_as_real(jc[lo:hi]),
-                                      fr=None if fr is None else fr[lo:hi],
-                                      flags=None if flags is None else flags[lo:hi])
-                else:
-                    sv.jacobian_sweep_complex(freqs[lo:hi], axis, torch.view_as_real(jc[lo:hi]),
-                                              h=None if fr is None else torch.view_as_real(fr[lo:hi]),
-                                              flags=None if flags is None else flags[lo:hi])
-            finally:
-                if berr is not None:
-                    sv.set_check(self.check_mode, self.check_tol)
-        self._run(call, freqs.numel(), [])
-        self.last_berr = berr
-        self.last_flags = _check_flags(flags) if flags is not None else None
+        n = freqs.numel()
+        self._sweep_lanes(self._lane_request("jacobian", n, dict(freqs=freqs, jc=torch.view_as_real(jc), flags=flags),
+                                             axis=axis, resp=fr, berr=berr), n, {})
+        self.record(flags, berr)
 
     def population_sweep(self, freqs, C, jac=True):
         """One sweep for a population of coefficient sets ``C`` (P, 18) complex over the same ``freqs`` (F,): a lane
@@ -617,25 +659,15 @@ class _Engine:
                 sv.set_rhs(self.rhs, complex(beta[0]), self.mass_sum)
             self._pruned_stats()
         f = freqs[torch.as_tensor(index, device=dev)].contiguous()
-        fr = torch.empty(L, dtype=torch.float64, device=dev)
-        jc = torch.empty((L, self.n_stiff), dtype=torch.complex128, device=dev) if jac else None
-        flags = torch.zeros(L, dtype=torch.int32, device=dev)
-        berr = torch.full((L, 2), float('nan'), dtype=torch.float64, device=dev)
-        mode = self.check_mode & ~_native.PFR_CHECK_REFINE_ADJ
-        Kr = torch.view_as_real(Kpop)
-
-        def call(sv, lo, hi, bufs):
-            sv.set_check(mode, self.check_tol, berr[lo:hi])
-            try:
-                sv.population_sweep(f[lo:hi], member[lo // 64:(hi + 63) // 64], Kr, beta, fr[lo:hi],
-                                    jc=None if jc is None else torch.view_as_real(jc[lo:hi]), flags=flags[lo:hi])
-            finally:
-                sv.set_check(self.check_mode, self.check_tol)
-        self._run(call, L, [])
+        fr, flags, berr, jc = self.outputs(L, jc=jac)
+        request = self._lane_request("population", L, dict(freqs=f, jc=None if jc is None else torch.view_as_real(jc),
+                                                           flags=flags),
+                                     resp=fr, berr=berr, per_group=dict(member=member), Kpop=torch.view_as_real(Kpop),
+                                     beta=beta)
+        self._sweep_lanes(request, L, {}, mode=self.check_mode & ~_native.PFR_CHECK_REFINE_ADJ)
         vm = torch.as_tensor(valid, device=dev)
         pick = lambda t: t[vm].reshape((P, F) + t.shape[1:])                 # noqa: E731
-        self.last_berr = pick(berr)
-        self.last_flags = _check_flags(pick(flags))
+        self.record(pick(flags), pick(berr))
         return pick(fr), None if jc is None else pick(jc), self.last_flags, self.last_berr
 
     # ---- measurement (bench.py)
@@ -661,41 +693,6 @@ def _coeffs18(transform, params: torch.Tensor) -> torch.Tensor:
     return torch.cat([A, B, D]).to(torch.complex128)
 
 
-class _SweepFR(torch.autograd.Function):
-    """fr(c) for a frequency vector; backward = adjoint sweep with dL/dfr."""
-
-    @staticmethod
-    def forward(ctx, c, engine, freqs):
-        cn = c.detach().cpu().numpy()
-        engine.set_coefficients(cn)
-        fr = torch.empty(freqs.numel(), dtype=torch.float64, device=engine.device)
-        flags = torch.zeros(freqs.numel(), dtype=torch.int32, device=engine.device)
-        berr = torch.full((freqs.numel(), 2), float('nan'), dtype=torch.float64, device=engine.device)
-        engine.sweep(freqs, _native.LOSS_NONE, fr=fr, flags=flags, berr=berr)
-        engine.last_berr = berr
-        engine.last_flags = _check_flags(flags)
-        ctx.engine, ctx.freqs, ctx.cn = engine, freqs, cn
-        return fr
-
-    @staticmethod
-    def backward(ctx, grad_fr):
-        engine = ctx.engine
-        engine.set_coefficients(ctx.cn)
-        ref = torch.zeros(ctx.freqs.numel(), dtype=torch.complex128, device=engine.device)
-        ref.real.copy_(grad_fr.to(torch.float64))
-        w = torch.zeros(engine.n_stiff, dtype=torch.complex128, device=engine.device)
-        loss = torch.zeros(1, dtype=torch.float64, device=engine.device)
-        # the cotangent sweep's solves are checked like the forward ones: flags and backward errors
-        # reported, not dropped
-        flags = torch.zeros(ctx.freqs.numel(), dtype=torch.int32, device=engine.device)
-        berr = torch.full((ctx.freqs.numel(), 2), float('nan'), dtype=torch.float64, device=engine.device)
-        engine.sweep(ctx.freqs, _native.LOSS_COTANGENT, ref=torch.view_as_real(ref), scale=1.0,
-                     loss=loss, w=torch.view_as_real(w), flags=flags, berr=berr)
-        engine.last_berr = berr
-        engine.last_flags = _check_flags(flags)
-        return torch.conj(engine.expand(w)).to(torch.complex128).cpu(), None, None
-
-
 def _sensing_axis(axis) -> np.ndarray:
     """The real sensing axis (dU, dV, dW) of the complex response as 3 float64 (default: out of plane)."""
     a = np.asarray((0.0, 0.0, 1.0) if axis is None else axis, dtype=np.float64).reshape(-1)
@@ -704,37 +701,63 @@ def _sensing_axis(axis) -> np.ndarray:
     return a
 
 
-class _SweepTF(torch.autograd.Function):
-    """H(c) = axis . (ts U, ts V, W) (complex) for a frequency vector; backward = one PFR_LOSS_CCOTANGENT sweep with
-    g = conj(grad_out), torch's convention dL = Re(conj(grad) dH)."""
+class _SweepResponse(torch.autograd.Function):
+    """The response of a frequency vector as a function of c: the magnitude fr (float64; ``axis`` None) or the complex
+    H(c) = axis . (ts U, ts V, W).  Backward = one adjoint sweep with the incoming gradient as the loss cotangent:
+    dL/dfr (PFR_LOSS_COTANGENT), or g = conj(grad_out) (PFR_LOSS_CCOTANGENT), torch's convention
+    dL = Re(conj(grad) dH)."""
 
     @staticmethod
     def forward(ctx, c, engine, freqs, axis):
         cn = c.detach().cpu().numpy()
         engine.set_coefficients(cn)
-        h = torch.empty(freqs.numel(), dtype=torch.complex128, device=engine.device)
-        flags = torch.zeros(freqs.numel(), dtype=torch.int32, device=engine.device)
-        berr = torch.full((freqs.numel(), 2), float('nan'), dtype=torch.float64, device=engine.device)
-        engine.sweep(freqs, _native.LOSS_NONE, fr=h, flags=flags, berr=berr, axis=axis)
-        engine.last_berr = berr
-        engine.last_flags = _check_flags(flags)
+        out, flags, berr, _ = engine.outputs(freqs.numel(), torch.float64 if axis is None else torch.complex128)
+        engine.sweep(freqs, _native.LOSS_NONE, fr=out, flags=flags, berr=berr, axis=axis)
+        engine.record(flags, berr)
         ctx.engine, ctx.freqs, ctx.cn, ctx.axis = engine, freqs, cn, axis
-        return h
+        return out
 
     @staticmethod
-    def backward(ctx, grad_h):
+    def backward(ctx, grad):
         engine = ctx.engine
         engine.set_coefficients(ctx.cn)
-        g = torch.conj(grad_h.to(torch.complex128)).resolve_conj().contiguous()
-        w = torch.zeros(engine.n_stiff, dtype=torch.complex128, device=engine.device)
-        loss = torch.zeros(1, dtype=torch.float64, device=engine.device)
-        flags = torch.zeros(ctx.freqs.numel(), dtype=torch.int32, device=engine.device)
-        berr = torch.full((ctx.freqs.numel(), 2), float('nan'), dtype=torch.float64, device=engine.device)
-        engine.sweep(ctx.freqs, _native.LOSS_CCOTANGENT, ref=torch.view_as_real(g), scale=1.0,
-                     loss=loss, w=torch.view_as_real(w), flags=flags, berr=berr, axis=ctx.axis)
-        engine.last_berr = berr
-        engine.last_flags = _check_flags(flags)
+        if ctx.axis is None:
+            ref = torch.zeros(ctx.freqs.numel(), dtype=torch.complex128, device=engine.device)
+            ref.real.copy_(grad.to(torch.float64))
+        else:
+            ref = torch.conj(grad.to(torch.complex128)).resolve_conj().contiguous()
+        loss, w = engine.accumulators()
+        # the cotangent sweep's solves are checked like the forward ones: flags and backward errors
+        # reported, not dropped
+        _, flags, berr, _ = engine.outputs(ctx.freqs.numel(), None)
+        engine.sweep(ctx.freqs, _native.LOSS_COTANGENT if ctx.axis is None else _native.LOSS_CCOTANGENT,
+                     ref=torch.view_as_real(ref), scale=1.0, loss=loss, w=torch.view_as_real(w), flags=flags,
+                     berr=berr, axis=ctx.axis)
+        engine.record(flags, berr)
         return torch.conj(engine.expand(w)).to(torch.complex128).cpu(), None, None, None
+
+
+def _loss_id(func_type: str, axis=None, no_complex: str | None = None):
+    """``(native loss id, sensing axis)`` of a loss name: the checked axis (default: out of plane) for the complex
+    response's losses -- an error for the sweep ``no_complex`` names, which has none -- and None for the magnitude's,
+    which take no axis."""
+    if func_type in _native.COMPLEX_LOSS_IDS:
+        if no_complex is not None:
+            raise ValueError(f'the {no_complex} sweep has no complex-response losses ("{func_type}")')
+        return _native.COMPLEX_LOSS_IDS[func_type], _sensing_axis(axis)
+    if func_type not in _native.LOSS_IDS:
+        raise ValueError(f'Function type "{func_type}" is not supported!')
+    if axis is not None:
+        raise ValueError(f'"{func_type}" is a loss of the magnitude fr: it takes no sensing axis')
+    return _native.LOSS_IDS[func_type], None
+
+
+def _loss_step(engine, freqs, ref, loss_id, n_total, axis):
+    """``(loss sum, w (18,) complex)`` of the single-process step (_Engine.loss_step: reused buffers, one
+    device->host copy), its flags recorded -- copied only when some are set."""
+    lsum, w, flags, nflag = engine.loss_step(freqs, loss_id, torch.view_as_real(ref), 1.0 / n_total, axis)
+    engine.record(flags, engine.last_berr, nflag)
+    return lsum, w
 
 
 class _SweepLoss(torch.autograd.Function):
@@ -746,25 +769,18 @@ class _SweepLoss(torch.autograd.Function):
         cn = c.detach().cpu().numpy()
         engine.set_coefficients(cn)
         if reduce_fn is None:
-            # the single-process step: reused buffers, one device->host copy (_Engine.loss_step)
-            lsum, w, flags, nflag = engine.loss_step(freqs, loss_id, torch.view_as_real(ref), 1.0 / n_total, axis)
-            engine.last_flags = _check_flags(flags) if nflag else np.zeros(flags.numel(), np.int32)
+            lsum, w = _loss_step(engine, freqs, ref, loss_id, n_total, axis)
             ctx.save_for_backward(torch.from_numpy(w))
             return torch.tensor(lsum / n_total, dtype=torch.float64)
-        w = torch.zeros(engine.n_stiff, dtype=torch.complex128, device=engine.device)
-        loss = torch.zeros(1, dtype=torch.float64, device=engine.device)
-        flags = torch.zeros(freqs.numel(), dtype=torch.int32, device=engine.device)
-        berr = torch.full((freqs.numel(), 2), float('nan'), dtype=torch.float64, device=engine.device)
+        loss, w = engine.accumulators()
+        _, flags, berr, _ = engine.outputs(freqs.numel(), None)
         engine.sweep(freqs, loss_id, ref=torch.view_as_real(ref), scale=1.0 / n_total,
                      loss=loss, w=torch.view_as_real(w), flags=flags, berr=berr, axis=axis)
-        engine.last_berr = berr
-        packed = torch.cat([loss.to(torch.complex128), engine.expand(w)])
-        if reduce_fn is not None:
-            packed = reduce_fn(packed)
+        packed = reduce_fn(torch.cat([loss.to(torch.complex128), engine.expand(w)]))
         # one device->host copy per step: loss, gradient partials and the number of flagged frequencies
         # (the flags themselves are copied only when some are set)
         host = torch.cat([packed, torch.count_nonzero(flags).to(torch.complex128).reshape(1)]).cpu()
-        engine.last_flags = _check_flags(flags) if host[-1].real != 0 else np.zeros(flags.numel(), np.int32)
+        engine.record(flags, berr, host[-1].real != 0)
         ctx.save_for_backward(host[1:-1])
         return host[0].real / n_total
 
@@ -790,8 +806,7 @@ class _JetSweepLoss(torch.autograd.Function):
         p = (params.detach().to(torch.float64).cpu() if ctx.cast else params.detach()).numpy() * scaling
         c, J = _cached_abd(material, h, p)
         engine.set_coefficients(c)
-        lsum, w, flags, nflag = engine.loss_step(freqs, loss_id, torch.view_as_real(ref), 1.0 / n_total, axis)
-        engine.last_flags = _check_flags(flags) if nflag else np.zeros(flags.numel(), np.int32)
+        lsum, w = _loss_step(engine, freqs, ref, loss_id, n_total, axis)
         # dL/dparams for an incoming gradient of 1 (the chain's values for it, bit for bit: Re(w J) * scaling)
         ctx.gt = torch.from_numpy(np.real(w @ J) * scaling)
         ctx.dtype, ctx.device = params.dtype, params.device
@@ -1084,6 +1099,13 @@ class Problem:
         return torch.as_tensor(np.asarray(freqs, dtype=np.float64) if not isinstance(freqs, torch.Tensor)
                                else freqs, dtype=torch.float64, device=self.device).contiguous()
 
+    def _response(self, transform, freqs, params, axis) -> torch.Tensor:
+        """The response at ``freqs`` on the device, differentiable in ``params``: fr, or H along ``axis``."""
+        f = self._freqs(freqs)
+        p = params if isinstance(params, torch.Tensor) else torch.as_tensor(np.asarray(params, dtype=np.float64))
+        c = self._coeffs(transform, p.to(torch.float64).cpu())
+        return _SweepResponse.apply(c, self.engine(f.numel()), f, axis)
+
     # ------------------------------------------------------------------ API
     def getFRFunction(self) -> Callable:
         """``fr(freqs, params) -> (F,) float64 tensor`` on the device, differentiable in params
@@ -1095,10 +1117,7 @@ class Problem:
         transform = self._transform()
 
         def fr_function(freqs, params):
-            f = self._freqs(freqs)
-            p = params if isinstance(params, torch.Tensor) else torch.as_tensor(np.asarray(params, dtype=np.float64))
-            c = self._coeffs(transform, p.to(torch.float64).cpu())
-            return _SweepFR.apply(c, self.engine(f.numel()), f)
+            return self._response(transform, freqs, params, None)
 
         self._fr_function = weakref.ref(fr_function)    # no Problem <-> closure reference cycle
         return fr_function
@@ -1116,10 +1135,7 @@ class Problem:
         ax = _sensing_axis(axis)
 
         def tf_function(freqs, params):
-            f = self._freqs(freqs)
-            p = params if isinstance(params, torch.Tensor) else torch.as_tensor(np.asarray(params, dtype=np.float64))
-            c = self._coeffs(transform, p.to(torch.float64).cpu())
-            return _SweepTF.apply(c, self.engine(f.numel()), f, ax)
+            return self._response(transform, freqs, params, ax)
 
         return tf_function
 
@@ -1165,9 +1181,7 @@ class Problem:
         c = _coeffs18(self._transform(), p).detach().numpy()
         eng = self.engine(f.numel())
         eng.set_coefficients(c)
-        fr = torch.empty(f.numel(), dtype=torch.float64, device=eng.device)
-        flags = torch.zeros(f.numel(), dtype=torch.int32, device=eng.device)
-        berr = torch.full((f.numel(), 2), float('nan'), dtype=torch.float64, device=eng.device)
+        fr, flags, berr, _ = eng.outputs(f.numel())
         mode = eng.check_mode
         m = mode | _native.PFR_CHECK_FORWARD | (_native.PFR_CHECK_REFINE if refine else 0)
         if correct is not None:
@@ -1191,40 +1205,42 @@ class Problem:
         every rank sweeps its contiguous block of the frequencies and one
         all-reduce combines loss and gradient partials.
         """
+        s = self._loss_setup(frequencies, reference_fr, func_type, scaling_params, distributed, axis)
+        scaling = 1.0 if scaling_params is None else torch.as_tensor(s.scaling)
+        transform = self._transform()
+
+        def loss(params):
+            p = params if isinstance(params, torch.Tensor) else torch.as_tensor(np.asarray(params, dtype=np.float64))
+            if s.reduce_fn is None and self.material.atype in _JET_TYPES:
+                # one autograd node (host turnaround of the optimiser / bench loop)
+                return _JetSweepLoss.apply(p, self.material, self.geometry.height, s.scaling, self.engine(s.n_engine),
+                                           s.freqs, s.ref, s.loss_id, s.n_total, s.axis)
+            c = self._coeffs(transform, p.to(torch.float64).cpu() * scaling)
+            return _SweepLoss.apply(c, self.engine(s.n_engine), s.freqs, s.ref, s.loss_id, s.n_total, s.reduce_fn,
+                                    s.axis)
+
+        return loss
+
+    def _loss_setup(self, frequencies, reference_fr, func_type, scaling_params, distributed, axis=None,
+                    no_complex=None):
+        """What a loss sweep is made from, checked once: the loss id and sensing axis (``_loss_id``), the parameter
+        scaling (1.0 or a float64 numpy array), this rank's block of the frequencies and of the reference on the
+        device (all of them unless ``distributed``: then ``distributed.shard_range``, and ``reduce_fn`` the
+        all-reduce of the packed partials), the frequency count of the mean and the one the engine is sized for."""
         frequencies = np.asarray(frequencies)
         reference_fr = np.asarray(reference_fr)
         assert frequencies.shape[0] == reference_fr.shape[0]
-        if func_type in _native.COMPLEX_LOSS_IDS:
-            loss_id, axis = _native.COMPLEX_LOSS_IDS[func_type], _sensing_axis(axis)
-        elif func_type not in _native.LOSS_IDS:
-            raise ValueError(f'Function type "{func_type}" is not supported!')
-        elif axis is not None:
-            raise ValueError(f'"{func_type}" is a loss of the magnitude fr: it takes no sensing axis')
-        else:
-            loss_id = _native.LOSS_IDS[func_type]
-        scaling = 1.0 if scaling_params is None else torch.as_tensor(np.array(scaling_params, dtype=np.float64))
-        scaling_np = 1.0 if scaling_params is None else np.array(scaling_params, dtype=np.float64)
+        loss_id, axis = _loss_id(func_type, axis, no_complex)
         n_total = frequencies.shape[0]
         lo, hi, reduce_fn = 0, n_total, None
         if distributed:
             from .distributed import shard_range, all_reduce_sum
             lo, hi = shard_range(n_total)
             reduce_fn = all_reduce_sum
-        transform = self._transform()
-        f_local = self._freqs(frequencies[lo:hi])
-        ref_local = torch.as_tensor(reference_fr[lo:hi].astype(np.complex128), device=self.device)
-
-        def loss(params):
-            p = params if isinstance(params, torch.Tensor) else torch.as_tensor(np.asarray(params, dtype=np.float64))
-            if reduce_fn is None and self.material.atype in _JET_TYPES:
-                # one autograd node (host turnaround of the optimiser / bench loop)
-                return _JetSweepLoss.apply(p, self.material, self.geometry.height, scaling_np,
-                                           self.engine(max(1, hi - lo)), f_local, ref_local, loss_id, n_total, axis)
-            c = self._coeffs(transform, p.to(torch.float64).cpu() * scaling)
-            return _SweepLoss.apply(c, self.engine(max(1, hi - lo)), f_local, ref_local, loss_id, n_total, reduce_fn,
-                                    axis)
-
-        return loss
+        return SimpleNamespace(loss_id=loss_id, axis=axis, n_total=n_total, n_engine=max(1, hi - lo),
+                               reduce_fn=reduce_fn, freqs=self._freqs(frequencies[lo:hi]),
+                               ref=torch.as_tensor(reference_fr[lo:hi].astype(np.complex128), device=self.device),
+                               scaling=1.0 if scaling_params is None else np.array(scaling_params, dtype=np.float64))
 
     def getLossHessianFunction(self, frequencies, reference_fr, func_type: str, scaling_params=None,
                                *, distributed: bool = False) -> Callable:
@@ -1238,59 +1254,30 @@ class Problem:
         direction; the material transform's first and second derivatives come
         from torch autograd on the host.
         """
-        frequencies = np.asarray(frequencies)
-        reference_fr = np.asarray(reference_fr)
-        assert frequencies.shape[0] == reference_fr.shape[0]
-        if func_type in _native.COMPLEX_LOSS_IDS:
-            raise ValueError(f'the Hessian sweep has no complex-response losses ("{func_type}")')
-        if func_type not in ('MSE', 'RMSE', 'MSE_AFC', 'MSE_LOG_AFC'):
-            raise ValueError(f'Function type "{func_type}" is not supported!')
-        loss_id = _native.LOSS_IDS[func_type]
-        scaling = 1.0 if scaling_params is None else torch.as_tensor(np.array(scaling_params, dtype=np.float64))
-        n_total = frequencies.shape[0]
-        lo, hi, reduce_fn = 0, n_total, None
-        if distributed:
-            from .distributed import shard_range, all_reduce_sum
-            lo, hi = shard_range(n_total)
-            reduce_fn = all_reduce_sum
-        transform = self._transform()
-        f_local = self._freqs(frequencies[lo:hi])
-        ref_local = torch.as_tensor(reference_fr[lo:hi].astype(np.complex128), device=self.device)
-
-        def c_real(p):
-            return torch.view_as_real(_coeffs18(transform, p * scaling)).reshape(-1)      # (36,)
+        s = self._loss_setup(frequencies, reference_fr, func_type, scaling_params, distributed, no_complex='Hessian')
+        c_and_dc = self._coeffs_jacobian(scaling_params)       # on the jet materials the same c (to the bit) as
+        c_real = c_and_dc.c_real                               # getLossFunction's jet transform
 
         def model(params):
             p = torch.as_tensor(np.asarray(params, dtype=np.float64)).detach()
             n = p.numel()
-            if self.material.atype in _JET_TYPES:
-                # the same c (to the bit) as getLossFunction's jet transform, and its Jacobian in p
-                from ._abd_jet import abd_and_jacobian
-                sc = np.broadcast_to(np.asarray(scaling, dtype=np.float64), (n,))
-                c, J = abd_and_jacobian(self.material, self.geometry.height, (p * scaling).numpy())
-                dc = J * sc[None, :]                                                      # (18, n)
-            else:
-                c = _coeffs18(transform, p * scaling).detach().numpy()
-                jac = torch.autograd.functional.jacobian(c_real, p).numpy().reshape(18, 2, n)
-                dc = jac[:, 0] + 1j * jac[:, 1]                                            # (18, n)
+            c, dc = c_and_dc(p)                                                            # (18,), (18, n)
             d2 = np.stack([torch.autograd.functional.hessian(lambda x, m=m: c_real(x)[m], p).numpy()
                            for m in range(36)]).reshape(18, 2, n, n)
             d2c = d2[:, 0] + 1j * d2[:, 1]                                                 # (18, n, n)
-            eng = self.engine(max(1, hi - lo))
+            eng = self.engine(s.n_engine)
             eng.set_coefficients(c)
-            dev = eng.device
-            w = torch.zeros(eng.n_stiff, dtype=torch.complex128, device=dev)
-            h = torch.zeros(n, eng.n_stiff, dtype=torch.complex128, device=dev)
-            loss = torch.zeros(1, dtype=torch.float64, device=dev)
-            flags = torch.zeros(f_local.numel(), dtype=torch.int32, device=dev)
-            eng.hessian_sweep(f_local, loss_id, torch.view_as_real(ref_local), 1.0 / n_total, dc[eng.kidx].T,
+            loss, w = eng.accumulators()
+            h = torch.zeros(n, eng.n_stiff, dtype=torch.complex128, device=eng.device)
+            flags = torch.zeros(s.freqs.numel(), dtype=torch.int32, device=eng.device)
+            eng.hessian_sweep(s.freqs, s.loss_id, torch.view_as_real(s.ref), 1.0 / s.n_total, dc[eng.kidx].T,
                               loss=loss, w=torch.view_as_real(w), h=torch.view_as_real(h), flags=flags)
             _check_flags(flags)
             packed = torch.cat([loss.to(torch.complex128), eng.expand(w), eng.expand(h).reshape(-1)])
-            if reduce_fn is not None:
-                packed = reduce_fn(packed)
+            if s.reduce_fn is not None:
+                packed = s.reduce_fn(packed)
             packed = packed.cpu().numpy()
-            val = packed[0].real / n_total
+            val = packed[0].real / s.n_total
             w_, h_ = packed[1:19], packed[19:].reshape(n, 18)
             grad = np.real(w_ @ dc)
             hess = np.real(h_ @ dc) + np.real(np.einsum('k,kij->ij', w_, d2c))
@@ -1303,6 +1290,10 @@ class Problem:
         ``J[q, i] = d fr_q / d params_i`` from ONE sweep (one factorisation and one adjoint solve per frequency,
         pfr_jacobian_sweep), where reverse mode through ``getFRFunction`` needs one adjoint sweep per frequency.
         ``scaling_params``: the function is of ``params * scaling_params`` and J is with respect to ``params``."""
+        return self._jacobian_function(scaling_params, None)
+
+    def _jacobian_function(self, scaling_params, axis) -> Callable:
+        """``getFRJacobianFunction`` (``axis`` None) or ``getTFJacobianFunction`` along the checked ``axis``."""
         c_and_dc = self._coeffs_jacobian(scaling_params)
 
         def fn(freqs, params):
@@ -1310,22 +1301,19 @@ class Problem:
             c, dc = c_and_dc(params)
             eng = self.engine(f.numel())
             eng.set_coefficients(c)
-            dev = eng.device
-            F = f.numel()
-            fr = torch.empty(F, dtype=torch.float64, device=dev)
-            jc = torch.empty((F, eng.n_stiff), dtype=torch.complex128, device=dev)
-            flags = torch.zeros(F, dtype=torch.int32, device=dev)
-            berr = torch.full((F, 2), float('nan'), dtype=torch.float64, device=dev)
-            eng.jacobian_sweep(f, jc, fr=fr, flags=flags, berr=berr)
-            # J = Re(expand(jc) @ dc): the contracted matrices' rows of dc (the others' partials vanish)
-            dct = torch.as_tensor(np.ascontiguousarray(dc[eng.kidx]), device=dev)
-            return fr, torch.real(jc @ dct)
+            out, flags, berr, jc = eng.outputs(f.numel(), torch.float64 if axis is None else torch.complex128, jc=True)
+            eng.jacobian_sweep(f, jc, fr=out, flags=flags, berr=berr, axis=axis)
+            # expand(jc) @ dc from the contracted matrices' rows of dc (the others' partials vanish); fr's is its
+            # real part, H is holomorphic in the coefficients
+            J = jc @ torch.as_tensor(np.ascontiguousarray(dc[eng.kidx]), device=eng.device)
+            return out, torch.real(J) if axis is None else J
 
         return fn
 
     def _coeffs_jacobian(self, scaling_params) -> Callable:
         """``fn(params) -> (c (18,), dc (18, n_params))`` complex numpy: c(params * scaling) and its derivative with
-        respect to params, as ``getLossHessianFunction`` forms them."""
+        respect to params; ``fn.c_real``: params -> c as 36 reals, for torch's functional derivatives
+        (``getLossHessianFunction``'s second ones)."""
         scaling = 1.0 if scaling_params is None else torch.as_tensor(np.array(scaling_params, dtype=np.float64))
         transform = self._transform()
 
@@ -1345,6 +1333,7 @@ class Problem:
             jac = torch.autograd.functional.jacobian(c_real, p).numpy().reshape(18, 2, n)
             return c, jac[:, 0] + 1j * jac[:, 1]
 
+        fn.c_real = c_real
         return fn
 
     def getTFJacobianFunction(self, scaling_params=None, axis=(0, 0, 1)) -> Callable:
@@ -1352,24 +1341,7 @@ class Problem:
         along ``axis`` (``getTFFunction``) and ``dH[q, i] = d H_q / d params_i`` from ONE sweep
         (pfr_jacobian_sweep_complex); H is holomorphic in the coefficients, so no real part is taken.
         ``scaling_params`` as in ``getFRJacobianFunction``."""
-        c_and_dc = self._coeffs_jacobian(scaling_params)
-        ax = _sensing_axis(axis)
-
-        def fn(freqs, params):
-            f = self._freqs(freqs)
-            c, dc = c_and_dc(params)
-            eng = self.engine(f.numel())
-            eng.set_coefficients(c)
-            dev = eng.device
-            F = f.numel()
-            h = torch.empty(F, dtype=torch.complex128, device=dev)
-            jc = torch.empty((F, eng.n_stiff), dtype=torch.complex128, device=dev)
-            flags = torch.zeros(F, dtype=torch.int32, device=dev)
-            berr = torch.full((F, 2), float('nan'), dtype=torch.float64, device=dev)
-            eng.jacobian_sweep(f, jc, fr=h, flags=flags, berr=berr, axis=ax)
-            return h, jc @ torch.as_tensor(np.ascontiguousarray(dc[eng.kidx]), device=dev)
-
-        return fn
+        return self._jacobian_function(scaling_params, _sensing_axis(axis))
 
     def solveForwardJacobian(self, freqs, params=None):
         """``(fr (F,), J (F, n_params))`` (numpy): the frequency response and its derivative with respect to the
@@ -1389,28 +1361,16 @@ class Problem:
         frequencies = np.asarray(frequencies, dtype=np.float64)
         reference_fr = np.asarray(reference_fr)
         assert frequencies.shape[0] == reference_fr.shape[0]
-        if func_type in _native.COMPLEX_LOSS_IDS:
-            tfn = self.getTFJacobianFunction(scaling_params, _sensing_axis(axis))
-            f_dev = self._freqs(frequencies)
-
-            def cres(params):
-                H, dH = tfn(f_dev, params)
-                r, dz, const = complex_residual_terms(H.cpu().numpy(), reference_fr, func_type)
-                Jz = dz[:, None] * dH.cpu().numpy()
-                return r, np.concatenate([Jz.real, Jz.imag]), const
-
-            return cres
-        if axis is not None:
-            raise ValueError(f'"{func_type}" is a loss of the magnitude fr: it takes no sensing axis')
-        if func_type not in _native.LOSS_IDS:
-            raise ValueError(f'Function type "{func_type}" is not supported!')
-        fn = self.getFRJacobianFunction(scaling_params)
+        _, axis = _loss_id(func_type, axis)
+        fn = self._jacobian_function(scaling_params, axis)
+        terms = residual_terms if axis is None else complex_residual_terms
         f_dev = self._freqs(frequencies)
 
         def res(params):
-            fr, J = fn(f_dev, params)
-            r, drdfr, const = residual_terms(fr.cpu().numpy(), reference_fr, func_type)
-            return r, drdfr[:, None] * J.cpu().numpy(), const
+            out, J = fn(f_dev, params)
+            r, d, const = terms(out.cpu().numpy(), reference_fr, func_type)
+            Jr = d[:, None] * J.cpu().numpy()          # dr/dfr dfr, or dz/dH dH
+            return r, Jr if axis is None else np.concatenate([Jr.real, Jr.imag]), const
 
         return res
 
@@ -1460,10 +1420,7 @@ class Problem:
         frequencies = np.asarray(frequencies, dtype=np.float64)
         reference_fr = np.asarray(reference_fr)
         assert frequencies.shape[0] == reference_fr.shape[0]
-        if func_type in _native.COMPLEX_LOSS_IDS:
-            raise ValueError(f'the population sweep has no complex-response losses ("{func_type}")')
-        if func_type not in _native.LOSS_IDS:
-            raise ValueError(f'Function type "{func_type}" is not supported!')
+        _loss_id(func_type, no_complex='population')
         scaling = 1.0 if scaling_params is None else np.array(scaling_params, dtype=np.float64)
         f_dev = self._freqs(frequencies)
 

@@ -163,6 +163,14 @@ def _f64(a):
     return a, a.ctypes.data_as(_DP)
 
 
+def _axis3(axis, what: str):
+    """A sensing axis as 3 host float64 and their pointer."""
+    a, ap = _f64(np.asarray(axis, dtype=np.float64).reshape(-1))
+    if a.size != 3:
+        raise ValueError(f"{what}: the sensing axis has 3 components")
+    return a, ap
+
+
 def _ptr(t) -> int:
     """Device pointer of a torch tensor (or None -> NULL)."""
     if t is None:
@@ -400,9 +408,7 @@ class Solver:
         solver's x gives, not conjugated (a reference recorded in the other time convention must be conjugated by the
         caller) -- and, with one of the LOSS_C* ids and ``ref`` (complex), loss / w as ``sweep`` accumulates them
         (``fresh``: initialised by the sweep).  ``axis``: 3 real numbers (host)."""
-        a, ap = _f64(np.asarray(axis, dtype=np.float64).reshape(-1))
-        if a.size != 3:
-            raise ValueError("sweep_complex: the sensing axis has 3 components")
+        a, ap = _axis3(axis, "sweep_complex")
         check(lib().pfr_sweep_complex(self._h, int(freqs.numel()), _ptr(freqs), ap, int(loss_type), _ptr(ref),
                                       float(scale), _ptr(h), _ptr(loss), _ptr(w), _ptr(flags), int(bool(fresh)),
                                       self._stream(freqs) if stream is None else stream), "pfr_sweep_complex")
@@ -410,9 +416,7 @@ class Solver:
     def jacobian_sweep_complex(self, freqs, axis, jc, h=None, flags=None, stream=None):
         """pfr_jacobian_sweep_complex: rows ``jc`` (nfreq, n_stiff) complex with dH_q = sum_k jc[q, k] dc_k (no real
         part taken) and ``h`` (nfreq) complex, under the solver's check mode."""
-        a, ap = _f64(np.asarray(axis, dtype=np.float64).reshape(-1))
-        if a.size != 3:
-            raise ValueError("jacobian_sweep_complex: the sensing axis has 3 components")
+        a, ap = _axis3(axis, "jacobian_sweep_complex")
         check(lib().pfr_jacobian_sweep_complex(self._h, int(freqs.numel()), _ptr(freqs), ap, _ptr(h), _ptr(jc),
                                                _ptr(flags), self._stream(freqs) if stream is None else stream),
               "pfr_jacobian_sweep_complex")
