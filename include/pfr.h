@@ -218,6 +218,21 @@ PFR_API int pfr_symbolic_prune(const pfr_symbolic* sym, int32_t max_batch, const
                                int32_t* sched_full, int64_t capacity_bytes);
 PFR_API int32_t pfr_solver_active(const pfr_solver* s, int32_t* mask, int64_t capacity);
 PFR_API int pfr_solver_schedule_active(const pfr_solver* s, int32_t* dst, int64_t capacity_bytes);
+/* Live stiffness matrices: the matrices k with a non-zero value (!= 0.0) on at least one entry
+ * of the rows a sweep's forward residual walk visits -- the pivot rows of the loaded trees under pruning, every row
+ * otherwise.  The gradient contraction fused into that walk accumulates only those when they are 6 or 12 of more
+ * (a table compacted to them is built once per view and pfr_set_stiffness; PFR_CONTRACT_LIVE=0 or any other count:
+ * all n_stiff); the partials of the other matrices are written as the zeros their sums are, so every output keeps its
+ * bits.
+ * pfr_symbolic_live (host only, no device): the live set as a bit mask (bit k) for the stiffness table stiff_host
+ * (nnz x n_stiff, entry-major, as pfr_set_stiffness takes it on the device) on a symmetric analysis whose right-hand
+ * side vector is rhs (caller numbering); prune != 0: over the loaded trees' rows, else over every row.  Returns the
+ * number of live matrices, or -1 on bad arguments.
+ * pfr_solver_live: the same for the view the operator-form sweeps walk now (the loaded trees' under pruning);
+ * *compact (may be NULL) = 1 when the walk takes the compacted table.  A solver on a general analysis keeps all. */
+PFR_API int32_t pfr_symbolic_live(const pfr_symbolic* sym, const double* rhs, int32_t prune, int32_t n_stiff,
+                                  const double* stiff_host, uint32_t* live);
+PFR_API int32_t pfr_solver_live(const pfr_solver* s, uint32_t* live, int32_t* compact);
 
 /* ---------------------------------------------------------------- InnerState-compatible entry points
  * pfr_solve: x[q] = A_q^{-1} b[q]  (transpose != 0: A_q^{-T} b[q], NON-conjugate, = UMFPACK_Aat,

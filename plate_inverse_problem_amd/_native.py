@@ -90,6 +90,8 @@ _PROTOS = {
     "pfr_symbolic_prune": (C.c_int, [_P, C.c_int32, _DP, C.c_int32, _I32P, _I32P, _I32P, _I32P, _I32P, C.c_int64]),
     "pfr_solver_active": (C.c_int32, [_P, _I32P, C.c_int64]),
     "pfr_solver_schedule_active": (C.c_int, [_P, _I32P, C.c_int64]),
+    "pfr_symbolic_live": (C.c_int32, [_P, _DP, C.c_int32, C.c_int32, _DP, C.POINTER(C.c_uint32)]),
+    "pfr_solver_live": (C.c_int32, [_P, C.POINTER(C.c_uint32), _I32P]),
     "pfr_solve": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32, _P, _P]),
     "pfr_matvec": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32, _P]),
     "pfr_set_stiffness": (C.c_int, [_P, C.c_int32, _P, _DP]),
@@ -295,6 +297,18 @@ class Symbolic:
             return _schedule(st["n_levels"], lambda dst, cap: C.memmove(dst, row.ctypes.data, row.nbytes))
         return mask, table(flat[0]), table(flat[1]), table(flat[2])
 
+    def live(self, rhs, stiff_nz_k, prune: bool = True) -> list:
+        """pfr_symbolic_live: the stiffness matrices k with a non-zero value on an entry of the rows a sweep's
+        forward walk visits (the loaded trees' rows for ``prune``, else every row), for the table ``stiff_nz_k``
+        (nnz, n_stiff) and the right-hand side vector ``rhs``.  Needs no device."""
+        r, rp = _f64(rhs)
+        s, sp = _f64(stiff_nz_k)
+        bits = C.c_uint32(0)
+        n = lib().pfr_symbolic_live(self._h, rp, int(bool(prune)), int(s.shape[1]), sp, C.byref(bits))
+        if n < 0:
+            raise NativeError("pfr_symbolic_live: bad arguments (needs a symmetric analysis)")
+        return [k for k in range(int(s.shape[1])) if (bits.value >> k) & 1]
+
     def __del__(self):
         h = getattr(self, "_h", None)
         if h is not None and _lib is not None:
@@ -339,6 +353,13 @@ class Solver:
         mask = np.zeros(self.sym.stats()["n_fronts"], dtype=np.int32)
         lib().pfr_solver_active(self._h, mask.ctypes.data_as(_I32P), mask.size)
         return mask
+
+    def live(self) -> tuple:
+        """pfr_solver_live: (live stiffness matrices of the view the sweeps walk, whether the walk's contraction
+        takes the table compacted to them)."""
+        bits, compact = C.c_uint32(0), C.c_int32(0)
+        lib().pfr_solver_live(self._h, C.byref(bits), C.byref(compact))
+        return [k for k in range(18) if (bits.value >> k) & 1], bool(compact.value)
 
     def schedule_active(self) -> dict:
         """pfr_solver_schedule_active: the schedule of the view the sweeps launch (``schedule()`` while nothing is

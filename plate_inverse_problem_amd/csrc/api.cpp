@@ -67,6 +67,11 @@ struct SolverView {
   std::vector<int32_t> tile_ptr, blk_ptr, asm_ptr, item_ptr;   // per level: first Schur tile / block, A11 record, L21 item
   std::vector<void*> mine;              // device arrays of a view built after the solver (freed with the view)
   int32_t* d_walk = nullptr;            // the residual walks' row list (original order); -1: a row the view skips
+  // the stiffness matrices with a non-zero value on an entry of the walk's rows (update_live; all of them until then)
+  // and, where the walk's contraction takes the live ones only, the stiffness table compacted to them
+  uint32_t live = 0;
+  int n_live = 0;
+  double* d_se_live = nullptr;          // se_live[nz * n_live + i] on the entries of the walk's rows, or NULL
   int post_n = 0;                       // Dirichlet nodes on the view's fronts, with their column entries
   int2* post_dir = nullptr;             // (k_dirichlet_post over them)
   int32_t* post_dptr = nullptr;
@@ -168,6 +173,12 @@ struct pfr_solver : SolverView {
   // the functional correction's walk): per (workgroup, k, frequency) sums, reduced with m_q by k_reduce_q
   int contract_walk = 1;
   double2* kpart = nullptr;
+  // ... over the live stiffness matrices of the view's walk only (PFR_CONTRACT_LIVE, default on; 0: all n_stiff);
+  // stiff_bits: per matrix entry the k with a non-zero value (pfr_set_stiffness); live_unroll: the six-matrix walk's
+  // gather batch (PFR_LIVE_UNROLL, 4 / 8); d_live_bad: set by k_gather_live on a non-zero value in a dropped matrix
+  int contract_live = 1, live_unroll = 8;
+  std::vector<uint32_t> stiff_bits;
+  int32_t* d_live_bad = nullptr;
   double2 *F = nullptr, *WV = nullptr, *X = nullptr, *Y = nullptr, *XA = nullptr, *G = nullptr, *Y2 = nullptr;
   double2* XR = nullptr;                // refinement correction of the adjoint (PFR_CHECK_REFINE)
   // Hessian sweep: permuted matrix by rows and by columns ((ptr, index, nz) each),
@@ -631,17 +642,21 @@ int set_reach(pfr_solver* s, SolverView& v, int which, const std::vector<int32_t
 // dot products go to s->cpart, the fused contraction to s->kpart (a walk into R has neither: no maxima, no flags)
 void run_walk(pfr_solver* s, const SolverView& v, const pfr::ChunkOp& op, const Walk& w, int nvalid, hipStream_t st) {
   const bool fwd = w.sys == Walk::FORWARD;
-  // w.contract: the gradient contraction fused into the forward walk -- stiffness values nz-major, kpart out
+  // w.contract: the gradient contraction fused into the forward walk -- stiffness values nz-major, kpart out; over
+  // the view's live matrices where their compact table was built (update_live), else over all n_stiff
+  const bool compact = w.contract && v.d_se_live;
+  const unsigned all = w.contract ? (1u << s->n_stiff) - 1u : 0u;
   const pfr::ResidArgs d{.ptr = fwd ? s->d_rptr : s->d_cptr, .idx = fwd ? s->d_ridx : s->d_cidx,
                          .nzs = fwd ? s->d_rnz : s->d_cnz, .n = s->n, .K = op.K, .M = op.M, .freqs = op.freqs,
                          .data = w.data, .data_stride = w.ds, .nvalid = nvalid, .rhsP = w.rd.rhsP,
                          .beta_re = w.rd.beta_re, .beta_im = w.rd.beta_im, .mass_sum = w.rd.mass_sum, .B = w.rd.B,
                          .b_stride = w.rd.b_stride, .perm = s->P.perm, .G = w.rd.G, .walk = v.d_walk,
-                         .se = w.contract ? s->stiff : nullptr, .kpart = w.contract ? s->kpart : nullptr,
-                         .glist = w.glist};
+                         .se = compact ? v.d_se_live : w.contract ? s->stiff : nullptr,
+                         .kpart = w.contract ? s->kpart : nullptr, .live = compact ? v.live : all,
+                         .nslot = w.contract ? s->n_stiff : 0, .glist = w.glist};
   const int n_stiff = w.contract ? s->n_stiff : 0;
-  pfr::launch_residual(w.mat, w.rhs, d, n_stiff, s->res_unroll, op.pop, w.X, s->Fc, w.R, w.check ? s->d_berr_acc : nullptr,
-                       st, w.Mu, w.Mu ? s->cpart : nullptr);
+  pfr::launch_residual(w.mat, w.rhs, d, n_stiff, w.contract ? s->live_unroll : s->res_unroll, op.pop, w.X, s->Fc, w.R,
+                       w.check ? s->d_berr_acc : nullptr, st, w.Mu, w.Mu ? s->cpart : nullptr);
   if (!w.check) return;
   pfr::launch_berr_finish(s->d_berr_acc, s->Fc, nvalid, s->check_tol,
                           fwd ? PFR_FLAG_BACKWARD_ERROR : PFR_FLAG_BACKWARD_ERROR_ADJ, s->flags,
@@ -703,6 +718,37 @@ void release_view(pfr_solver* s, SolverView*& v) {
   }
   delete v;
   v = nullptr;
+}
+
+// The live stiffness matrices of a view's walk (plan.hpp, live_stiffness: decided by value from the registered
+// table, once per view and pfr_set_stiffness) and, where they are 6 or 12 of more, the table compacted to them for
+// the walk's contraction (PFR_CONTRACT_LIVE=0, any other count, or a solver that keeps no analysis: all n_stiff)
+int update_live(pfr_solver* s, SolverView& v) {
+  if (v.d_se_live) {
+    (void)hipDeviceSynchronize();   // launches that read the table
+    s->owned.erase(std::remove(s->owned.begin(), s->owned.end(), (void*)v.d_se_live), s->owned.end());
+    v.mine.erase(std::remove(v.mine.begin(), v.mine.end(), (void*)v.d_se_live), v.mine.end());
+    (void)hipFree(v.d_se_live);
+    v.d_se_live = nullptr;
+  }
+  v.live = s->n_stiff ? (1u << s->n_stiff) - 1u : 0u;
+  v.n_live = s->n_stiff;
+  if (!s->stiff || !s->sym || s->stiff_bits.empty()) return PFR_OK;
+  v.live = pfr::live_stiffness(s->S, &v == s ? nullptr : &v.active, s->stiff_bits);
+  v.n_live = __builtin_popcount(v.live);
+  if (!s->contract_live || v.n_live >= s->n_stiff || (v.n_live != 6 && v.n_live != 12)) return PFR_OK;
+  int rc;
+  if (!s->d_live_bad && (rc = s->alloc(&s->d_live_bad, 1))) return rc;
+  if ((rc = s->alloc(&v.d_se_live, s->nnz * v.n_live))) return rc;
+  if (&v != s) v.mine.push_back(v.d_se_live);
+  HIP_TRY(hipMemsetAsync(s->d_live_bad, 0, 4, nullptr));
+  HIP_TRY(hipMemsetAsync(v.d_se_live, 0, (size_t)s->nnz * v.n_live * 8, nullptr));
+  pfr::launch_gather_live(v.d_walk, s->n, s->d_rptr, s->d_rnz, s->stiff, s->n_stiff, v.live, v.n_live, v.d_se_live,
+                          s->d_live_bad, nullptr);
+  int32_t bad = 0;
+  HIP_TRY(hipMemcpy(&bad, s->d_live_bad, 4, hipMemcpyDeviceToHost));
+  if (bad) return fail(PFR_ERR_STATE, "a stiffness matrix outside the live list is non-zero on a visited entry");
+  return PFR_OK;
 }
 
 // A view of the fronts in `mask` (whole trees): its plan and schedule, the Dirichlet nodes on its fronts, and the
@@ -769,7 +815,8 @@ int update_prune(pfr_solver* s) {
   }
   if (!s->unl_rows.empty()) s->unl_rows.resize(k + 1);
   s->unl_dirty = true;   // the rows of the unloaded trees in X / XA: exact zeros from the first pruned sweep on
-  return make_view(s, mask, true, &s->act);
+  if (int rc = make_view(s, mask, true, &s->act)) return rc;
+  return update_live(s, *s->act);
 }
 
 }  // namespace
@@ -917,6 +964,8 @@ int pfr_solver_create(const pfr_symbolic* sym, const int32_t* colptr, const int3
   s->res_unroll = knob("PFR_RES_UNROLL", 8, 4, 8) == 8 ? 8 : 4;
   s->fn_dot = knob("PFR_FN_DOT", 1, 0, 1);
   s->contract_walk = knob("PFR_CONTRACT_WALK", 1, 0, 1);
+  s->contract_live = knob("PFR_CONTRACT_LIVE", 1, 0, 1);
+  s->live_unroll = knob("PFR_LIVE_UNROLL", 8, 4, 8) == 8 ? 8 : 4;
   s->scale_corr = knob("PFR_SCALE_CORR", 1, 0, 1);
   // PFR_GRAPH=1: repeated sweeps captured into and replayed from a hipGraph (off by default: bitwise the same
   // results and the host's enqueue of a 512-frequency sweep 427 -> 75 us, but 512 frequencies within the spread
@@ -1130,6 +1179,29 @@ int pfr_solver_schedule_active(const pfr_solver* s, int32_t* dst, int64_t cap) {
   return schedule_out(s->act ? s->act->sched : s->sched, dst, cap);
 }
 
+int32_t pfr_symbolic_live(const pfr_symbolic* sym, const double* rhs, int32_t prune, int32_t n_stiff,
+                          const double* stiff_host, uint32_t* live) {
+  if (!sym || !rhs || !stiff_host || n_stiff <= 0 || n_stiff > 18 || !sym->S.symmetric) return -1;
+  const Symbolic& S = sym->S;
+  std::vector<char> mask;
+  if (prune) {
+    std::vector<double> rp(S.n);
+    for (int p = 0; p < S.n; ++p) rp[p] = rhs[S.perm[p]];
+    mask = pfr::loaded_fronts(S, rp.data());
+  }
+  const uint32_t l = pfr::live_stiffness(S, prune ? &mask : nullptr, pfr::stiffness_bits(stiff_host, S.nnz, n_stiff));
+  if (live) *live = l;
+  return __builtin_popcount(l);
+}
+
+int32_t pfr_solver_live(const pfr_solver* s, uint32_t* live, int32_t* compact) {
+  if (!s) return -1;
+  const SolverView& v = sweeps_pruned(s) ? *s->act : static_cast<const SolverView&>(*s);
+  if (live) *live = v.live;
+  if (compact) *compact = v.d_se_live != nullptr;
+  return v.n_live;
+}
+
 int pfr_set_timing(pfr_solver* s, int32_t enable) {
   if (!s) return fail(PFR_ERR_ARG, "null solver");
   ++s->gen;
@@ -1316,6 +1388,16 @@ int pfr_set_stiffness(pfr_solver* s, int32_t n_stiff, const double* stiff_dev, c
   // registered buffer needs another pfr_set_stiffness, include/pfr.h)
   pfr::launch_gather_entries(s->d_uent, s->n_uent + 4, stiff_dev, n_stiff, s->d_se, nullptr);
   HIP_TRY(hipStreamSynchronize(nullptr));
+  // the live matrices of the walks (the full view's and the loaded trees'), from the table's values
+  s->stiff_bits.clear();
+  if (s->sym) {
+    std::vector<double> host((size_t)s->nnz * n_stiff);
+    HIP_TRY(hipMemcpy(host.data(), stiff_dev, host.size() * 8, hipMemcpyDeviceToHost));
+    s->stiff_bits = pfr::stiffness_bits(host.data(), s->nnz, n_stiff);
+  }
+  if (int rc = update_live(s, *s)) return rc;
+  if (s->act)
+    if (int rc = update_live(s, *s->act)) return rc;
   return PFR_OK;
 }
 

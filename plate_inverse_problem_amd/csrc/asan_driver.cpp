@@ -64,6 +64,19 @@ std::string build_views(const pfr::Symbolic& S, int bm, int32_t load_row, const 
     if (V.P[0].level_ptr[l + 1] - V.P[0].level_ptr[l] + V.P[1].level_ptr[l + 1] - V.P[1].level_ptr[l] !=
         S.level_ptr[l + 1] - S.level_ptr[l])
       return "views do not partition a level";
+  // the live stiffness matrices of each view's walk (pfr::live_stiffness): matrix 0 with values on the loaded trees'
+  // rows only, matrix 1 on the other rows only, matrix 2 nowhere
+  std::vector<double> stiff(3 * S.nnz, 0.0);
+  bool any[2] = {false, false};
+  for (int64_t e = 0; e < S.nnz; ++e) {
+    const int side = V.mask[0][foc[S.prow[e]]] ? 0 : 1;
+    stiff[3 * e + side] = 1.0 + e;
+    any[side] = true;
+  }
+  const std::vector<uint32_t> bits = pfr::stiffness_bits(stiff.data(), S.nnz, 3);
+  for (int side = 0; side < 2; ++side)
+    if (pfr::live_stiffness(S, &V.mask[side], bits) != (any[side] ? 1u << side : 0u)) return "live stiffness list of a view";
+  if (pfr::live_stiffness(S, nullptr, bits) != ((any[0] ? 1u : 0u) | (any[1] ? 2u : 0u))) return "live stiffness list";
   return "";
 }
 std::string check_views(const pfr::Symbolic& S, const Views& V, int64_t Fc, const pfr::Knobs& k) {

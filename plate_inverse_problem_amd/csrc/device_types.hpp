@@ -95,8 +95,10 @@ struct ResidArgs {
   const int* perm = nullptr;
   const double2* G = nullptr;
   const int* walk = nullptr;      // rows in walk order (original numbering: mesh-local gathers of X)
-  const double* se = nullptr;     // NSK > 0: stiffness values, nz-major (se[nz * NSK + k])
-  double2* kpart = nullptr;       // NSK > 0: per (workgroup, k, frequency) sums of S_k(nz) mu_row x_col
+  const double* se = nullptr;     // NSK > 0: stiffness values, nz-major (se[nz * NSK + i]: the i-th live matrix)
+  double2* kpart = nullptr;       // NSK > 0: per (workgroup, k, frequency) sums of S_k(nz) mu_row x_col, k < nslot
+  unsigned live = 0;              // NSK > 0: bit k set for the NSK matrices se holds, in order (the others: zeros out)
+  int nslot = 0;                  // NSK > 0: the stiffness matrices of kpart's layout (n_stiff >= NSK)
   const int* glist = nullptr;     // the groups to walk, indexed by grid row (REFINE_CAP, -1: none; NULL: grid row = group)
 };
 

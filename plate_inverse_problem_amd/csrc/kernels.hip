@@ -2726,18 +2726,25 @@ __device__ __forceinline__ cplx resid_entry(const ResidArgs& A, const cplx* __re
 }
 
 constexpr int RES_WPE = 4;   // the fused walk at 114 VGPRs with the compensated residual (round 3: 5 waves/SIMD, 96 VGPRs, 9.5 -> 8.0 ms)
+#ifndef RES_WPE_LIVE
+#define RES_WPE_LIVE 4       // ... with six accumulators (the live half of twelve matrices): a lower bound -- the walk takes
+                             // 84 VGPRs with gather batches of 4, 90 with batches of 8, and runs 5 waves; asking for 5
+                             // or 6 here gave slower code (profiles/contract_live/occupancy.md)
+#endif
 // NSK > 0 (with DOT, the loss sweep's forward walk under the functional correction): the gradient
 // contraction rides on the walk -- every entry (p, j, nz) it visits has x_j gathered and mu_p loaded
 // already, so s_k(q) += S_k(nz) mu_p x_j per lane (frequency), per workgroup; the loss cotangent scale
 // m_q is only known after this walk (k_correct_finish), so the partials stay per frequency and
 // k_reduce_q applies m_q.  Replaces k_contract_eg's separate entry walk.
+// NSK < A.nslot: only the live matrices (A.live, A.se compacted to them) are accumulated; the slots of the others,
+// whose values on every visited entry are exact zeros, are written as the +0.0 their sums would be.
 // CMP: the residual accumulated compensated (Dot2) -- the correction walk (DOT) and the refinement's residual (R):
 // both read the solve's own error, which a plain fp64 sum of the row's terms rounds away
 // RU: entries per batch of the row loop (all their gathers issued before the batch's products; the products in entry
 // order whatever RU, so every RU gives the same bits)
 // POP (MODE 0, the population sweep): the operator and the rhs scale of the group's member; the same arithmetic
 template <int MODE, int RHS, bool DOT = false, int NSK = 0, bool CMP = DOT, int RU = 4, bool POP = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NSK > 0 ? RES_WPE : 1))) void k_residual(ResidArgs A, const cplx* __restrict__ X, int64_t Fc,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NSK > 0 ? (NSK <= 6 ? RES_WPE_LIVE : RES_WPE) : 1))) void k_residual(ResidArgs A, const cplx* __restrict__ X, int64_t Fc,
                                                   cplx* __restrict__ R, double* __restrict__ acc,
                                                   const cplx* __restrict__ Mu, cplx* __restrict__ cpart, PopArgs pop) {
   // XCD-aware order: the workgroups of one 64-frequency group run together on one XCD, so the
@@ -2862,15 +2869,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NSK > 0 ? R
     // the waves' contraction sums in LDS, added in wave order: one partial per (workgroup, k, frequency)
     __shared__ cplx sks[4][64];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    unsigned left = A.live;                  // NSK bits (launch_residual): the slot of accumulator k is the k-th set one
 #pragma unroll
     for (int k = 0; k < NSK; ++k) {
+      const int slot = __builtin_ctz(left);
+      left &= left - 1;
       __syncthreads();
       sks[w][lane] = ks[k];
       __syncthreads();
       if (w == 0)
-        A.kpart[((int64_t)bx * NSK + k) * Fc + q] =
+        A.kpart[((int64_t)bx * A.nslot + slot) * Fc + q] =
             cadd(cadd(sks[0][lane], sks[1][lane]), cadd(sks[2][lane], sks[3][lane]));
     }
+    if (w == 0)
+      for (unsigned dead = ~A.live & ((1u << A.nslot) - 1u); dead; dead &= dead - 1)
+        A.kpart[((int64_t)bx * A.nslot + __builtin_ctz(dead)) * Fc + q] = make_double2(0.0, 0.0);
   }
   if (!acc) return;          // residual only (refinement step / correction without a check)
   if (bad) berr = __longlong_as_double(0x7ff0000000000000LL);     // +inf
@@ -3380,6 +3393,32 @@ __global__ void k_gather_entries(const int4* __restrict__ ent, int nent, const d
   const int4 en = ent[e];
   const bool ij = en.x >= 0 && en.y >= 0;
   for (int k = 0; k < ns; ++k) se[(int64_t)e * ns + k] = ij ? stiff[(int64_t)en.y * ns + k] : 0.0;
+}
+
+// The stiffness table compacted to the live matrices of a walk (the contraction of k_residual with NSK < n_stiff):
+// se_live[nz * nl + i] = stiff[nz * ns + k_i], k_i the i-th set bit of `live` (nl of them), over the entries of the
+// rows the walk visits (walk[t] >= 0; one row per thread; the other entries are never read).  A dropped matrix with
+// a non-zero value on a visited entry sets *bad: the live list does not belong to this table.
+__global__ void k_gather_live(const int* __restrict__ walk, int n, const int* __restrict__ ptr,
+                              const int* __restrict__ nzs, const double* __restrict__ stiff, int ns, unsigned live,
+                              int nl, double* __restrict__ se_live, int* __restrict__ bad) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const int p = walk[t];
+  if (p < 0) return;
+  for (int e = ptr[p]; e < ptr[p + 1]; ++e) {
+    const int64_t nz = nzs[e];
+    int i = 0;
+    for (int k = 0; k < ns; ++k) {
+      const double v = stiff[nz * ns + k];
+      if ((live >> k) & 1u) {
+        if (i < nl) se_live[nz * nl + i] = v;
+        ++i;
+      } else if (v != 0.0) {
+        *bad = 1;
+      }
+    }
+  }
 }
 
 // Gradient contraction, entry-major: w_k = sum_e S_k(e) P_e with P_e = sum_q lambda_i(q) x_j(q) -- the
@@ -3942,20 +3981,26 @@ void launch_residual(Mat mode, Rhs rhs, const ResidArgs& a, int n_stiff, int unr
   const int rh = mode == 0 ? (rhs == 0 ? 0 : 2) : (rhs == 1 ? 1 : 2);
   const bool dot = mode == 0 && rhs == 0 && Mu;          // the correction walk; with kpart: + the contraction
   // unroll 8 on the forward walk with the contraction: 1.87 -> 1.94 ms per 2,048-frequency chunk (not taken)
-  const int nsk = dot && a.kpart && (n_stiff == 12 || n_stiff == 18) ? n_stiff : 0;
+  // the accumulators: the matrices of a.live (api.cpp, walk_contraction: all n_stiff of them, or the 6 or 12 live ones)
+  const int nsk = dot && a.kpart && (n_stiff == 12 || n_stiff == 18) ? __builtin_popcount(a.live) : 0;
+  if (nsk && ((nsk != 6 && nsk != 12 && nsk != 18) || nsk > n_stiff || a.nslot != n_stiff || (a.live >> n_stiff))) {
+    dyn_ok(false, "k_residual: live stiffness list");
+    return;
+  }
   const bool cmp = dot || R;                             // the refinement's residual: compensated
   // the adjoint's check walk with 8 entries per gather batch: 757 -> 638 us per 2,048-frequency chunk
   // (gpurun_out/ru2_*)
-  const int ru = mode == 0 && rh == 2 && !cmp && unroll == 8 ? 8 : 4;
+  // the same batch on the six-accumulator walk: profiles/contract_live/occupancy.md
+  const int ru = unroll == 8 && ((mode == 0 && rh == 2 && !cmp) || nsk == 6) ? 8 : 4;
   // a population sweep: the POP twins of the operator-form instantiations, chosen the same way
   dispatch([&](auto md, auto rhc, auto dt, auto nk, auto cm, auto un, auto pp) {
     constexpr int MD = CV(md), RH = CV(rhc), NK = CV(nk), RU = CV(un);
     constexpr bool DT = CV(dt), CM = CV(cm), PP = CV(pp);
     if constexpr ((RH == 2 || RH == MD) && (!DT || (MD == 0 && RH == 0 && CM)) && (NK == 0 || DT) &&
-                  (RU == 4 || (MD == 0 && RH == 2 && !CM)) && (!PP || MD == 0))
+                  (RU == 4 || (MD == 0 && RH == 2 && !CM) || NK == 6) && (!PP || MD == 0))
       LAUNCH((k_residual<MD, RH, DT, NK, CM, RU, PP>), dim3((unsigned)residual_parts(a.n), (unsigned)(a.glist ? REFINE_CAP : Fc / 64)),
              dim3(256), st, a, X, Fc, R, acc, Mu, cpart, pop);
-  }, pick<0, 1>(mode), pick<0, 1, 2>(rh), flag(dot), pick<0, 12, 18>(nsk), flag(cmp), pick<4, 8>(ru),
+  }, pick<0, 1>(mode), pick<0, 1, 2>(rh), flag(dot), pick<0, 6, 12, 18>(nsk), flag(cmp), pick<4, 8>(ru),
      flag(pop.member != nullptr));
 }
 
@@ -4010,6 +4055,12 @@ void launch_functional(const FunctionalArgs& A, const double2* X, int64_t Fc, in
 void launch_gather_entries(const int4* ent, int nent, const double* stiff, int ns, double* se, hipStream_t st) {
   if (nent <= 0) return;
   LAUNCH(k_gather_entries, dim3((nent + 255) / 256), dim3(256), st, ent, nent, stiff, ns, se);
+}
+
+void launch_gather_live(const int* walk, int n, const int* ptr, const int* nzs, const double* stiff, int ns,
+                        unsigned live, int nl, double* se_live, int* bad, hipStream_t st) {
+  if (n <= 0) return;
+  LAUNCH(k_gather_live, dim3((n + 255) / 256), dim3(256), st, walk, n, ptr, nzs, stiff, ns, live, nl, se_live, bad);
 }
 
 

@@ -105,6 +105,10 @@ void launch_contract_eg(const int4* ent, int nent, const double* se, int n_stiff
                         int64_t Fc, int nvalid, double2* partial, hipStream_t st, const double2* msc = nullptr);
 // entry-ordered copy of the stiffness matrices (se)
 void launch_gather_entries(const int4* ent, int nent, const double* stiff, int ns, double* se, hipStream_t st);
+// the stiffness table compacted to the nl matrices of `live` (se_live[nz * nl + i]) on the entries of the rows of a
+// walk list (rows ptr / nzs: the permuted matrix by rows); *bad = 1 on a non-zero value of another matrix there
+void launch_gather_live(const int* walk, int n, const int* ptr, const int* nzs, const double* stiff, int ns,
+                        unsigned live, int nl, double* se_live, int* bad, hipStream_t st);
 void launch_rhs_dot(const int* sup, const double* val, int n_sup, const double2* Lam, int64_t Fc, double2* t_out,
                     hipStream_t st, const double2* msc = nullptr);
 // w_out[k] += -sum(partial[., k]) + e_k sum_q t_q ;  loss_out += sum_q loss_terms (q < nvalid)
@@ -131,7 +135,9 @@ void launch_dirichlet_post(const DirArgs& d, const PopArgs& pop, int n_dir, doub
 // RHS_VECTOR.  The per-frequency componentwise backward error accumulates in acc (max, zero on
 // entry); acc == NULL: only the residual is written to R.
 // n_stiff (12 or 18, with a.se / a.kpart; else 0): the gradient contraction fused into the forward walk (MAT_OPERATOR,
-// RHS_OPERATOR, Mu != NULL).  unroll: entries per gather batch of the adjoint check walk (4 or 8; the same bits).
+// RHS_OPERATOR, Mu != NULL) over the matrices of a.live (all n_stiff, or 6 or 12 live ones with a.se compacted to them:
+// the other slots of kpart are written as zeros; any other count is refused).  unroll: entries per gather batch of
+// the adjoint check walk and of the six-matrix contraction walk (4 or 8; the same bits).
 // pop (population sweep, MAT_OPERATOR): K and beta of the group's member.
 // Mu != NULL (MAT_OPERATOR, RHS_OPERATOR): also the functional-correction dot products sum_p Mu_p r_p, one partial
 // per workgroup and frequency in cpart (residual_parts(n) x Fc), summed by launch_correct_finish

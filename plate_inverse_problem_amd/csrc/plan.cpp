@@ -456,6 +456,26 @@ std::vector<char> loaded_fronts(const Symbolic& S, const double* rhs_perm) {
   return mask;
 }
 
+std::vector<uint32_t> stiffness_bits(const double* stiff, int64_t nnz, int n_stiff) {
+  std::vector<uint32_t> bits(nnz, 0);
+  for (int64_t nz = 0; nz < nnz; ++nz)
+    for (int k = 0; k < n_stiff; ++k)
+      if (stiff[nz * n_stiff + k] != 0.0) bits[nz] |= 1u << k;
+  return bits;
+}
+
+uint32_t live_stiffness(const Symbolic& S, const std::vector<char>* mask, const std::vector<uint32_t>& bits) {
+  std::vector<char> row_on(S.n, mask ? 0 : 1);
+  if (mask)
+    for (size_t t = 0; t < S.fronts.size(); ++t)
+      if ((*mask)[t])
+        for (int a = 0; a < S.fronts[t].ns; ++a) row_on[S.fronts[t].col0 + a] = 1;
+  uint32_t live = 0;
+  for (int64_t nz = 0; nz < S.nnz && nz < (int64_t)bits.size(); ++nz)
+    if (row_on[S.prow[nz]]) live |= bits[nz];
+  return live;
+}
+
 std::vector<int32_t> rows_in(const Symbolic& S, const std::vector<char>& mask, const std::vector<int32_t>& prows) {
   std::vector<char> row_on(S.n, 0);
   for (size_t t = 0; t < S.fronts.size(); ++t)

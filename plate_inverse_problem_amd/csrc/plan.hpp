@@ -167,6 +167,12 @@ int build_plan(const Symbolic& S, int blk_min, Plan& P, std::string& err, const 
 // Dirichlet nodes whose column reaches such a tree.  On the other trees the forward solution of the operator right-hand
 // side is exactly zero.
 std::vector<char> loaded_fronts(const Symbolic& S, const double* rhs_perm);
+// The stiffness matrices a residual walk's gradient contraction needs ("Live matrices"), by value:
+// stiffness_bits gives per matrix entry nz the set of k with stiff[nz * n_stiff + k] != 0.0 (bit k); live_stiffness
+// the union over the entries of the rows a walk visits -- the pivot rows of the fronts in `mask` (a view's walk
+// list), every row for mask == NULL.  A matrix outside the set holds exact zeros on every entry the walk multiplies.
+std::vector<uint32_t> stiffness_bits(const double* stiff, int64_t nnz, int n_stiff);
+uint32_t live_stiffness(const Symbolic& S, const std::vector<char>* mask, const std::vector<uint32_t>& bits);
 // rows of `prows` on fronts of the mask (a reach restricted to a view)
 std::vector<int32_t> rows_in(const Symbolic& S, const std::vector<char>& mask, const std::vector<int32_t>& prows);
 
