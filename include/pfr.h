@@ -337,6 +337,32 @@ PFR_API int pfr_sweep_complex(pfr_solver* s, int32_t nfreq, const double* freqs_
                               double* w_dev, int32_t* flags_dev, int32_t fresh /* as pfr_sweep_fresh */, void* stream);
 PFR_API int pfr_jacobian_sweep_complex(pfr_solver* s, int32_t nfreq, const double* freqs_dev, const double* axis,
                                        double* h_dev /* may be NULL */, double* jc_dev, int32_t* flags_dev, void* stream);
+/* The field: the solution x_q of (K - omega_q^2 M) x = b itself, at every frequency, for the rows the caller selects
+ * -- the operating deflection shapes over a band, and the data under the reference's Problem.getModePicture
+ * (Problem.py:521-608, one UMFPACK solve per picture).
+ *   out_dev[q * n_sel + j] = x_q[rows[j]]      (complex, nfreq x n_sel, frequency-major, caller numbering)
+ * rows_host: n_rows int32 in the caller's numbering, repeats and any order allowed (n_sel = n_rows); NULL: all n rows
+ * in order (n_sel = n, n_rows ignored).  fr_dev (may be NULL): fr as a PFR_LOSS_NONE pfr_sweep gives it without the
+ * functional correction.  Per chunk the call launches what pfr_sweep(PFR_LOSS_NONE) launches with the check mode
+ * reduced to its PFR_CHECK_FORWARD and PFR_CHECK_REFINE bits (the functional kernel only with fr_dev), on the view that
+ * sweep runs on, then k_field_gather: a transpose of the chunk's frequency-minor, permuted solution through LDS in
+ * tiles of 64 frequencies x pfr_field_tile_rows() selected rows.  PFR_CHECK_CORRECT, PFR_CHECK_ADJOINT and
+ * PFR_CHECK_REFINE_ADJ are ignored, not refused: there is no functional to correct and no adjoint.  Under pruning the
+ * rows of unloaded trees come out as exact +0.0, the true solution there; Dirichlet rows come out with the values the
+ * solve gives them.  flags_dev (may be NULL): the bad-pivot and forward backward-error flags as in pfr_sweep; a
+ * pfr_set_check berr_dev gets slot 2 q written and 2 q + 1 left alone.  Nothing is written outside out_dev's nfreq x
+ * n_sel entries.  PFR_ERR_ARG before anything is launched: a null out_dev, n_rows <= 0 with a list, a row outside
+ * [0, n).  The selection is uploaded once per call on the sweep's stream.  Never part of the PFR_GRAPH graph; the next
+ * loss sweep is bit-identical to one run without it.  Like every sweep the call needs the operator, the right-hand side
+ * and the functional set (PFR_ERR_STATE otherwise) -- pfr_set_functional too when fr_dev is NULL: the analysis' reaches
+ * are set with it.
+ * Out of scope: gradients through the field, a loss on field data, the adjoint field, a population form, a
+ * complex-axis form (pfr_sweep_complex gives H), gathering the field across ranks. */
+PFR_API int pfr_field_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_t n_rows,
+                            const int32_t* rows_host, double* out_dev /* complex nfreq x n_sel */,
+                            double* fr_dev /* nfreq, may be NULL */, int32_t* flags_dev /* may be NULL */, void* stream);
+/* selected rows per tile of k_field_gather (the sizes at which its launch grid changes) */
+PFR_API int32_t pfr_field_tile_rows(void);
 /* A population of parameter sets in one sweep: a lane is a (member, frequency) pair.
  * pfr_combine_batch: Kpop_dev[m * nnz + nz] = sum_k coef[m * n_stiff + k] S_k(nz) for m < n_members (member-major;
  * each row bitwise what pfr_combine gives for that member's coefficients), the stiffness read once.
@@ -409,7 +435,7 @@ PFR_API int pfr_debug_solution(pfr_solver* s, int32_t which, int32_t q, double* 
 
 /* Per-phase device times [ms] of the last pfr_sweep/pfr_solve call on this solver, measured with HIP
  * events on the call's stream (0 = factor, 1 = forward solves, 2 = functional, 3 = adjoint solves,
- * 4 = contraction).  Timing is enabled by pfr_set_timing(s, 1). */
+ * 4 = contraction; in a pfr_field_sweep: the gather).  Timing is enabled by pfr_set_timing(s, 1). */
 PFR_API int pfr_set_timing(pfr_solver* s, int32_t enable);
 PFR_API int pfr_last_timings(const pfr_solver* s, double* ms_out /* 5 */);
 

@@ -113,7 +113,8 @@ class _LaneThread:
 # a new kind of sweep is one more row here and one public _Engine method that states its request (_lane_request)
 _LANE_CALLS = {("sweep", False): ("sweep", "fr"), ("sweep", True): ("sweep_complex", "h"),
                ("jacobian", False): ("jacobian_sweep", "fr"), ("jacobian", True): ("jacobian_sweep_complex", "h"),
-               ("population", False): ("population_sweep", "fr"), ("hessian", False): ("hessian_sweep", None)}
+               ("population", False): ("population_sweep", "fr"), ("hessian", False): ("hessian_sweep", None),
+               ("field", False): ("field_sweep", "fr")}
 _NO_ARGS = {}
 
 
@@ -633,6 +634,26 @@ class _Engine:
         self._sweep_lanes(self._lane_request("jacobian", n, dict(freqs=freqs, jc=torch.view_as_real(jc), flags=flags),
                                              axis=axis, resp=fr, berr=berr), n, {})
         self.record(flags, berr)
+
+    def field_sweep(self, freqs, rows=None, fr=None):
+        """``Solver.field_sweep`` over all lanes: the solution's rows ``rows`` (host, caller numbering; None: every
+        row) at every frequency as an (F, n_sel) complex128 device tensor -- frequency-major, so every lane writes
+        its own block of rows of it, as of ``fr`` (F,), the flags and the backward errors; nothing is accumulated.
+        The sweep honours the forward check and the refinement of the engine's check mode (pfr_field_sweep ignores
+        the rest).  Sets ``last_berr`` (column 1 stays NaN: no adjoint) and ``last_flags``."""
+        n = freqs.numel()
+        if rows is not None:
+            rows = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.int32)
+        n_sel = self._sym_args[0] if rows is None else int(rows.size)
+        _, flags, berr, _ = self.outputs(n, dtype=None)
+        out = torch.empty((n, n_sel), dtype=torch.complex128, device=self.device)
+        # pfr_field_sweep reduces the mode itself; reduced here only so that _sweep_lanes does not count refinement
+        # seed vectors (PFR_CHECK_REFINE_ADJ) that this sweep never allocates
+        mode = self.check_mode & (_native.PFR_CHECK_FORWARD | _native.PFR_CHECK_REFINE)
+        self._sweep_lanes(self._lane_request("field", n, dict(freqs=freqs, out=out, flags=flags), resp=fr, berr=berr,
+                                             rows=rows), n, {}, mode=mode)
+        self.record(flags, berr)
+        return out
 
     def population_sweep(self, freqs, C, jac=True):
         """One sweep for a population of coefficient sets ``C`` (P, 18) complex over the same ``freqs`` (F,): a lane
@@ -1192,6 +1213,99 @@ class Problem:
         finally:
             eng.set_check(mode)
         return fr.cpu().numpy(), berr[:, 0].cpu().numpy(), flags.cpu().numpy()
+
+    # ------------------------------------------------------------------ the field
+    def vertex_rows(self) -> np.ndarray:
+        """Rows of the system ``[u (Lh); v (Lh); w (Mh)]`` that hold u, v and w at the mesh vertices, ``(3, V)``
+        int64 (host only).  For the geometries meshed by ``fem/``: P1 lives on the vertices and ``fem/varf.py``
+        numbers the Morley vertex values before the edge normal derivatives, so vertex ``i`` is rows ``i``,
+        ``Lh + i`` and ``2 Lh + i``.  A geometry read from FreeFEM output keeps FreeFEM's numbering of the degrees
+        of freedom, which is not recorded in that output."""
+        if getattr(self.geometry, "_ff", None) is not None:
+            raise NotImplementedError('vertex_rows: a geometry read by Geometry.from_freefem_output carries '
+                                      "FreeFEM's numbering of the degrees of freedom, which its output does not give.")
+        V, L = int(self.mesh.n_vertices), int(self.Lh_size)
+        if L != V or self.Mh_size < V:
+            raise RuntimeError(f'vertex_rows: Lh has {L} and Mh {self.Mh_size} degrees of freedom on {V} vertices')
+        i = np.arange(V, dtype=np.int64)
+        return np.stack([i, L + i, 2 * L + i])
+
+    def _field_fits(self, eng: _Engine, n_freqs: int, n_sel: int):
+        """ValueError when the (F, n_sel) complex field (with its fr, flags and backward errors) would not fit the
+        HBM left free beside the engine's workspaces -- the share of the free memory ``_Engine._shape_for`` lets
+        the chunk buffers take (85 %)."""
+        need = n_freqs * (16 * n_sel + 8 + 4 + 16)
+        free, _ = torch.cuda.mem_get_info(eng.device)
+        if need > 0.85 * free:
+            raise ValueError(f'solveForwardField: the field of {n_freqs} frequencies x {n_sel} rows takes {need:,} '
+                             f'bytes on the device, and {int(free):,} bytes are free beside the solver workspaces; '
+                             'sweep the band in parts or select fewer rows (dofs)')
+
+    def solveForwardField(self, freqs, params=None, dofs=None, *, return_fr: bool = False):
+        """The solution of ``(K - omega^2 M) x = b`` itself at ``freqs`` [Hz]: a complex ``(F, n_sel)`` numpy array
+        in the caller's numbering, ``dofs`` (rows of the system ``[u (Lh); v (Lh); w (Mh)]``, repeats and any order
+        allowed; None: every row) selecting its columns -- the operating deflection shapes over a band
+        (pfr_field_sweep: one forward sweep, the rows gathered on the device).  ``return_fr``: ``(field, fr)``, fr as
+        ``solveForward`` gives it without the functional correction.  Dirichlet rows carry their boundary values.
+        The reference solves one frequency per call for its mode picture (``Problem.py:521-608``)."""
+        if params is None:
+            params = self.parameters
+        n = self.mat_size
+        rows = None
+        if dofs is not None:
+            rows = np.asarray(dofs).reshape(-1)
+            if rows.size == 0 or not np.issubdtype(rows.dtype, np.integer):
+                raise ValueError('solveForwardField: `dofs` is a non-empty list of integer row indices')
+            if rows.min() < 0 or rows.max() >= n:
+                raise ValueError(f'solveForwardField: `dofs` outside [0, {n})')
+        nf = int(freqs.numel()) if isinstance(freqs, torch.Tensor) else int(np.asarray(freqs).size)
+        if nf == 0:
+            raise ValueError('solveForwardField: no frequencies')
+        n_sel = n if rows is None else int(rows.size)
+        eng = self.engine(nf)              # sized first: the field has to fit beside the workspaces as they now are
+        self._field_fits(eng, nf, n_sel)   # refused before the field is allocated or anything is enqueued
+        f = self._freqs(freqs).reshape(-1)
+        p = params if isinstance(params, torch.Tensor) else torch.as_tensor(np.asarray(params, dtype=np.float64))
+        with torch.no_grad():              # the coefficients as solveForward forms them
+            c = self._coeffs(self._transform(), p.to(torch.float64).cpu())
+        eng.set_coefficients(c.detach().cpu().numpy())
+        fr = torch.empty(f.numel(), dtype=torch.float64, device=eng.device) if return_fr else None
+        x = eng.field_sweep(f, rows, fr).cpu().numpy()
+        return (x, fr.cpu().numpy()) if return_fr else x
+
+    def solveForwardShapes(self, freqs, params=None) -> dict:
+        """The operating deflection shapes over a band: ``{"u", "v", "w"}`` of complex ``(F, V)`` arrays, the
+        in-plane and out-of-plane displacements at the mesh vertices (``vertex_rows``) at every frequency."""
+        vr = self.vertex_rows()
+        x = self.solveForwardField(freqs, params, vr.reshape(-1))
+        V = vr.shape[1]
+        return {k: np.ascontiguousarray(x[:, i * V:(i + 1) * V]) for i, k in enumerate("uvw")}
+
+    def getModePicture(self, freq, use_freefem: bool = False, params=None, *, plot: bool = True):
+        """The deflection shape at ``freq`` [Hz] (``Problem.py:521-608``): returns ``(mesh, values)`` with ``values``
+        = ``|w|`` at the mesh vertices, Dirichlet vertices included -- the quantity the reference shows.  ``plot``:
+        drawn as the reference draws it (filled contours over the mesh, equal aspect, a horizontal colour bar) when
+        matplotlib can be imported; without it the data is returned and nothing is drawn.  ``use_freefem`` (the
+        reference's FreeFem++ ``plot``): FreeFem++ is not part of this build."""
+        if use_freefem:
+            raise NotImplementedError('getModePicture: use_freefem=True needs FreeFem++, which is not part of this build')
+        w = self.solveForwardField([float(freq)], params, self.vertex_rows()[2])[0]
+        values = np.abs(w)
+        if plot:
+            try:
+                import matplotlib.pyplot as plt
+            except ImportError:
+                plt = None
+            if plt is not None:
+                xy, tri = np.asarray(self.mesh.vertices), np.asarray(self.mesh.triangles)
+                cf = plt.tricontourf(xy[:, 0], xy[:, 1], tri, values, 200, cmap='coolwarm', norm='symlog',
+                                     antialiased=False)
+                ax = plt.gca()
+                ax.set_aspect('equal')
+                plt.colorbar(cf, orientation='horizontal', location='bottom', pad=0.05)
+                ax.triplot(xy[:, 0], xy[:, 1], tri, color='k', alpha=.4, lw=.4)
+                ax.axis('off')
+        return self.mesh, values
 
     def getLossFunction(self, frequencies, reference_fr, func_type: str, scaling_params=None,
                         *, distributed: bool = False, axis=None) -> Callable:

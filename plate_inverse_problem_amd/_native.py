@@ -106,6 +106,8 @@ _PROTOS = {
     "pfr_jacobian_sweep": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P]),
     "pfr_sweep_complex": (C.c_int, [_P, C.c_int32, _P, _DP, C.c_int32, _P, C.c_double, _P, _P, _P, _P, C.c_int32, _P]),
     "pfr_jacobian_sweep_complex": (C.c_int, [_P, C.c_int32, _P, _DP, _P, _P, _P, _P]),
+    "pfr_field_sweep": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _I32P, _P, _P, _P, _P]),
+    "pfr_field_tile_rows": (C.c_int32, []),
     "pfr_combine_batch": (C.c_int, [_P, C.c_int32, _DP, _P, _P]),
     "pfr_population_sweep": (C.c_int, [_P, C.c_int32, _P, _I32P, C.c_int32, _P, _DP, _P, _P, _P, _P]),
     "pfr_solve_multi": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, C.c_int64,
@@ -192,6 +194,11 @@ def _schedule(n_levels: int, fill) -> dict:
         out[name] = flat[at:at + size].copy().view(np.dtype([(c, np.int32) for c in cols]))
         at += size
     return out
+
+
+def field_tile_rows() -> int:
+    """pfr_field_tile_rows: the selected rows per tile of the field sweep's gather kernel."""
+    return int(lib().pfr_field_tile_rows())
 
 
 def stream_order(waiter: int, signaller: int):
@@ -441,6 +448,21 @@ class Solver:
         check(lib().pfr_jacobian_sweep_complex(self._h, int(freqs.numel()), _ptr(freqs), ap, _ptr(h), _ptr(jc),
                                                _ptr(flags), self._stream(freqs) if stream is None else stream),
               "pfr_jacobian_sweep_complex")
+
+    def field_sweep(self, freqs, out, rows=None, fr=None, flags=None, stream=None):
+        """pfr_field_sweep: ``out`` (nfreq, n_sel) complex128, frequency-major, receives the solution's rows ``rows``
+        (host int32, caller numbering, repeats and any order allowed; None: all n rows) at every frequency; ``fr``
+        (nfreq) and ``flags`` as a LOSS_NONE ``sweep`` gives them under the forward-check and refinement bits of the
+        solver's check mode (the others are ignored)."""
+        n_rows, rp = 0, None
+        if rows is not None:
+            r, rp = _i32(np.asarray(rows).reshape(-1))
+            n_rows = int(r.size)
+        n_sel = n_rows if rows is not None else self.sym.n
+        if out is not None and out.numel() // (1 if out.is_complex() else 2) < int(freqs.numel()) * n_sel:
+            raise ValueError("field_sweep: out holds fewer than nfreq x n_sel complex entries")
+        check(lib().pfr_field_sweep(self._h, int(freqs.numel()), _ptr(freqs), n_rows, rp, _ptr(out), _ptr(fr),
+                                    _ptr(flags), self._stream(freqs) if stream is None else stream), "pfr_field_sweep")
 
     def combine_batch(self, coef: np.ndarray, out, stream=None):
         """pfr_combine_batch: ``out`` (P, nnz) complex = the operators of the P coefficient rows ``coef`` (P, n_stiff),

@@ -255,15 +255,16 @@ struct pfr_solver : SolverView {
   hipGraph_t graph = nullptr;
   hipGraphExec_t gexec = nullptr;
   int64_t graph_launches = 0;           // sweeps replayed from the graph (pfr_sweep_graph_launches)
-  // host tables of pfr_combine_batch (slot 0) and pfr_population_sweep (slot 1) on their way to the device: a
-  // pinned staging block, its device copy and the event after the copy (waited for before the block is refilled)
+  // host tables of pfr_combine_batch (slot 0), pfr_population_sweep (slot 1) and pfr_field_sweep (slot 2: the row
+  // selection) on their way to the device: a pinned staging block, its device copy and the event after the copy
+  // (waited for before the block is refilled)
   struct Stage {
     void* host = nullptr;
     void* dev = nullptr;
     size_t cap = 0;
     hipEvent_t ev = nullptr;
     bool busy = false;
-  } stage[2];
+  } stage[3];
 
   void drop_graph() {
     if (gexec) (void)hipGraphExecDestroy(gexec);
@@ -377,9 +378,10 @@ pfr::RhsArgs rhs_vector(const double2* G) { return {.G = G}; }
 
 // pruning (pfr_set_prune): the operator-form sweeps walk the loaded trees' view; the refinement modes keep the full
 // one (their corrections solve right-hand sides that are not the operator's)
-bool sweeps_pruned(const pfr_solver* s) {
-  return s->act && !(s->check_mode & (PFR_CHECK_REFINE | PFR_CHECK_REFINE_ADJ));
+bool sweeps_pruned(const pfr_solver* s, int mode) {
+  return s->act && !(mode & (PFR_CHECK_REFINE | PFR_CHECK_REFINE_ADJ));
 }
+bool sweeps_pruned(const pfr_solver* s) { return sweeps_pruned(s, s->check_mode); }
 
 // bytes of a host table to the device on stream st (stage slot `slot`); *dev: the device copy
 int stage_upload(pfr_solver* s, int slot, const void* src, size_t bytes, void** dev, hipStream_t st) {
@@ -1525,6 +1527,15 @@ struct Response {
 // pop.member[g] * pop.nnz (chunk_op).  resp.cpx (the complex sweeps): response holds complex H, loss_type is a PFR_LOSS_C*
 // id, pfr::LOSS_UNIT or PFR_LOSS_NONE, and the functional kernels run in their CPX forms (seed kept in s->h0); every
 // launch after them takes G, fcoef and mscale as it does for the magnitude.
+// field.out != NULL (pfr_field_sweep): the forward sweep whose solution leaves the device -- after the chunk's passes
+// k_field_gather writes the rows field.sel (permuted, n_sel of them) of X to field.out, frequency-major; the functional
+// runs only for a caller who takes fr.  check_mask: the pfr_set_check bits the call honours (the field sweep: the
+// forward check and the refinement; it has no functional to correct and no adjoint).
+struct FieldOut {
+  double2* out = nullptr;
+  const int32_t* sel = nullptr;
+  int32_t n_sel = 0;
+};
 struct SweepSpec {
   int32_t nfreq = 0;
   const double* freqs = nullptr;
@@ -1539,6 +1550,8 @@ struct SweepSpec {
   const double2* popK = nullptr;
   pfr::PopArgs pop;
   Response resp;
+  FieldOut field;
+  int32_t check_mask = ~0;
   double* fr() const { return resp.cpx ? nullptr : response; }   // where the magnitude kernels write fr
 };
 
@@ -1554,6 +1567,8 @@ struct SweepPasses {
   bool fn_fast = false;      // functional from the bottom-up passes
   bool pruned = false;       // on the loaded trees' view (sweeps_pruned)
   bool jac = false;          // the contraction stays per frequency (spec.jc)
+  bool functional = true;    // the functional kernels run (a field sweep without fr: not)
+  bool field = false;        // the chunk's solution rows gathered to the caller (spec.field)
   bool cwalk = false;        // the gradient contraction rides on the forward residual walk (loss sweeps with the correction)
   bool refine_adj = false;   // selective adjoint refinement of the groups next to a resonance (PFR_CHECK_REFINE_ADJ)
   bool scorr = false;        // the solve-error scale of the cotangent (k_correct_finish): t_q = mu^T rhsP in, m_q t_q out
@@ -1563,24 +1578,27 @@ struct SweepPasses {
 
 SweepPasses sweep_passes(const pfr_solver* s, const SweepSpec& sp) {
   SweepPasses p;
+  const int mode = s->check_mode & sp.check_mask;
   p.reverse = sp.loss_type != PFR_LOSS_NONE;
   p.jac = sp.jc != nullptr;
-  p.refine = (s->check_mode & PFR_CHECK_REFINE) != 0;
-  p.correct = (s->check_mode & PFR_CHECK_CORRECT) != 0;
+  p.field = sp.field.out != nullptr;
+  p.functional = !p.field || sp.response != nullptr;
+  p.refine = (mode & PFR_CHECK_REFINE) != 0;
+  p.correct = (mode & PFR_CHECK_CORRECT) != 0;
   p.adj = p.reverse || p.correct;
   p.paired = s->sym && p.adj && !p.refine;
   p.fwd_late = p.paired || p.correct;
   p.fn_fast = p.paired && s->fn_dot;
-  p.pruned = sweeps_pruned(s);
+  p.pruned = sweeps_pruned(s, mode);
   p.cwalk = p.reverse && p.correct && s->contract_walk && (s->n_stiff == 12 || s->n_stiff == 18);
   p.refine_adj =
-      p.reverse && p.correct && p.cwalk && p.fn_fast && !sp.resp.cpx && (s->check_mode & PFR_CHECK_REFINE_ADJ);
+      p.reverse && p.correct && p.cwalk && p.fn_fast && !sp.resp.cpx && (mode & PFR_CHECK_REFINE_ADJ);
   p.scorr = p.reverse && p.correct && s->scale_corr;
-  const bool want_f = p.fwd_late && (s->check_mode & PFR_CHECK_FORWARD);
-  p.check_fwd_early = !p.paired && !p.fwd_late && (s->check_mode & PFR_CHECK_FORWARD);
+  const bool want_f = p.fwd_late && (mode & PFR_CHECK_FORWARD);
+  p.check_fwd_early = !p.paired && !p.fwd_late && (mode & PFR_CHECK_FORWARD);
   p.check_fwd_walk = want_f && p.correct;
   p.check_fwd_after = want_f && !p.correct;
-  p.check_adj = p.adj && (s->check_mode & PFR_CHECK_ADJOINT) != 0;
+  p.check_adj = p.adj && (mode & PFR_CHECK_ADJOINT) != 0;
   return p;
 }
 
@@ -1781,7 +1799,7 @@ int sweep_launches(pfr_solver* s, const SweepSpec& sp, hipStream_t st) {
   if (ps.fn_fast && (rc = fn_setup(s, v))) return rc;
   if (sp.resp.cpx && ps.correct && !s->h0 && (rc = s->alloc(&s->h0, Fc))) return rc;
   if ((ps.cwalk || ps.jac) && !s->kpart && (rc = s->alloc(&s->kpart, s->ws.kpart))) return rc;
-  const bool used[5] = {true, true, true, ps.adj, ps.adj};
+  const bool used[5] = {true, true, true, ps.adj, ps.adj || ps.field};
   Chunk c{.st = st, .fa = functional_args(s, sp)};
   for (c.q0 = 0; c.q0 < sp.nfreq; c.q0 += Fc) {
     c.nv = (int)std::min<int64_t>(Fc, sp.nfreq - c.q0);
@@ -1800,11 +1818,14 @@ int sweep_launches(pfr_solver* s, const SweepSpec& sp, hipStream_t st) {
     record(s, 1, st);
     if ((rc = phase_forward(s, v, op, ps, sp, c))) return rc;
     record(s, 2, st);
-    phase_functional(s, v, op, ps, sp, c);
+    if (ps.functional) phase_functional(s, v, op, ps, sp, c);
     record(s, 3, st);
     if (ps.adj && (rc = phase_adjoint(s, v, op, ps, sp, c))) return rc;
     record(s, 4, st);
     if (ps.adj && (rc = phase_finish(s, v, op, ps, sp, c))) return rc;
+    // the way out of a field sweep, before the next chunk overwrites X (timed as the last phase, otherwise empty here)
+    if (ps.field)
+      pfr::launch_field_gather(sp.field.sel, sp.field.n_sel, s->X, Fc, c.nv, sp.field.out + c.q0 * sp.field.n_sel, st);
     record(s, 5, st);
     if (sp.flags) pfr::launch_flags_merge(s->flags, c.nv, sp.flags + c.q0, st);
     LAUNCH_TRY();
@@ -1950,6 +1971,35 @@ int pfr_jacobian_sweep_complex(pfr_solver* s, int32_t nfreq, const double* freqs
   const SweepSpec sp{.nfreq = nfreq, .freqs = freqs_dev, .loss_type = pfr::LOSS_UNIT, .response = h_dev,
                      .jc = reinterpret_cast<double2*>(jc_dev), .flags = flags_dev, .resp = resp};
   return sweep_launches(s, sp, (hipStream_t)stream);
+}
+
+int32_t pfr_field_tile_rows(void) { return pfr::FIELD_R; }
+
+int pfr_field_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_t n_rows, const int32_t* rows,
+                    double* out_dev, double* fr_dev, int32_t* flags_dev, void* stream) {
+  if (!s || nfreq <= 0 || !freqs_dev || !out_dev) return fail(PFR_ERR_ARG, "bad field sweep arguments");
+  std::vector<int32_t> sel;
+  if (rows) {
+    const std::string refusal = pfr::field_rows(s->iperm, n_rows, rows, sel);
+    if (!refusal.empty()) return fail(PFR_ERR_ARG, refusal);
+  }
+  if (int rc = sweep_ready(s)) return rc;
+  never_captured(s);
+  HIP_TRY(hipSetDevice(s->device));
+  hipStream_t st = (hipStream_t)stream;
+  // every row: the full view's walk list is iperm, on the device already.  That holds because the solver's own view
+  // covers every front (upload_view writes -1 only for rows of fronts outside a view; pruned views are s->act /
+  // s->comp, never *s): a full view that skipped rows would need its own list here, the gather reads X[sel[j] * Fc + q]
+  FieldOut field{.out = reinterpret_cast<double2*>(out_dev), .sel = s->d_walk, .n_sel = s->n};
+  if (rows) {
+    void* d_sel = nullptr;
+    if (int rc = stage_upload(s, 2, sel.data(), sel.size() * sizeof(int32_t), &d_sel, st)) return rc;
+    field.sel = static_cast<const int32_t*>(d_sel);
+    field.n_sel = (int32_t)sel.size();
+  }
+  const SweepSpec sp{.nfreq = nfreq, .freqs = freqs_dev, .response = fr_dev, .flags = flags_dev, .field = field,
+                     .check_mask = PFR_CHECK_FORWARD | PFR_CHECK_REFINE};
+  return sweep_launches(s, sp, st);
 }
 
 int pfr_combine_batch(pfr_solver* s, int32_t n_members, const double* coef, double* Kpop_dev, void* stream) {

@@ -3679,6 +3679,48 @@ __global__ void k_unpermute(const int* __restrict__ perm, int n, const cplx* __r
   out[(int64_t)q * n + perm[p]] = X[(int64_t)p * Fc + q];
 }
 
+// out[q * n_sel + j] = X[sel[j] * Fc + q] for q < nvalid, j < n_sel (pfr_field_sweep): the selected rows of a chunk's
+// solution, frequency-minor and permuted, as caller-numbered frequency-major output -- a transpose through LDS.
+// A workgroup (FIELD_W waves) owns 64 frequencies x FIELD_R selected rows.  Load: lane = frequency, a wave takes the
+// tile rows w, w + FIELD_W, ...; the row index is wave-uniform (a scalar load from sel), each row one 1 KiB wave load,
+// all FIELD_R / FIELD_W of a wave in flight before the first goes to LDS.  Store: lane = (frequency parity, tile row),
+// a wave store covers the FIELD_R rows of two frequencies: two runs of 512 B of out.
+// LDS: row pitch FIELD_PITCH = 65 entries (1,040 B).  The b128 stores of the load phase are contiguous over the
+// lanes (8-lane groups on 8 distinct 16-B slots of the 128-B store row); the b128 reads of the store phase take slot
+// (row + frequency) mod 16 of the 256-B bank row, distinct over each of ds_read_b128's four 16-lane groups (tile rows
+// {0-3, 12-15, 20-27} and {4-11, 16-19, 28-31} of one frequency: every residue mod 16 once).  No conflicts either way.
+// A ragged tile loads its last valid row again (never stored); the padded frequencies of a chunk are loaded (X holds
+// them: Fc is a multiple of 64) and not stored.
+constexpr int FIELD_W = 4;
+constexpr int FIELD_PITCH = 65;
+static_assert(FIELD_R == 32 && FIELD_R % FIELD_W == 0, "k_field_gather: two frequencies of FIELD_R rows per wave store");
+__global__ __launch_bounds__(64 * FIELD_W) void k_field_gather(const int* __restrict__ sel, int n_sel,
+                                                               const cplx* __restrict__ X, int64_t Fc, int nvalid,
+                                                               cplx* __restrict__ out) {
+  __shared__ cplx tile[FIELD_R * FIELD_PITCH];
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int j0 = blockIdx.x * FIELD_R;
+  const int q0 = blockIdx.y * 64;
+  constexpr int NR = FIELD_R / FIELD_W;
+  cplx v[NR];
+#pragma unroll
+  for (int i = 0; i < NR; ++i) {
+    const int p = sel[min(j0 + w + FIELD_W * i, n_sel - 1)];
+    v[i] = X[(int64_t)p * Fc + q0 + lane];
+  }
+#pragma unroll
+  for (int i = 0; i < NR; ++i) tile[(w + FIELD_W * i) * FIELD_PITCH + lane] = v[i];
+  __syncthreads();
+  const int r = lane & (FIELD_R - 1), h = lane >> 5;
+  const int j = j0 + r;
+#pragma unroll
+  for (int i = 0; i < NR; ++i) {
+    const int f = 2 * (w + FIELD_W * i) + h;
+    if (j < n_sel && q0 + f < nvalid) out[(int64_t)(q0 + f) * n_sel + j] = tile[r * FIELD_PITCH + f];
+  }
+}
+
 // y = A x (or A^T x) for a batch of matrices on the CSC pattern (InnerState::matvec,
 // InnerState.h:310-470; csc_matvec.h:31-66).  One thread per (column, batch item).
 __global__ void k_matvec(const int* __restrict__ colptr, const int* __restrict__ rowind, int n,
@@ -4106,6 +4148,13 @@ void launch_reduce(const double2* partial, int nparts, int n_stiff, const double
 
 void launch_unpermute(const int* perm, int n, const double2* X, int64_t Fc, int nvalid, double2* out, hipStream_t st) {
   LAUNCH(k_unpermute, dim3(n, (nvalid + 63) / 64), dim3(64), st, perm, n, X, Fc, nvalid, out);
+}
+
+void launch_field_gather(const int* sel, int n_sel, const double2* X, int64_t Fc, int nvalid, double2* out,
+                         hipStream_t st) {
+  if (n_sel <= 0 || nvalid <= 0) return;
+  LAUNCH(k_field_gather, dim3((n_sel + FIELD_R - 1) / FIELD_R, (nvalid + 63) / 64), dim3(64 * FIELD_W), st, sel, n_sel, X,
+         Fc, nvalid, out);
 }
 
 void launch_matvec(const int* colptr, const int* rowind, int n, const double2* data, int64_t ds, const double2* x,

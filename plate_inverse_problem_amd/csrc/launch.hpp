@@ -195,6 +195,12 @@ void launch_axpy_vec(double2* X, const double2* D, int64_t count, hipStream_t st
                      int64_t Fc = 64);
 void launch_scale_vec(double2* X, const double2* m, int n, int64_t Fc, hipStream_t st);
 void launch_unpermute(const int* perm, int n, const double2* X, int64_t Fc, int nvalid, double2* out, hipStream_t st);
+// pfr_field_sweep's way out: out[q * n_sel + j] = X[sel[j] * Fc + q] for q < nvalid, j < n_sel (sel: permuted rows,
+// each in [0, n); out: the chunk's first row of the caller's frequency-major array).  Tiles of 64 frequencies x
+// FIELD_R selected rows through LDS; nothing outside [0, nvalid) x [0, n_sel) is stored.
+constexpr int FIELD_R = 32;
+void launch_field_gather(const int* sel, int n_sel, const double2* X, int64_t Fc, int nvalid, double2* out,
+                         hipStream_t st);
 void launch_matvec(const int* colptr, const int* rowind, int n, const double2* data, int64_t ds, const double2* x,
                    int64_t xs, double2* y, int transpose, int batch, hipStream_t st);
 // a chunk's frequencies (padded with the last) and its flags cleared, one kernel

@@ -504,6 +504,22 @@ void reach_lists(const std::vector<int32_t>& front_of_col, const std::vector<int
   }
 }
 
+std::string field_rows(const std::vector<int32_t>& iperm, int32_t n_rows, const int32_t* rows, std::vector<int32_t>& out) {
+  out.clear();
+  if (!rows || n_rows <= 0) return "field sweep: a row list needs at least one row";
+  const int64_t n = (int64_t)iperm.size();
+  out.reserve((size_t)n_rows);
+  for (int32_t j = 0; j < n_rows; ++j) {
+    if (rows[j] < 0 || rows[j] >= n) {
+      char buf[128];
+      snprintf(buf, sizeof buf, "field sweep: row %d = %d outside [0, %lld)", (int)j, (int)rows[j], (long long)n);
+      return buf;
+    }
+    out.push_back(iperm[rows[j]]);
+  }
+  return "";
+}
+
 std::string check_plan(const Symbolic& S, const Plan& P, int64_t Fc) {
   char buf[256];
   auto bad = [&](const char* what, int64_t at, int64_t v, int64_t lim) {

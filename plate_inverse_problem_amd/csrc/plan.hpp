@@ -183,6 +183,11 @@ void reach_lists(const std::vector<int32_t>& front_of_col, const std::vector<int
                  const std::vector<int32_t>& prows, std::vector<int32_t>& mark, std::vector<int32_t>& list,
                  std::vector<int32_t>& ptr);
 
+// The row selection of a field sweep (pfr_field_sweep): rows[0 .. n_rows) in the caller's numbering, repeats and any
+// order allowed, as the permuted rows iperm[rows[j]] the gather kernel reads.  Returns "" or the refusal (no rows, a
+// null list, an index outside [0, n)); `out` is complete only on "".
+std::string field_rows(const std::vector<int32_t>& iperm, int32_t n_rows, const int32_t* rows, std::vector<int32_t>& out);
+
 // Every index each launch of a solver with chunk Fc takes from the plan, against the buffer it addresses
 // (element ids < factor entries, nz < nnz, record offsets and overflow ranges inside their arrays, the
 // per-workgroup partial buffers against the grids that write them).  Returns "" or the first violation.
