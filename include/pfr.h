@@ -72,6 +72,13 @@ extern "C" {
 #define PFR_LOSS_CRMSE 17       /* |H - ref|^2 / |ref|^2,  g = 2 conj(H - ref) / |ref|^2 */
 #define PFR_LOSS_CLOG 18        /* |z|^2, z = log(H / ref) on the principal branch, g = 2 conj(z) / H */
 #define PFR_LOSS_CCOTANGENT 19  /* ref holds dL/dH (complex), loss not computed */
+/* losses on the field (pfr_field_loss_sweep): x_j the selected rows of the solution, r_j the reference, v_j the weights;
+ * d term = Re(sum_j g_j dx_j), g_j = v_j (c1 conj(x_j) + c2 conj(r_j)) */
+#define PFR_LOSS_FMSE 32        /* sum v |x - r|^2,                                 c1 = 2, c2 = -2 */
+#define PFR_LOSS_FRMSE 33       /* sum v |x - r|^2 / R2, R2 = sum v |r|^2,          c1 = 2 / R2, c2 = -2 / R2 */
+#define PFR_LOSS_FMAC 34        /* 1 - |s|^2 / (X2 R2), s = sum v conj(r) x, X2 = sum v |x|^2 (one minus the modal
+                                 * assurance criterion), c1 = 2 |s|^2 / (X2^2 R2), c2 = -2 conj(s) / (X2 R2) */
+#define PFR_LOSS_FCOTANGENT 35  /* ref holds dL/dx (complex, per selected row), loss not computed */
 
 typedef struct pfr_symbolic pfr_symbolic;
 typedef struct pfr_solver pfr_solver;
@@ -356,13 +363,45 @@ PFR_API int pfr_jacobian_sweep_complex(pfr_solver* s, int32_t nfreq, const doubl
  * loss sweep is bit-identical to one run without it.  Like every sweep the call needs the operator, the right-hand side
  * and the functional set (PFR_ERR_STATE otherwise) -- pfr_set_functional too when fr_dev is NULL: the analysis' reaches
  * are set with it.
- * Out of scope: gradients through the field, a loss on field data, the adjoint field, a population form, a
- * complex-axis form (pfr_sweep_complex gives H), gathering the field across ranks. */
+ * Out of scope: the adjoint field, a population form, a complex-axis form (pfr_sweep_complex gives H), gathering the
+ * field across ranks.  No longer out of scope: gradients through the field and a loss on field data, which
+ * pfr_field_loss_sweep gives. */
 PFR_API int pfr_field_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_t n_rows,
                             const int32_t* rows_host, double* out_dev /* complex nfreq x n_sel */,
                             double* fr_dev /* nfreq, may be NULL */, int32_t* flags_dev /* may be NULL */, void* stream);
 /* selected rows per tile of k_field_gather (the sizes at which its launch grid changes) */
 PFR_API int32_t pfr_field_tile_rows(void);
+/* A loss on the field and its gradient: full-field data (a scanning vibrometer's deflection shapes) fitted directly.
+ * With x_j = x_q[rows[j]], r_j = ref_dev[q * n_sel + j] (the layout of pfr_field_sweep's out_dev: a field computed
+ * earlier serves as data unchanged) and weights v_j (weights_host, n_sel real, NULL: all 1), per frequency q the term
+ * and seed of PFR_LOSS_FMSE / FRMSE / FMAC (see the ids); the seed convention is the complex response's:
+ * d term = Re(sum_j g_j dx_j), the adjoint A^T lam_q = scale g_q, non-conjugate.  Then, accumulating as pfr_sweep does
+ * (fresh != 0: as pfr_sweep_fresh),
+ *   loss_dev[0] += scale sum_q term_q,     w_dev[k] += sum_q (-lam_q^T S_k x_q + e_k lam_q^T rhs)   (complex n_stiff).
+ * PFR_LOSS_FCOTANGENT: g_j = ref (the caller's dL/dx), no term, loss_dev left alone (may be NULL), no weights.
+ * out_dev (may be NULL): the field too, bitwise pfr_field_sweep's in the same mode.
+ * Per chunk: the unpaired full forward solve (refined under PFR_CHECK_REFINE), k_field_terms / k_field_finish /
+ * k_field_seed (the loss's sums over tiles of 64 frequencies x pfr_field_tile_rows() rows, the term and two seed
+ * coefficients per frequency, the seed scattered into the adjoint's right-hand side), the unpaired adjoint solve over
+ * every front, k_contract_eg, k_rhs_dot and k_reduce.  The call honours PFR_CHECK_FORWARD, PFR_CHECK_ADJOINT and
+ * PFR_CHECK_REFINE; the other bits are ignored, not refused (there is no single functional to correct), and it runs
+ * pruned exactly when a sweep in that reduced mode would.  Under pruning selected rows of unloaded trees enter the
+ * terms with x = +0.0 (a constant); their seed is written but nothing in w needs their adjoint, which stays +0.0 until
+ * pfr_debug_solution(1, q) completes it.  A frequency with R2 = 0 (FRMSE, FMAC) or X2 = 0 (FMAC) gives a non-finite
+ * term: validate the reference before the call.  Never part of the PFR_GRAPH graph; the next loss sweep is
+ * bit-identical to one run without it.
+ * PFR_ERR_ARG before any launch: a null ref_dev or w_dev, a null loss_dev with a loss term, a loss id outside 32 .. 35,
+ * a weight that is negative or not finite, all weights zero, weights with FCOTANGENT, n_rows <= 0 with a list, a row
+ * outside [0, n), a repeated row (the seed is a scatter: pfr_field_sweep allows repeats, this call does not).
+ * PFR_ERR_STATE: as the reverse sweeps (no operator, rhs, functional or stiffness set).
+ * Out of scope: the field Jacobian and covariance, the Hessian, population and distributed forms, a correction of the
+ * field loss (near a resonance the accuracy tool is PFR_CHECK_REFINE), magnitude-only field data. */
+PFR_API int pfr_field_loss_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_t n_rows,
+                                 const int32_t* rows_host /* NULL: all n rows */,
+                                 const double* weights_host /* n_sel, may be NULL */, int32_t loss_type /* 32..35 */,
+                                 const double* ref_dev /* complex nfreq x n_sel */, double scale,
+                                 double* out_dev /* complex nfreq x n_sel, may be NULL */, double* loss_dev,
+                                 double* w_dev, int32_t* flags_dev /* may be NULL */, int32_t fresh, void* stream);
 /* A population of parameter sets in one sweep: a lane is a (member, frequency) pair.
  * pfr_combine_batch: Kpop_dev[m * nnz + nz] = sum_k coef[m * n_stiff + k] S_k(nz) for m < n_members (member-major;
  * each row bitwise what pfr_combine gives for that member's coefficients), the stiffness read once.

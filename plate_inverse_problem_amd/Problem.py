@@ -114,7 +114,7 @@ class _LaneThread:
 _LANE_CALLS = {("sweep", False): ("sweep", "fr"), ("sweep", True): ("sweep_complex", "h"),
                ("jacobian", False): ("jacobian_sweep", "fr"), ("jacobian", True): ("jacobian_sweep_complex", "h"),
                ("population", False): ("population_sweep", "fr"), ("hessian", False): ("hessian_sweep", None),
-               ("field", False): ("field_sweep", "fr")}
+               ("field", False): ("field_sweep", "fr"), ("field_loss", False): ("field_loss_sweep", None)}
 _NO_ARGS = {}
 
 
@@ -655,6 +655,29 @@ class _Engine:
         self.record(flags, berr)
         return out
 
+    def field_loss_step(self, freqs, rows, weights, loss_id, ref, scale, out=None):
+        """``Solver.field_loss_sweep`` over all lanes: a loss on the solution's rows ``rows`` (host, caller numbering,
+        no repeats; None: every row) with the host ``weights`` (None: all 1) against ``ref`` (F, n_sel) complex128 on
+        the device -- frequency-major, so ``ref`` and the optional field ``out`` are cut into the lanes' frequency
+        blocks like the field sweep's ``out``.  ``loss_id`` a LOSS_F* id (LOSS_FCOTANGENT: ``ref`` is the caller's
+        dL/dx and the loss stays 0).  Returns ``(scale x the sum of the terms, w (18,) complex)`` on the host; the
+        sweep honours the forward and adjoint checks and the refinement of the engine's check mode.  Sets
+        ``last_berr`` and ``last_flags``."""
+        n = freqs.numel()
+        if rows is not None:
+            rows = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.int32)
+        _, flags, berr, _ = self.outputs(n, dtype=None)
+        loss, w = self.accumulators()
+        # which bits the sweep honours is pfr_field_loss_sweep's business alone; the one bit taken out here is the
+        # engine's own bookkeeping: _sweep_lanes counts refinement seed vectors (PFR_CHECK_REFINE_ADJ) as allocated
+        # by any sweep that runs under that bit, and this one never allocates them
+        self._sweep_lanes(self._lane_request("field_loss", n, dict(freqs=freqs, ref=ref, out=out, flags=flags),
+                                             berr=berr, rows=rows, weights=weights, loss_type=loss_id, scale=scale),
+                          n, dict(loss=loss, w=torch.view_as_real(w)),
+                          mode=self.check_mode & ~_native.PFR_CHECK_REFINE_ADJ)
+        self.record(flags, berr)
+        return float(loss.item()), self.expand(w).cpu().numpy()
+
     def population_sweep(self, freqs, C, jac=True):
         """One sweep for a population of coefficient sets ``C`` (P, 18) complex over the same ``freqs`` (F,): a lane
         is a (member, frequency) pair in ``population_layout``'s order, every 64-lane group assembled from its
@@ -838,6 +861,87 @@ class _JetSweepLoss(torch.autograd.Function):
         grad = ctx.gt * g
         return (grad.to(dtype=ctx.dtype, device=ctx.device) if ctx.cast else grad), None, None, None, None, None, \
             None, None, None, None
+
+
+def field_selection(dofs, n: int, what: str = 'the field loss'):
+    """The row selection of a field loss as host int32 (None: every row), checked: integer indices inside ``[0, n)``,
+    no row twice (the adjoint seed is a scatter; ``solveForwardField`` allows repeats, a loss does not)."""
+    if dofs is None:
+        return None
+    rows = np.asarray(dofs).reshape(-1)
+    if rows.size == 0 or not np.issubdtype(rows.dtype, np.integer):
+        raise ValueError(f'{what}: `dofs` is a non-empty list of integer row indices')
+    if rows.min() < 0 or rows.max() >= n:
+        raise ValueError(f'{what}: `dofs` outside [0, {n})')
+    if np.unique(rows).size != rows.size:
+        raise ValueError(f'{what}: `dofs` holds a row twice')
+    return np.ascontiguousarray(rows, dtype=np.int32)
+
+
+def field_reference(reference_field, n_freqs: int, n_sel: int, weights=None, what: str = 'the field loss'):
+    """``(reference (F, n_sel) complex128, weights (n_sel,) float64 or None)`` of a field loss, checked on the host
+    before anything reaches the device: the shape, finite values, weights finite, ``>= 0`` and not all zero, and a
+    non-zero weighted norm ``sum_j v_j |r_j|^2`` at every frequency (FIELD_RMSE and FIELD_MAC divide by it)."""
+    ref = np.asarray(reference_field)
+    if ref.shape != (n_freqs, n_sel):
+        raise ValueError(f'{what}: the reference field has shape {ref.shape}, not (frequencies, selected rows) = '
+                         f'({n_freqs}, {n_sel})')
+    ref = np.ascontiguousarray(ref, dtype=np.complex128)
+    if not np.isfinite(ref).all():
+        raise ValueError(f'{what}: the reference field holds values that are not finite')
+    v = None
+    if weights is not None:
+        v = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+        if v.size != n_sel:
+            raise ValueError(f'{what}: {v.size} weights for {n_sel} selected rows')
+        if not np.isfinite(v).all() or (v < 0).any():
+            raise ValueError(f'{what}: the weights are finite and not negative')
+        if not v.any():
+            raise ValueError(f'{what}: every weight is zero')
+    r2 = (np.abs(ref) ** 2 * (1.0 if v is None else v)).sum(axis=1)
+    if not (r2 > 0).all():
+        q = int(np.argmin(r2 > 0))
+        raise ValueError(f'{what}: the weighted norm of the reference field is zero at frequency {q}')
+    return ref, v
+
+
+class _FieldSweepLoss(torch.autograd.Function):
+    """c -> the mean over the frequencies of a field loss term, one fused sweep (``_Engine.field_loss_step``): the
+    full forward solve, the loss and its seed on the device, the adjoint over every front and the contraction."""
+
+    @staticmethod
+    def forward(ctx, c, engine, freqs, ref, rows, weights, loss_id):
+        cn = c.detach().cpu().numpy()
+        engine.set_coefficients(cn)
+        lsum, w = engine.field_loss_step(freqs, rows, weights, loss_id, ref, 1.0 / freqs.numel())
+        ctx.save_for_backward(torch.from_numpy(w))
+        return torch.tensor(lsum, dtype=torch.float64)
+
+    @staticmethod
+    def backward(ctx, g):
+        (w,) = ctx.saved_tensors
+        return torch.conj(w) * g, None, None, None, None, None, None
+
+
+class _FieldResponse(torch.autograd.Function):
+    """c -> the field (F, n_sel) complex128 on the device (``_Engine.field_sweep``).  Backward = one field-loss sweep
+    with the incoming gradient as the cotangent, g = conj(grad_out) (PFR_LOSS_FCOTANGENT), torch's convention
+    dL = Re(conj(grad) dx) as in ``_SweepResponse``."""
+
+    @staticmethod
+    def forward(ctx, c, engine, freqs, rows):
+        cn = c.detach().cpu().numpy()
+        engine.set_coefficients(cn)
+        ctx.engine, ctx.freqs, ctx.cn, ctx.rows = engine, freqs, cn, rows
+        return engine.field_sweep(freqs, rows)
+
+    @staticmethod
+    def backward(ctx, grad):
+        engine = ctx.engine
+        engine.set_coefficients(ctx.cn)
+        g = torch.conj(grad.to(torch.complex128)).resolve_conj().contiguous()
+        _, w = engine.field_loss_step(ctx.freqs, ctx.rows, None, _native.LOSS_FCOTANGENT, g, 1.0)
+        return torch.conj(torch.from_numpy(w)).resolve_conj(), None, None, None
 
 
 def residual_terms(fr, reference_fr, func_type: str):
@@ -1230,11 +1334,15 @@ class Problem:
         i = np.arange(V, dtype=np.int64)
         return np.stack([i, L + i, 2 * L + i])
 
-    def _field_fits(self, eng: _Engine, n_freqs: int, n_sel: int):
+    def _field_fits(self, eng: _Engine, n_freqs: int, n_sel: int, loss_sums: int = 0):
         """ValueError when the (F, n_sel) complex field (with its fr, flags and backward errors) would not fit the
         HBM left free beside the engine's workspaces -- the share of the free memory ``_Engine._shape_for`` lets
-        the chunk buffers take (85 %)."""
+        the chunk buffers take (85 %).  ``loss_sums`` (a field loss: 1, 2 or 4 sums per tile and frequency): the
+        lanes' partial-sum buffers of pfr_field_loss_sweep, allocated on its first call, are counted too."""
         need = n_freqs * (16 * n_sel + 8 + 4 + 16)
+        if loss_sums:
+            tiles = -(-n_sel // _native.field_tile_rows())
+            need += eng.n_lanes * 8 * (tiles * loss_sums + 3) * int(eng.solver.max_batch)
         free, _ = torch.cuda.mem_get_info(eng.device)
         if need > 0.85 * free:
             raise ValueError(f'solveForwardField: the field of {n_freqs} frequencies x {n_sel} rows takes {need:,} '
@@ -1306,6 +1414,61 @@ class Problem:
                 ax.triplot(xy[:, 0], xy[:, 1], tri, color='k', alpha=.4, lw=.4)
                 ax.axis('off')
         return self.mesh, values
+
+    def getFieldLossFunction(self, frequencies, reference_field, func_type: str, dofs=None, weights=None,
+                             scaling_params=None) -> Callable:
+        """``loss(params) -> 0-dim tensor`` with autograd: full-field data -- a scanning vibrometer's deflection shapes
+        ``reference_field`` (F, n_sel) complex at the rows ``dofs`` (of the system ``[u (Lh); v (Lh); w (Mh)]``, no
+        repeats; None: every row) -- fitted directly (pfr_field_loss_sweep).  With x the solution's selected rows, r
+        the reference and the ``weights`` v (n_sel real >= 0; None: all 1), the value is the mean over the frequencies
+        of ``func_type``'s term: FIELD_MSE ``sum v |x - r|^2``, FIELD_RMSE that over ``sum v |r|^2``, FIELD_MAC
+        ``1 - |sum v conj(r) x|^2 / (sum v |x|^2 sum v |r|^2)`` -- one minus the modal assurance criterion, blind to
+        the amplitude and phase of either shape: the form for a scan whose excitation level is not known.  x is the
+        number the solver gives, not conjugated (``getTFFunction``).  The reference is validated on the host and has
+        to fit the device beside the workspaces (``solveForwardField``)."""
+        if func_type not in _native.FIELD_LOSS_IDS:
+            raise ValueError(f'Function type "{func_type}" is not a field loss {tuple(_native.FIELD_LOSS_IDS)}')
+        loss_id = _native.FIELD_LOSS_IDS[func_type]
+        frequencies = np.asarray(frequencies, dtype=np.float64).reshape(-1)
+        if frequencies.size == 0:
+            raise ValueError('getFieldLossFunction: no frequencies')
+        rows = field_selection(dofs, self.mat_size, 'getFieldLossFunction')
+        n_sel = self.mat_size if rows is None else int(rows.size)
+        ref, v = field_reference(reference_field, frequencies.size, n_sel, weights, 'getFieldLossFunction')
+        eng = self.engine(frequencies.size)
+        self._field_fits(eng, frequencies.size, n_sel, loss_sums=_native.FIELD_LOSS_SUMS[func_type])
+        f = self._freqs(frequencies)
+        ref_dev = torch.as_tensor(ref, device=self.device)
+        scaling = 1.0 if scaling_params is None else torch.as_tensor(np.array(scaling_params, dtype=np.float64))
+        transform = self._transform()
+
+        def loss(params):
+            p = params if isinstance(params, torch.Tensor) else torch.as_tensor(np.asarray(params, dtype=np.float64))
+            c = self._coeffs(transform, p.to(torch.float64).cpu() * scaling)
+            return _FieldSweepLoss.apply(c, self.engine(f.numel()), f, ref_dev, rows, v, loss_id)
+
+        return loss
+
+    def getFieldFunction(self, dofs=None) -> Callable:
+        """``field(freqs, params) -> (F, n_sel) complex128 tensor`` on the device, differentiable in params: the
+        solution's rows ``dofs`` (no repeats; None: every row) at every frequency.  Forward is the field sweep
+        (``solveForwardField``), backward one cotangent sweep of the field loss for the whole band -- any loss on
+        field data torch can express, at the cost of the field on the device."""
+        rows = field_selection(dofs, self.mat_size, 'getFieldFunction')
+        n_sel = self.mat_size if rows is None else int(rows.size)
+        transform = self._transform()
+
+        def field_function(freqs, params):
+            f = self._freqs(freqs).reshape(-1)
+            if f.numel() == 0:
+                raise ValueError('getFieldFunction: no frequencies')
+            eng = self.engine(f.numel())
+            self._field_fits(eng, f.numel(), n_sel)
+            p = params if isinstance(params, torch.Tensor) else torch.as_tensor(np.asarray(params, dtype=np.float64))
+            c = self._coeffs(transform, p.to(torch.float64).cpu())
+            return _FieldResponse.apply(c, eng, f, rows)
+
+        return field_function
 
     def getLossFunction(self, frequencies, reference_fr, func_type: str, scaling_params=None,
                         *, distributed: bool = False, axis=None) -> Callable:

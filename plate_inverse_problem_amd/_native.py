@@ -31,6 +31,12 @@ LOSS_IDS = {"MSE": LOSS_MSE, "RMSE": LOSS_RMSE, "MSE_AFC": LOSS_MSE_AFC, "MSE_LO
 # caller's complex dL/dH in ref
 LOSS_CMSE, LOSS_CRMSE, LOSS_CLOG, LOSS_CCOTANGENT = 16, 17, 18, 19
 COMPLEX_LOSS_IDS = {"MSE_COMPLEX": LOSS_CMSE, "RMSE_COMPLEX": LOSS_CRMSE, "MSE_LOG_COMPLEX": LOSS_CLOG}
+# losses on the field x itself (pfr_field_loss_sweep): sum v |x - r|^2, that over sum v |r|^2, one minus the modal
+# assurance criterion, and the caller's complex dL/dx in ref
+LOSS_FMSE, LOSS_FRMSE, LOSS_FMAC, LOSS_FCOTANGENT = 32, 33, 34, 35
+FIELD_LOSS_IDS = {"FIELD_MSE": LOSS_FMSE, "FIELD_RMSE": LOSS_FRMSE, "FIELD_MAC": LOSS_FMAC}
+# sums per tile and frequency each keeps (launch.hpp, field_nsum): what sizes the sweep's partial-sum buffer
+FIELD_LOSS_SUMS = {"FIELD_MSE": 1, "FIELD_RMSE": 2, "FIELD_MAC": 4}
 
 EXPORT = dict(PERM=0, IPERM=1, FRONTS=2, IDX=3, RELPOS=4, ASM_PTR=5, ASM_COL=6, ASM_NZ=7, EA_PTR=8,
               EA_SRC=9, LEVEL_PTR=10, LEVEL_FRONTS=11, DIRICHLET=12, COUPLING=13)
@@ -108,6 +114,8 @@ _PROTOS = {
     "pfr_jacobian_sweep_complex": (C.c_int, [_P, C.c_int32, _P, _DP, _P, _P, _P, _P]),
     "pfr_field_sweep": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _I32P, _P, _P, _P, _P]),
     "pfr_field_tile_rows": (C.c_int32, []),
+    "pfr_field_loss_sweep": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _I32P, _DP, C.c_int32, _P, C.c_double, _P, _P, _P,
+                                       _P, C.c_int32, _P]),
     "pfr_combine_batch": (C.c_int, [_P, C.c_int32, _DP, _P, _P]),
     "pfr_population_sweep": (C.c_int, [_P, C.c_int32, _P, _I32P, C.c_int32, _P, _DP, _P, _P, _P, _P]),
     "pfr_solve_multi": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, C.c_int64, _P, C.c_int64,
@@ -463,6 +471,31 @@ class Solver:
             raise ValueError("field_sweep: out holds fewer than nfreq x n_sel complex entries")
         check(lib().pfr_field_sweep(self._h, int(freqs.numel()), _ptr(freqs), n_rows, rp, _ptr(out), _ptr(fr),
                                     _ptr(flags), self._stream(freqs) if stream is None else stream), "pfr_field_sweep")
+
+    def field_loss_sweep(self, freqs, loss_type, ref, w, rows=None, weights=None, scale=1.0, out=None, loss=None,
+                         flags=None, fresh=False, stream=None):
+        """pfr_field_loss_sweep: a loss on the solution's rows ``rows`` (host int32, caller numbering, no repeats;
+        None: all n rows) against ``ref`` (nfreq, n_sel) complex128, frequency-major, with the host ``weights``
+        (n_sel real >= 0; None: all 1): ``loss[0] += scale sum_q term_q`` and the contracted partials ``w``
+        accumulated as ``sweep`` accumulates them (``fresh``: initialised by the call).  ``loss_type`` a LOSS_F* id;
+        LOSS_FCOTANGENT: ``ref`` holds the caller's dL/dx, ``loss`` is left alone.  ``out`` (nfreq, n_sel) complex128:
+        the field too, as ``field_sweep`` gives it."""
+        n_rows, rp, wp = 0, None, None
+        if rows is not None:
+            r, rp = _i32(np.asarray(rows).reshape(-1))
+            n_rows = int(r.size)
+        n_sel = n_rows if rows is not None else self.sym.n
+        if weights is not None:
+            wt, wp = _f64(np.asarray(weights, dtype=np.float64).reshape(-1))
+            if wt.size != n_sel:
+                raise ValueError(f"field_loss_sweep: {wt.size} weights for {n_sel} selected rows")
+        for name, t in (("ref", ref), ("out", out)):
+            if t is not None and t.numel() // (1 if t.is_complex() else 2) < int(freqs.numel()) * n_sel:
+                raise ValueError(f"field_loss_sweep: {name} holds fewer than nfreq x n_sel complex entries")
+        check(lib().pfr_field_loss_sweep(self._h, int(freqs.numel()), _ptr(freqs), n_rows, rp, wp, int(loss_type),
+                                         _ptr(ref), float(scale), _ptr(out), _ptr(loss), _ptr(w), _ptr(flags),
+                                         1 if fresh else 0, self._stream(freqs) if stream is None else stream),
+              "pfr_field_loss_sweep")
 
     def combine_batch(self, coef: np.ndarray, out, stream=None):
         """pfr_combine_batch: ``out`` (P, nnz) complex = the operators of the P coefficient rows ``coef`` (P, n_stiff),

@@ -142,6 +142,7 @@ struct pfr_solver : SolverView {
   pfr::ChunkOp last_op;                 // the last chunk's operator (the accessor's completion factorises with it)
   hipStream_t last_st = nullptr;        // ... and its stream
   bool last_adj = false;                // ... which solved an adjoint (G holds its seed)
+  pfr::Reach last_reach = pfr::REACH_SUPPORT;   // ... over these fronts (a field loss: every front)
   int32_t* d_colptr = nullptr;
   int32_t* d_rowind = nullptr;
   // symmetric mode (options.symmetric): U never formed; Dirichlet nodes decoupled
@@ -200,6 +201,11 @@ struct pfr_solver : SolverView {
   // the residual walk's per-workgroup dot-product partials (residual_parts(n) x Fc)
   double* fr0 = nullptr;
   double2* h0 = nullptr;                // the complex response of the solve (pfr_sweep_complex; allocated on first use)
+  // the field loss (pfr_field_loss_sweep; allocated on first use): the tiles' partial sums (fpart_cap doubles) and
+  // the seed coefficients per frequency (3 x Fc)
+  double* fpart = nullptr;
+  int64_t fpart_cap = 0;
+  double* fseed = nullptr;
   double2 *mscale = nullptr, *cpart = nullptr;     // mscale complex: the solve-error scale (k_correct_finish)
   int scale_corr = 1;                   // PFR_SCALE_CORR: the solve-error scale of the loss sweeps' cotangent
   int32_t* flags = nullptr;
@@ -255,9 +261,9 @@ struct pfr_solver : SolverView {
   hipGraph_t graph = nullptr;
   hipGraphExec_t gexec = nullptr;
   int64_t graph_launches = 0;           // sweeps replayed from the graph (pfr_sweep_graph_launches)
-  // host tables of pfr_combine_batch (slot 0), pfr_population_sweep (slot 1) and pfr_field_sweep (slot 2: the row
-  // selection) on their way to the device: a pinned staging block, its device copy and the event after the copy
-  // (waited for before the block is refilled)
+  // host tables of pfr_combine_batch (slot 0), pfr_population_sweep (slot 1) and pfr_field_sweep /
+  // pfr_field_loss_sweep (slot 2: the row selection, behind the weights) on their way to the device: a pinned
+  // staging block, its device copy and the event after the copy (waited for before the block is refilled)
   struct Stage {
     void* host = nullptr;
     void* dev = nullptr;
@@ -1226,7 +1232,7 @@ int complete_adjoint(pfr_solver* s) {
   const int timing = s->timing;
   s->timing = 0;
   rc = factor_all(s, *s->comp, s->last_op, pfr::MAT_OPERATOR, nullptr, 0, (int)s->Fc, s->last_st);
-  if (rc == PFR_OK) rc = adjoint_solve(s, *s->comp, s->last_op, rhs_vector(s->G), s->XA, s->last_st, pfr::REACH_SUPPORT);
+  if (rc == PFR_OK) rc = adjoint_solve(s, *s->comp, s->last_op, rhs_vector(s->G), s->XA, s->last_st, s->last_reach);
   s->timing = timing;
   s->comp_done = true;
   s->unl_dirty = true;
@@ -1536,6 +1542,9 @@ struct FieldOut {
   const int32_t* sel = nullptr;
   int32_t n_sel = 0;
 };
+// floss.ref != NULL (pfr_field_loss_sweep): the loss is on the solution's rows -- in place of the functional kernels
+// launch_field_loss writes the seed into G for every selected row, so the adjoint runs unpaired over every front; the
+// loss terms and the contraction then go the way of any reverse sweep without the correction.  field.out may be set too.
 struct SweepSpec {
   int32_t nfreq = 0;
   const double* freqs = nullptr;
@@ -1551,6 +1560,7 @@ struct SweepSpec {
   pfr::PopArgs pop;
   Response resp;
   FieldOut field;
+  pfr::FieldLossArgs floss;
   int32_t check_mask = ~0;
   double* fr() const { return resp.cpx ? nullptr : response; }   // where the magnitude kernels write fr
 };
@@ -1569,6 +1579,8 @@ struct SweepPasses {
   bool jac = false;          // the contraction stays per frequency (spec.jc)
   bool functional = true;    // the functional kernels run (a field sweep without fr: not)
   bool field = false;        // the chunk's solution rows gathered to the caller (spec.field)
+  bool floss = false;        // the loss and its seed from the solution's rows (spec.floss), in place of the functional
+  pfr::Reach adj_reach = pfr::REACH_SUPPORT;   // the fronts the unpaired adjoint's bottom-up pass visits
   bool cwalk = false;        // the gradient contraction rides on the forward residual walk (loss sweeps with the correction)
   bool refine_adj = false;   // selective adjoint refinement of the groups next to a resonance (PFR_CHECK_REFINE_ADJ)
   bool scorr = false;        // the solve-error scale of the cotangent (k_correct_finish): t_q = mu^T rhsP in, m_q t_q out
@@ -1582,11 +1594,13 @@ SweepPasses sweep_passes(const pfr_solver* s, const SweepSpec& sp) {
   p.reverse = sp.loss_type != PFR_LOSS_NONE;
   p.jac = sp.jc != nullptr;
   p.field = sp.field.out != nullptr;
-  p.functional = !p.field || sp.response != nullptr;
+  p.floss = sp.floss.ref != nullptr;
+  p.functional = p.floss || !p.field || sp.response != nullptr;
+  if (p.floss) p.adj_reach = pfr::REACH_ALL;   // the seed is on any row, not on the support's reach
   p.refine = (mode & PFR_CHECK_REFINE) != 0;
   p.correct = (mode & PFR_CHECK_CORRECT) != 0;
   p.adj = p.reverse || p.correct;
-  p.paired = s->sym && p.adj && !p.refine;
+  p.paired = s->sym && p.adj && !p.refine && !p.floss;
   p.fwd_late = p.paired || p.correct;
   p.fn_fast = p.paired && s->fn_dot;
   p.pruned = sweeps_pruned(s, mode);
@@ -1682,7 +1696,11 @@ void phase_functional(pfr_solver* s, SolverView& v, const pfr::ChunkOp&, const S
                       const Chunk& c) {
   const int64_t Fc = s->Fc;
   if (ps.adj) pfr::launch_zero(s->G, (int64_t)s->n * Fc, c.st);
-  if (ps.fn_fast) {
+  if (ps.floss) {
+    pfr::FieldLossArgs a = sp.floss;
+    a.ref += c.q0 * a.n_sel;
+    pfr::launch_field_loss(a, s->X, Fc, c.nv, s->G, s->fpart, s->loss_terms, s->fseed, c.st);
+  } else if (ps.fn_fast) {
     const double2* Yk[3] = {s->Y2, s->YVk, s->YVk + (int64_t)s->n * Fc};
     pfr::launch_fn_dot(v.d_fn_rows, v.n_fn_rows, s->F, s->Y, Yk, Fc, s->fn_parts, c.st);
     pfr::launch_functional_fn(ps.correct ? seeded(s, c.fa) : c.fa, s->fn_parts, Fc, c.nv, c.q0,
@@ -1714,7 +1732,7 @@ int phase_adjoint(pfr_solver* s, SolverView& v, const pfr::ChunkOp& op, const Sw
       return rc;
     pfr::launch_dirichlet_post(post_desc(s, v, op), op.pop, v.post_n, s->XA, Fc, c.st);
   } else {
-    if ((rc = adjoint_solve(s, v, op, rg, s->XA, c.st, pfr::REACH_SUPPORT))) return rc;
+    if ((rc = adjoint_solve(s, v, op, rg, s->XA, c.st, ps.adj_reach))) return rc;
     if (ps.refine) {
       // l += A^{-T} (g - A^T l): residual into Y2, correction into XR
       run_walk(s, v, op, Walk::residual(Walk::ADJOINT, pfr::RHS_VECTOR, rg, s->XA, s->Y2), c.nv, c.st);
@@ -1793,12 +1811,31 @@ int sweep_launches(pfr_solver* s, const SweepSpec& sp, hipStream_t st) {
   const int64_t Fc = s->Fc;
   SolverView& v = begin_on_view(s, ps.pruned, st);
   s->last_adj = ps.adj;
+  s->last_reach = ps.adj_reach;
   s->last_st = st;
   int rc;
   // buffers and row lists allocated on first use (never under capture: a sweep's first run is direct)
   if (ps.fn_fast && (rc = fn_setup(s, v))) return rc;
   if (sp.resp.cpx && ps.correct && !s->h0 && (rc = s->alloc(&s->h0, Fc))) return rc;
   if ((ps.cwalk || ps.jac) && !s->kpart && (rc = s->alloc(&s->kpart, s->ws.kpart))) return rc;
+  if (ps.floss && sp.floss.loss_type != PFR_LOSS_FCOTANGENT) {
+    const int64_t need = pfr::field_loss_parts(sp.floss.loss_type, sp.floss.n_sel, Fc);
+    if (need > s->fpart_cap) {
+      // a larger request than any before: the new block first (a failure leaves the old block and its capacity in
+      // place), then the old one freed once the launches that read it are done
+      double* grown = nullptr;
+      HIP_TRY(hipMalloc(&grown, (size_t)need * sizeof(double)));
+      if (s->fpart) {
+        (void)hipDeviceSynchronize();
+        s->owned.erase(std::remove(s->owned.begin(), s->owned.end(), (void*)s->fpart), s->owned.end());
+        (void)hipFree(s->fpart);
+      }
+      s->owned.push_back(grown);
+      s->fpart = grown;
+      s->fpart_cap = need;
+    }
+    if (!s->fseed && (rc = s->alloc(&s->fseed, 3 * Fc))) return rc;
+  }
   const bool used[5] = {true, true, true, ps.adj, ps.adj || ps.field};
   Chunk c{.st = st, .fa = functional_args(s, sp)};
   for (c.q0 = 0; c.q0 < sp.nfreq; c.q0 += Fc) {
@@ -1999,6 +2036,42 @@ int pfr_field_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32
   }
   const SweepSpec sp{.nfreq = nfreq, .freqs = freqs_dev, .response = fr_dev, .flags = flags_dev, .field = field,
                      .check_mask = PFR_CHECK_FORWARD | PFR_CHECK_REFINE};
+  return sweep_launches(s, sp, st);
+}
+
+int pfr_field_loss_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, int32_t n_rows, const int32_t* rows,
+                         const double* weights, int32_t loss_type, const double* ref_dev, double scale, double* out_dev,
+                         double* loss_dev, double* w_dev, int32_t* flags_dev, int32_t fresh, void* stream) {
+  if (!s || nfreq <= 0 || !freqs_dev || !ref_dev || !w_dev) return fail(PFR_ERR_ARG, "bad field loss sweep arguments");
+  if (loss_type < PFR_LOSS_FMSE || loss_type > PFR_LOSS_FCOTANGENT) return fail(PFR_ERR_ARG, "bad field loss type");
+  const bool cot = loss_type == PFR_LOSS_FCOTANGENT;
+  if (!cot && !loss_dev) return fail(PFR_ERR_ARG, "field loss sweep: a loss term needs loss_dev");
+  std::vector<int32_t> sel;
+  const std::string refusal = pfr::field_loss_rows(s->iperm, n_rows, rows, weights, cot, sel);
+  if (!refusal.empty()) return fail(PFR_ERR_ARG, refusal);
+  if (int rc = sweep_ready(s, "reverse pass needs pfr_set_stiffness")) return rc;
+  never_captured(s);
+  HIP_TRY(hipSetDevice(s->device));
+  hipStream_t st = (hipStream_t)stream;
+  // all rows: the full view's walk list is iperm, on the device already (pfr_field_sweep)
+  pfr::FieldLossArgs fl{.loss_type = loss_type, .sel = s->d_walk, .n_sel = rows ? (int32_t)sel.size() : s->n,
+                        .ref = reinterpret_cast<const double2*>(ref_dev), .scale = scale};
+  if (rows || weights) {
+    // one staged block: the weights (8-byte entries first), then the selection
+    const size_t wb = weights ? (size_t)fl.n_sel * sizeof(double) : 0, sb = sel.size() * sizeof(int32_t);
+    std::vector<char> block(wb + sb);
+    if (wb) std::memcpy(block.data(), weights, wb);
+    if (sb) std::memcpy(block.data() + wb, sel.data(), sb);
+    void* d_block = nullptr;
+    if (int rc = stage_upload(s, 2, block.data(), block.size(), &d_block, st)) return rc;
+    if (wb) fl.wts = static_cast<const double*>(d_block);
+    if (sb) fl.sel = reinterpret_cast<const int32_t*>(static_cast<const char*>(d_block) + wb);
+  }
+  const FieldOut field{.out = reinterpret_cast<double2*>(out_dev), .sel = fl.sel, .n_sel = fl.n_sel};
+  const SweepSpec sp{.nfreq = nfreq, .freqs = freqs_dev, .loss_type = loss_type, .scale = scale,
+                     .loss = cot ? nullptr : loss_dev, .w = w_dev, .flags = flags_dev, .fresh = fresh != 0,
+                     .field = field, .floss = fl,
+                     .check_mask = PFR_CHECK_FORWARD | PFR_CHECK_ADJOINT | PFR_CHECK_REFINE};
   return sweep_launches(s, sp, st);
 }
 

@@ -3721,6 +3721,156 @@ __global__ __launch_bounds__(64 * FIELD_W) void k_field_gather(const int* __rest
   }
 }
 
+// ------------------------------------------------------------------ loss on the field (pfr_field_loss_sweep)
+// Three passes between the forward solve and the adjoint: the per-frequency sums of the loss over the selected rows
+// (k_field_terms), the term and the two seed coefficients of a frequency (k_field_finish), and the seed
+// g_j = v_j (c1 conj(x_j) + c2 conj(r_j)) written into G where the adjoint solves read it (k_field_seed).  No atomics,
+// every summation order fixed: rows of a tile in the order wave w takes them (w, w + FIELD_W, ...), the tile's waves
+// 0 .. FIELD_W - 1, the tiles ascending.  field_nsum (launch.hpp): the sums a loss keeps per tile and frequency.
+
+// Pass 1, k_field_gather's transpose the other way round: ref[q * n_sel + j] (frequency-major, caller numbering) ->
+// G[sel[j] * Fc + q] (frequency-minor, permuted), and on the way the loss's sums over the tile's rows per frequency:
+//   FMSE sum v |x - r|^2;  FRMSE that and sum v |r|^2;  FMAC Re s, Im s (s = sum v conj(r) x), sum v |x|^2, sum v |r|^2
+// into fpart[(tile * NSUM + k) * Fc + q].  FCOTANGENT: no sums, G = scale * ref (the seed itself; passes 2, 3 skipped).
+// A workgroup (FIELD_W waves) owns 64 frequencies x FIELD_R selected rows.  Load: lane = (frequency parity, tile row),
+// a wave load covers the FIELD_R rows of two frequencies (two runs of 512 B of ref), all FIELD_R / FIELD_W of a wave in
+// flight before the first goes to LDS; ref is never read for q >= nvalid or j >= n_sel (those entries are zeros).
+// Sum: lane = frequency, the row wave-uniform (sel and wts: scalar loads), x and G one 1 KiB wave access each.
+// LDS: the gather's pitch-65 tile.  The b128 stores of the load phase: entry 65 r + f, 16-B slot (r + f) mod 8 of the
+// 128-B store row, distinct over each of ds_write_b128's eight groups of 8 contiguous lanes (8 consecutive tile rows of
+// one frequency).  The b128 reads of the sum phase are contiguous over the lanes: slot (row + lane) mod 16 of the 256-B
+// bank row, distinct over each of ds_read_b128's four 16-lane groups (lanes {0-3, 12-15, 20-27}, ...: every residue
+// mod 16 once).  No conflicts either way.  The wave sums meet in LDS and wave 0 adds them in wave order.
+template <int LOSS>
+__global__ __launch_bounds__(64 * FIELD_W) void k_field_terms(const int* __restrict__ sel,
+                                                              const double* __restrict__ wts, int n_sel,
+                                                              const cplx* __restrict__ ref, const cplx* __restrict__ X,
+                                                              int64_t Fc, int nvalid, double scale,
+                                                              cplx* __restrict__ G, double* __restrict__ fpart) {
+  constexpr int NSUM = field_nsum(LOSS);
+  __shared__ cplx tile[FIELD_R * FIELD_PITCH];
+  __shared__ double red[NSUM > 0 ? FIELD_W * NSUM * 64 : 1];
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int j0 = blockIdx.x * FIELD_R;
+  const int q0 = blockIdx.y * 64;
+  constexpr int NR = FIELD_R / FIELD_W;
+  {
+    const int r = lane & (FIELD_R - 1), h = lane >> 5;
+    const int j = j0 + r;
+    cplx v[NR];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+      const int f = 2 * (w + FIELD_W * i) + h;
+      v[i] = make_double2(0.0, 0.0);
+      if (j < n_sel && q0 + f < nvalid) v[i] = ref[(int64_t)(q0 + f) * n_sel + j];
+    }
+#pragma unroll
+    for (int i = 0; i < NR; ++i) tile[r * FIELD_PITCH + 2 * (w + FIELD_W * i) + h] = v[i];
+  }
+  __syncthreads();
+  double a[NSUM > 0 ? NSUM : 1] = {};
+#pragma unroll
+  for (int i = 0; i < NR; ++i) {
+    const int row = w + FIELD_W * i;
+    const int j = j0 + row;
+    if (j >= n_sel) break;   // wave-uniform
+    const int64_t at = (int64_t)sel[j] * Fc + q0 + lane;
+    const cplx r = tile[row * FIELD_PITCH + lane];
+    if (LOSS == PFR_LOSS_FCOTANGENT) {
+      G[at] = make_double2(scale * r.x, scale * r.y);
+      continue;
+    }
+    const double v = wts ? wts[j] : 1.0;
+    const cplx x = X[at];
+    G[at] = r;
+    if (LOSS == PFR_LOSS_FMSE || LOSS == PFR_LOSS_FRMSE) {
+      const double dx = x.x - r.x, dy = x.y - r.y;
+      a[0] += v * (dx * dx + dy * dy);
+      if (LOSS == PFR_LOSS_FRMSE) a[1] += v * (r.x * r.x + r.y * r.y);
+    } else if (LOSS == PFR_LOSS_FMAC) {
+      a[0] += v * (r.x * x.x + r.y * x.y);
+      a[1] += v * (r.x * x.y - r.y * x.x);
+      a[2] += v * (x.x * x.x + x.y * x.y);
+      a[3] += v * (r.x * r.x + r.y * r.y);
+    }
+  }
+  if (NSUM > 0) {
+#pragma unroll
+    for (int k = 0; k < NSUM; ++k) red[(w * NSUM + k) * 64 + lane] = a[k];
+    __syncthreads();
+    if (w == 0) {
+#pragma unroll
+      for (int k = 0; k < NSUM; ++k) {
+        double t = red[k * 64 + lane];
+#pragma unroll
+        for (int u = 1; u < FIELD_W; ++u) t += red[(u * NSUM + k) * 64 + lane];
+        fpart[((int64_t)blockIdx.x * NSUM + k) * Fc + q0 + lane] = t;
+      }
+    }
+  }
+}
+
+// Pass 2, lane = frequency: the tiles' partials summed in ascending tile order, then loss_terms[q] = scale term_q and
+// the seed coefficients fc[q] = scale c1_q, (fc[Fc + q], fc[2 Fc + q]) = scale c2_q; all zero for q >= nvalid.
+// R2 = 0 (FRMSE, FMAC) or X2 = 0 (FMAC) gives a non-finite term (pfr.h).
+template <int LOSS>
+__global__ __launch_bounds__(64) void k_field_finish(const double* __restrict__ fpart, int ntiles, int64_t Fc, int nvalid,
+                                                     double scale, double* __restrict__ loss_terms,
+                                                     double* __restrict__ fc) {
+  constexpr int NSUM = field_nsum(LOSS);
+  const int64_t q = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  double a[NSUM] = {};
+  if ((int64_t)blockIdx.x * 64 < nvalid) {   // pass 1 wrote the partials of these groups
+#pragma unroll 4
+    for (int t = 0; t < ntiles; ++t)
+#pragma unroll
+      for (int k = 0; k < NSUM; ++k) a[k] += fpart[((int64_t)t * NSUM + k) * Fc + q];
+  }
+  double term = 0.0, c1 = 0.0;
+  cplx c2 = make_double2(0.0, 0.0);
+  if (q < nvalid) {
+    if (LOSS == PFR_LOSS_FMSE) {
+      term = a[0];
+      c1 = 2.0;
+      c2.x = -2.0;
+    } else if (LOSS == PFR_LOSS_FRMSE) {
+      term = a[0] / a[1];
+      c1 = 2.0 / a[1];
+      c2.x = -2.0 / a[1];
+    } else {
+      const double s2 = a[0] * a[0] + a[1] * a[1], xr = a[2] * a[3];
+      term = 1.0 - s2 / xr;
+      c1 = 2.0 * s2 / (a[2] * xr);
+      c2 = make_double2(-2.0 * a[0] / xr, 2.0 * a[1] / xr);
+    }
+  }
+  loss_terms[q] = scale * term;
+  fc[q] = scale * c1;
+  fc[Fc + q] = scale * c2.x;
+  fc[2 * Fc + q] = scale * c2.y;
+}
+
+// Pass 3, lane = frequency, one wave per selected row (wave-uniform), in place:
+// G[p Fc + q] = v_j (c1_q conj(X[p Fc + q]) + c2_q conj(G[p Fc + q])), zero for q >= nvalid.
+__global__ __launch_bounds__(64 * FIELD_W) void k_field_seed(const int* __restrict__ sel, const double* __restrict__ wts,
+                                                             int n_sel, const cplx* __restrict__ X, int64_t Fc,
+                                                             int nvalid, const double* __restrict__ fc,
+                                                             cplx* __restrict__ G) {
+  const int j = __builtin_amdgcn_readfirstlane(blockIdx.x * FIELD_W + (threadIdx.x >> 6));
+  if (j >= n_sel) return;
+  const int64_t q = (int64_t)blockIdx.y * 64 + (threadIdx.x & 63);
+  const int64_t at = (int64_t)sel[j] * Fc + q;
+  const double v = wts ? wts[j] : 1.0;
+  const double c1 = fc[q];
+  const cplx c2 = make_double2(fc[Fc + q], fc[2 * Fc + q]);
+  const cplx x = X[at], r = G[at];
+  // c2 conj(r) = (c2.x r.x + c2.y r.y, c2.y r.x - c2.x r.y)
+  cplx g = make_double2(v * (c1 * x.x + (c2.x * r.x + c2.y * r.y)), v * ((c2.y * r.x - c2.x * r.y) - c1 * x.y));
+  if (q >= nvalid) g = make_double2(0.0, 0.0);
+  G[at] = g;
+}
+
 // y = A x (or A^T x) for a batch of matrices on the CSC pattern (InnerState::matvec,
 // InnerState.h:310-470; csc_matvec.h:31-66).  One thread per (column, batch item).
 __global__ void k_matvec(const int* __restrict__ colptr, const int* __restrict__ rowind, int n,
@@ -4155,6 +4305,23 @@ void launch_field_gather(const int* sel, int n_sel, const double2* X, int64_t Fc
   if (n_sel <= 0 || nvalid <= 0) return;
   LAUNCH(k_field_gather, dim3((n_sel + FIELD_R - 1) / FIELD_R, (nvalid + 63) / 64), dim3(64 * FIELD_W), st, sel, n_sel, X,
          Fc, nvalid, out);
+}
+
+void launch_field_loss(const FieldLossArgs& a, const double2* X, int64_t Fc, int nvalid, double2* G, double* fpart,
+                       double* loss_terms, double* fc, hipStream_t st) {
+  if (a.n_sel <= 0 || nvalid <= 0) return;
+  const int ntiles = field_loss_tiles(a.n_sel);
+  const unsigned ngroups = (unsigned)((nvalid + 63) / 64);
+  with_int<PFR_LOSS_FMSE, PFR_LOSS_FRMSE, PFR_LOSS_FMAC, PFR_LOSS_FCOTANGENT>(a.loss_type, [&](auto lt) {
+    LAUNCH(k_field_terms<CV(lt)>, dim3(ntiles, ngroups), dim3(64 * FIELD_W), st, a.sel, a.wts, a.n_sel, a.ref, X, Fc,
+           nvalid, a.scale, G, fpart);
+    if constexpr (CV(lt) != PFR_LOSS_FCOTANGENT) {
+      LAUNCH(k_field_finish<CV(lt)>, dim3((unsigned)(Fc / 64)), dim3(64), st, fpart, ntiles, Fc, nvalid, a.scale,
+             loss_terms, fc);
+      LAUNCH(k_field_seed, dim3((a.n_sel + FIELD_W - 1) / FIELD_W, ngroups), dim3(64 * FIELD_W), st, a.sel, a.wts,
+             a.n_sel, X, Fc, nvalid, fc, G);
+    }
+  });
 }
 
 void launch_matvec(const int* colptr, const int* rowind, int n, const double2* data, int64_t ds, const double2* x,

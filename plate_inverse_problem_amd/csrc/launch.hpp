@@ -201,6 +201,29 @@ void launch_unpermute(const int* perm, int n, const double2* X, int64_t Fc, int 
 constexpr int FIELD_R = 32;
 void launch_field_gather(const int* sel, int n_sel, const double2* X, int64_t Fc, int nvalid, double2* out,
                          hipStream_t st);
+// pfr_field_loss_sweep between the forward solve and the adjoint: the loss PFR_LOSS_F* on the selected rows of X against
+// ref (the chunk's first row of the caller's frequency-major array; wts NULL: all 1) and its seed into G (zeroed by the
+// caller): G[sel[j] * Fc + q] = scale g_j, loss_terms[q] = scale term_q (both zero for q >= nvalid).  fpart:
+// field_loss_parts(loss, n_sel, Fc) doubles, fc: 3 x Fc doubles (both unused by FCOTANGENT, which writes scale * ref and
+// leaves loss_terms alone).  sel must hold no row twice (the seed is a scatter).
+struct FieldLossArgs {
+  int32_t loss_type = 0;
+  const int32_t* sel = nullptr;
+  const double* wts = nullptr;
+  int32_t n_sel = 0;
+  const double2* ref = nullptr;
+  double scale = 1.0;
+};
+inline int field_loss_tiles(int n_sel) { return (n_sel + FIELD_R - 1) / FIELD_R; }
+// the sums a loss keeps per tile and frequency, and the partial buffer's doubles for a selection
+constexpr int field_nsum(int loss) {
+  return loss == PFR_LOSS_FMSE ? 1 : loss == PFR_LOSS_FRMSE ? 2 : loss == PFR_LOSS_FMAC ? 4 : 0;
+}
+inline int64_t field_loss_parts(int loss, int n_sel, int64_t Fc) {
+  return (int64_t)field_loss_tiles(n_sel) * field_nsum(loss) * Fc;
+}
+void launch_field_loss(const FieldLossArgs& a, const double2* X, int64_t Fc, int nvalid, double2* G, double* fpart,
+                       double* loss_terms, double* fc, hipStream_t st);
 void launch_matvec(const int* colptr, const int* rowind, int n, const double2* data, int64_t ds, const double2* x,
                    int64_t xs, double2* y, int transpose, int batch, hipStream_t st);
 // a chunk's frequencies (padded with the last) and its flags cleared, one kernel

@@ -520,6 +520,42 @@ std::string field_rows(const std::vector<int32_t>& iperm, int32_t n_rows, const 
   return "";
 }
 
+std::string field_loss_rows(const std::vector<int32_t>& iperm, int32_t n_rows, const int32_t* rows,
+                            const double* weights, bool cotangent, std::vector<int32_t>& out) {
+  out.clear();
+  char buf[160];
+  const int64_t n = (int64_t)iperm.size();
+  if (!rows && n <= 0) return "field loss sweep: no rows";
+  if (rows && n_rows <= 0) return "field loss sweep: a row list needs at least one row";
+  if (weights && cotangent)
+    return "field loss sweep: weights do not apply to PFR_LOSS_FCOTANGENT (the cotangent carries them)";
+  if (weights) {
+    const int64_t n_sel = rows ? n_rows : n;
+    bool any = false;
+    for (int64_t j = 0; j < n_sel; ++j) {
+      const double v = weights[j];
+      if (!(v >= 0.0) || v > 1.7976931348623157e308) {   // negative, NaN or infinite
+        snprintf(buf, sizeof buf, "field loss sweep: weight %lld = %g is negative or not finite", (long long)j, v);
+        return buf;
+      }
+      any = any || v > 0.0;
+    }
+    if (!any) return "field loss sweep: every weight is zero";
+  }
+  if (!rows) return "";
+  std::string refusal = field_rows(iperm, n_rows, rows, out);
+  std::vector<char> seen((size_t)n, 0);
+  for (int32_t j = 0; refusal.empty() && j < n_rows; ++j) {
+    if (seen[rows[j]]) {
+      snprintf(buf, sizeof buf, "field loss sweep: row %d = %d repeats an earlier one", (int)j, (int)rows[j]);
+      refusal = buf;
+    }
+    seen[rows[j]] = 1;
+  }
+  if (!refusal.empty()) out.clear();
+  return refusal;
+}
+
 std::string check_plan(const Symbolic& S, const Plan& P, int64_t Fc) {
   char buf[256];
   auto bad = [&](const char* what, int64_t at, int64_t v, int64_t lim) {

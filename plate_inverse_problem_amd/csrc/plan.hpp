@@ -188,6 +188,13 @@ void reach_lists(const std::vector<int32_t>& front_of_col, const std::vector<int
 // null list, an index outside [0, n)); `out` is complete only on "".
 std::string field_rows(const std::vector<int32_t>& iperm, int32_t n_rows, const int32_t* rows, std::vector<int32_t>& out);
 
+// The selection and weights of a field-loss sweep (pfr_field_loss_sweep).  rows as in field_rows, but no row twice (the
+// adjoint seed is a scatter); rows NULL: all n rows in order (n_rows ignored, `out` left empty: the caller walks iperm).
+// weights (NULL: all 1): one per selected row, finite, >= 0, not all zero; refused together with cotangent (the
+// caller's dL/dx carries them).  Returns "" or the refusal; `out` is complete only on "".
+std::string field_loss_rows(const std::vector<int32_t>& iperm, int32_t n_rows, const int32_t* rows,
+                            const double* weights, bool cotangent, std::vector<int32_t>& out);
+
 // Every index each launch of a solver with chunk Fc takes from the plan, against the buffer it addresses
 // (element ids < factor entries, nz < nnz, record offsets and overflow ranges inside their arrays, the
 // per-workgroup partial buffers against the grids that write them).  Returns "" or the first violation.

@@ -7,6 +7,9 @@ ranks of an initialised ``torch.distributed`` group (one all-reduce per
 evaluation, every rank runs the identical optimiser).  Extra optimizers:
 ``'lbfgs'`` (BASELINE.json C5) and ``'lm'`` / ``'levenberg_marquardt'`` (least squares over
 ``Problem.getResidualFunction``'s residual and per-frequency Jacobian; single process).
+Full-field data: a ``FIELD_MSE`` / ``FIELD_RMSE`` / ``FIELD_MAC`` loss type with ``ref_field=(freqs, field)``,
+``field_dofs`` and ``field_weights`` fits ``Problem.getFieldLossFunction`` with the gradient optimisers and the
+non-vectorised ``de`` / ``shgo``.
 """
 from __future__ import annotations
 
@@ -18,6 +21,7 @@ import torch
 from scipy.optimize import OptimizeResult, differential_evolution, shgo
 
 from . import Optimizers as opt
+from . import _native
 from .Input import Compressor
 
 _LOCAL = {("trust_region", "tr"): opt.optimize_trust_region, ("coord_descent", "cd"): opt.optimize_cd,
@@ -32,7 +36,25 @@ def _a2s(s):
 def solve_inverse(prob, arg0, loss_type: str, optimizer: str, compression=(False, 0), comp_alg: int = 1,
                   ref_fr=None, use_rel: bool = False, use_scaling: bool = False, use_constraints: bool = False,
                   report: bool = True, log: bool = True, case_name: str = '', uid: str = None,
-                  extra_info: str = '', log_dir: str = None, distributed: bool = False, **opt_kwargs):
+                  extra_info: str = '', log_dir: str = None, distributed: bool = False, ref_field=None,
+                  field_dofs=None, field_weights=None, **opt_kwargs):
+    field = loss_type in _native.FIELD_LOSS_IDS
+    if field:
+        # full-field data: (frequencies, field (F, n_sel)) in place of ref_fr; the loss is Problem.getFieldLossFunction
+        if ref_field is None:
+            raise ValueError(f'the loss "{loss_type}" fits full-field data: pass ref_field=(freqs, field)')
+        no = {'the trust region needs the Hessian of the field loss, which is not built': optimizer in ('trust_region', 'tr'),
+              'Levenberg-Marquardt needs the field Jacobian, which is not built': optimizer in ('levenberg_marquardt', 'lm'),
+              'the field loss has no population form': bool(opt_kwargs.get('vectorized', False)),
+              'the field loss has no distributed form': distributed,
+              'the compression selects frequencies from a response curve, which field data does not carry':
+                  bool(compression[0]) if isinstance(compression, tuple) and len(compression) == 2 else False}
+        for why, hit in no.items():
+            if hit:
+                raise NotImplementedError(f'solveInverse with "{loss_type}": {why}')
+        ref_fr = (np.asarray(ref_field[0]), np.asarray(ref_field[1]))
+    elif ref_field is not None or field_dofs is not None or field_weights is not None:
+        raise ValueError(f'ref_field, field_dofs and field_weights go with a FIELD_* loss, not "{loss_type}"')
     if ref_fr is None:
         ref_fr = getattr(prob, 'reference_fr', None)
         if ref_fr is None:
@@ -72,7 +94,10 @@ def solve_inverse(prob, arg0, loss_type: str, optimizer: str, compression=(False
 
     if distributed and optimizer in ('levenberg_marquardt', 'lm'):
         raise NotImplementedError('the Jacobian sweep is not distributed: use `lm` with distributed=False')
-    loss = prob.getLossFunction(ref_fr[0], ref_fr[1], loss_type, scaling, distributed=distributed)
+    if field:
+        loss = prob.getFieldLossFunction(ref_fr[0], ref_fr[1], loss_type, field_dofs, field_weights, scaling)
+    else:
+        loss = prob.getLossFunction(ref_fr[0], ref_fr[1], loss_type, scaling, distributed=distributed)
     scale_arr = np.ones_like(x0) if scaling is None else (np.tile(scaling, (2, 1)).T if x0.ndim == 2 else scaling)
 
     local = next((fn for names, fn in _LOCAL.items() if optimizer in names), None)
