@@ -344,6 +344,56 @@ PFR_API int pfr_sweep_complex(pfr_solver* s, int32_t nfreq, const double* freqs_
                               double* w_dev, int32_t* flags_dev, int32_t fresh /* as pfr_sweep_fresh */, void* stream);
 PFR_API int pfr_jacobian_sweep_complex(pfr_solver* s, int32_t nfreq, const double* freqs_dev, const double* axis,
                                        double* h_dev /* may be NULL */, double* jc_dev, int32_t* flags_dev, void* stream);
+/* The inertia rows: sensitivities to the other half of the operator.  With the mass matrix split into n_mass components,
+ *   A(omega) = K - omega^2 sum_j I_j G_j,   b(omega) = rhs (beta - omega^2 sum_j d_j I_j),
+ * pfr_set_inertia registers the components G_j (mass_dev: (nnz, n_mass) real, entry-major like pfr_set_stiffness' table;
+ * n_mass 1 .. 4) and their load weights d_j (rhs_weights, host).  It takes an entry-ordered copy of the table (after
+ * changing the values, call it again), lists the pattern entries on which some component is non-zero -- under pruning
+ * only those on the loaded trees' rows; the list follows pfr_set_prune and a pfr_set_rhs that changes the loaded trees --
+ * and, like every setter, ends the captured graph.  It does not touch M or mass_sum: the caller keeps pfr_set_operator's
+ * M = sum_j I_j G_j and pfr_set_rhs' mass_sum = sum_j d_j I_j consistent with its coefficients I_j, which the library
+ * never sees.
+ * pfr_inertia_sweep is pfr_jacobian_sweep (axis == NULL: resp_dev holds fr, real nfreq) or pfr_jacobian_sweep_complex
+ * (axis: 3 host doubles, resp_dev holds the complex H) with one more output per frequency,
+ *   jm_dev[q * n_mass + j] = omega_q^2 ( m_q mu_q^T G_j x_q - d_j t_q )        (complex, WRITTEN, every row q < nfreq),
+ * m_q and t_q = m_q mu_q^T rhs the cotangent scale and load term of the rows jc, omega_q = 2 pi f_q, so that
+ *   d fr_q / d I_j = Re jm[q][j]      (the complex response: d H_q / d I_j = jm[q][j], no real part taken).
+ * resp_dev and jc_dev may be NULL (jc_dev NULL: the stiffness contraction is skipped and pfr_set_stiffness is not
+ * needed); what they receive, the flags and the pfr_set_check backward errors are bitwise those of the Jacobian sweep
+ * on the same solver state.  Two identities tie the rows together, in every check mode:
+ *   homogeneity:      sum_k c_k jc[q][k] + sum_j I_j jm[q][j] = 0       (complex; scaling K, beta, M and mass_sum alike
+ *                                                                         leaves x where it is)
+ *   frequency slope:  d fr_q / d f = (2 / f_q) Re sum_j I_j jm[q][j]    (f in Hz; H: the same without Re)
+ * Every pfr_set_check mode applies as in the Jacobian sweeps (PFR_CHECK_REFINE_ADJ: honoured for fr, PFR_ERR_ARG with
+ * an axis).  Per chunk, after k_jac_finish: k_contract_mass (lane = frequency, the listed entries only, fixed order, no
+ * atomics; its partials take the stiffness partials' buffer) and k_inertia_finish.  Never part of the PFR_GRAPH graph;
+ * the next loss sweep is bit-identical to one run without it.
+ * PFR_ERR_ARG before any launch: a null solver or jm_dev, nfreq <= 0, a zero or non-finite axis, n_mass outside 1 .. 4
+ * (pfr_set_inertia).  PFR_ERR_STATE: no operator, rhs or functional, no pfr_set_inertia, jc_dev without pfr_set_stiffness.
+ * Out of scope: inertia rows in pfr_population_sweep, pfr_hessian_sweep and pfr_field_loss_sweep, and across devices.
+ * The reference has no analogue: its inertia constants are Python floats closed over by _solve (Problem.py).
+ * pfr_symbolic_mass_list (host only, no device): the list pfr_set_inertia builds for the table mass_host on this
+ * analysis -- prune != 0: for the trees loaded by rhs (caller numbering; symmetric analyses), else every row.  Returns
+ * the number of listed entries (-1: bad arguments or a capacity below what is written).  The contraction's waves each
+ * own a fixed range of the contraction entries, the same on every view (so that a view's rows equal the full walk's bit
+ * for bit); list (may be NULL) receives the listed positions in ascending order, wave by wave, each wave's run padded
+ * with -1 to whole 4-entry batches, ptr (may be NULL) the first batch of each wave's run and the end (waves + 1);
+ * entries (may be NULL; capacity in int32) the contraction entries, four int32 each: permuted column, matrix entry
+ * (i, j) or -1, matrix entry (j, i) or -1, permuted row; counts (may be NULL, 3): the contraction entries, the list's
+ * padded length, the waves.
+ * pfr_solver_mass_list: the count for the view the operator-form sweeps walk now (-1 before pfr_set_inertia), *padded
+ * (may be NULL) the length on the device. */
+PFR_API int pfr_set_inertia(pfr_solver* s, int32_t n_mass /* 1..4 */, const double* mass_dev /* (nnz, n_mass) */,
+                            const double* rhs_weights /* host, n_mass: d_j */);
+PFR_API int pfr_inertia_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev,
+                              const double* axis /* host, 3, or NULL: the magnitude fr */,
+                              double* resp_dev /* may be NULL */, double* jc_dev /* may be NULL */, double* jm_dev,
+                              int32_t* flags_dev /* may be NULL */, void* stream);
+PFR_API int32_t pfr_symbolic_mass_list(const pfr_symbolic* sym, const double* rhs, int32_t prune, int32_t n_mass,
+                                       const double* mass_host, int32_t* list, int64_t capacity, int32_t* ptr,
+                                       int64_t ptr_capacity, int32_t* entries, int64_t entries_capacity,
+                                       int32_t* counts);
+PFR_API int32_t pfr_solver_mass_list(const pfr_solver* s, int32_t* padded);
 /* The field: the solution x_q of (K - omega_q^2 M) x = b itself, at every frequency, for the rows the caller selects
  * -- the operating deflection shapes over a band, and the data under the reference's Problem.getModePicture
  * (Problem.py:521-608, one UMFPACK solve per picture).

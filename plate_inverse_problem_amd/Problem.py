@@ -114,7 +114,8 @@ class _LaneThread:
 _LANE_CALLS = {("sweep", False): ("sweep", "fr"), ("sweep", True): ("sweep_complex", "h"),
                ("jacobian", False): ("jacobian_sweep", "fr"), ("jacobian", True): ("jacobian_sweep_complex", "h"),
                ("population", False): ("population_sweep", "fr"), ("hessian", False): ("hessian_sweep", None),
-               ("field", False): ("field_sweep", "fr"), ("field_loss", False): ("field_loss_sweep", None)}
+               ("field", False): ("field_sweep", "fr"), ("field_loss", False): ("field_loss_sweep", None),
+               ("inertia", False): ("inertia_sweep", "resp"), ("inertia", True): ("inertia_sweep", "resp")}
 _NO_ARGS = {}
 
 
@@ -182,6 +183,12 @@ class _Engine:
             + I2 * vals[24] + I2c * vals[25]                                                  # Problem.py:441-443
         self.mass = torch.as_tensor(np.ascontiguousarray(mass), device=device)
         self.mass_sum = I0 + I0c + I2 + I2c
+        # inertia sweeps (set_inertia / inertia_sweep): the constants the operator holds now, the problem's own, and --
+        # built at first use -- the four mass matrices G_j on the host and as the device table the lanes register
+        self.inertia = self.own_inertia = (I0, I0c, I2, I2c)
+        self._mats = prob.mats
+        self._G = self._G_dev = None
+        self._inertia_lanes = None     # the solvers pfr_set_inertia was called on
         self.K = torch.empty(self.keep.size, dtype=torch.complex128, device=device)
         self.e = np.concatenate([np.zeros(12), RHS_WEIGHTS_D])
         aU, aV, aW = prob.averaging_vectors()
@@ -635,6 +642,50 @@ class _Engine:
                                              axis=axis, resp=fr, berr=berr), n, {})
         self.record(flags, berr)
 
+    def set_inertia(self, I):
+        """The inertia constants ``I = (I0, I0Corr, I2, I2Corr)`` of every later sweep: ``mass = sum_j I_j G_j``
+        recombined on the host with the constructor's expression (at the problem's own constants: the same bits),
+        uploaded into the lanes' mass buffer, ``mass_sum`` with it (the lanes' rhs scale follows at the next
+        ``set_coefficients``).  No symbolic analysis, no new solver.  Memoised on the last ``I``."""
+        I = tuple(float(v) for v in I)
+        if len(I) != 4:
+            raise ValueError('set_inertia takes (I0, I0Corr, I2, I2Corr)')
+        if I == self.inertia:
+            return
+        I0, I0c, I2, I2c = I
+        G = self._mass_parts()
+        mass = I0 * G[0] + I0c * G[1] + I2 * G[2] + I2c * G[3]
+        self.mass.copy_(torch.as_tensor(np.ascontiguousarray(mass)))
+        self.mass_sum = I0 + I0c + I2 + I2c
+        self.inertia = I
+        for sv in self.solvers:
+            sv.set_operator(torch.view_as_real(self.K), self.mass)
+        self._coef_key = None          # set_rhs on every lane with the new mass_sum, at the next set_coefficients
+
+    def _mass_parts(self):
+        """G_0 .. G_3 (4, nnz) on the host: v18 + v20 + v22, v19 + v21 + v23, v24, v25 of the kept entries."""
+        if self._G is None:
+            v = self._mats[18:26][:, self.keep]
+            self._G = np.stack([v[0] + v[2] + v[4], v[1] + v[3] + v[5], v[6], v[7]])
+        return self._G
+
+    def inertia_sweep(self, freqs, jm, jc=None, fr=None, flags=None, berr=None, axis=None):
+        """``Solver.inertia_sweep`` over all lanes: the Jacobian sweep with the inertia rows ``jm`` (F, 4) complex,
+        ``d fr_q / d I_j = Re jm[q, j]`` (``axis``: ``d H_q / d I_j = jm[q, j]``); ``jc`` (F, n_stiff) may be None.
+        The lanes register the mass matrices (pfr_set_inertia, load weights 1) at the first call.  Sets ``last_berr``
+        and ``last_flags``."""
+        if self._inertia_lanes is not self.solvers:
+            if self._G_dev is None:
+                self._G_dev = torch.as_tensor(np.ascontiguousarray(self._mass_parts().T), device=self.device)
+            for sv in self.solvers:
+                sv.set_inertia(self._G_dev, np.ones(4))
+            self._inertia_lanes = self.solvers
+        n = freqs.numel()
+        per_freq = dict(freqs=freqs, jm=torch.view_as_real(jm), jc=None if jc is None else torch.view_as_real(jc),
+                        flags=flags)
+        self._sweep_lanes(self._lane_request("inertia", n, per_freq, axis=axis, resp=fr, berr=berr), n, {})
+        self.record(flags, berr)
+
     def field_sweep(self, freqs, rows=None, fr=None):
         """``Solver.field_sweep`` over all lanes: the solution's rows ``rows`` (host, caller numbering; None: every
         row) at every frequency as an (F, n_sel) complex128 device tensor -- frequency-major, so every lane writes
@@ -944,6 +995,63 @@ class _FieldResponse(torch.autograd.Function):
         return torch.conj(torch.from_numpy(w)).resolve_conj(), None, None, None
 
 
+EXTRA_NAMES = ('rho', 'h', 'acc_mass')
+
+
+def inertia_constants(rho, h, acc, acc_mass=None):
+    """``(I (4,), dI (4, 3))`` (host, numpy): the inertia constants ``(I0, I0Corr, I2, I2Corr)`` of a plate of density
+    ``rho`` and thickness ``h`` under the accelerometer ``acc`` (its mass ``acc_mass``, default ``acc.mass``) -- the
+    lines of ``Problem._build_system``, the same bits at the problem's own values -- and their derivatives with
+    respect to ``EXTRA_NAMES`` = (rho, h, acc_mass), closed form."""
+    rho, h, m = float(rho), float(h), float(acc.mass if acc_mass is None else acc_mass)
+    area_h = 1.0 / (np.pi * acc.radius ** 2) / acc.height        # d rho_corr / d acc_mass
+    rho_corr = m / (np.pi * acc.radius ** 2) / acc.height
+    top = h / 2 + acc.height
+    I = np.array([h * rho, acc.height * rho_corr, rho * h ** 3 / 12, rho_corr / 3 * (top ** 3 - h ** 3 / 8)])
+    dI = np.array([[h, rho, 0.0],
+                   [0.0, 0.0, acc.height * area_h],
+                   [h ** 3 / 12, rho * h ** 2 / 4, 0.0],
+                   [0.0, rho_corr / 3 * (1.5 * top ** 2 - 0.375 * h ** 2), area_h / 3 * (top ** 3 - h ** 3 / 8)]])
+    return I, dI
+
+
+def thickness_scaling(h, h0):
+    """(18,) ``(h / h0) ** (1, 2, 3)`` on the A, B, D blocks of six: ``c(h) = c(h0) * thickness_scaling(h, h0)``, exact
+    for every laminate map here (A ~ h, B ~ h^2, D ~ h^3: the ply coordinates are ``linspace(-h / 2, h / 2)``); so
+    ``d c_k / d h = (1, 2, 3) / h * c_k``."""
+    return np.repeat((h / h0) ** np.array([1.0, 2.0, 3.0]), 6)
+
+
+def check_extra(extra):
+    """The names of the extended parameters as a tuple, each of ``EXTRA_NAMES`` at most once."""
+    extra = (extra,) if isinstance(extra, str) else tuple(extra)
+    if not extra or any(e not in EXTRA_NAMES for e in extra) or len(set(extra)) != len(extra):
+        raise ValueError(f'`extra` is a tuple of distinct names from {EXTRA_NAMES}, not {extra}')
+    return extra
+
+
+def loss_and_gradient(r, Jr, const, n_freqs: int):
+    """``(loss, grad)`` of a least-squares loss from its residual: ``(r @ r + const) / F`` and ``2 Jr^T r / F``
+    (``Jr`` None: no gradient)."""
+    return (float(r @ r) + const) / n_freqs, None if Jr is None else 2.0 * (Jr.T @ r) / n_freqs
+
+
+class _ResidualLoss(torch.autograd.Function):
+    """A loss whose value and gradient come from one residual evaluation on the host (``res(params) -> (r, Jr,
+    const)``): one sweep per evaluation, for the gradient optimisers."""
+
+    @staticmethod
+    def forward(ctx, params, res, n_freqs):
+        r, Jr, const = res(params.detach().cpu().numpy())
+        loss, grad = loss_and_gradient(r, Jr, const, n_freqs)
+        ctx.grad = torch.as_tensor(grad, dtype=params.dtype)
+        return torch.tensor(loss, dtype=torch.float64)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g * ctx.grad.to(g.device), None, None
+
+
 def residual_terms(fr, reference_fr, func_type: str):
     """The four losses as least squares (host, numpy): ``(r, dr/dfr, const)`` with
     ``loss = (r @ r + const) / F`` and ``d loss / d fr = 2 r dr/dfr / F``.
@@ -1039,10 +1147,10 @@ def population_loss_grad(fr, jc, dc, reference_fr, func_type: str):
     grad = None if jc is None else np.empty((P, np.asarray(dc).shape[2]))
     for p in range(P):
         r, drdfr, const = residual_terms(fr[p], reference_fr, func_type)
-        loss[p] = (float(r @ r) + const) / F
+        Jr = None if jc is None else drdfr[:, None] * np.real(np.asarray(jc[p]) @ np.asarray(dc[p]))
+        loss[p], g = loss_and_gradient(r, Jr, const, F)
         if jc is not None:
-            Jr = drdfr[:, None] * np.real(np.asarray(jc[p]) @ np.asarray(dc[p]))
-            grad[p] = 2.0 * (Jr.T @ r) / F
+            grad[p] = g
     return loss, grad
 
 
@@ -1416,7 +1524,7 @@ class Problem:
         return self.mesh, values
 
     def getFieldLossFunction(self, frequencies, reference_field, func_type: str, dofs=None, weights=None,
-                             scaling_params=None) -> Callable:
+                             scaling_params=None, extra=None) -> Callable:
         """``loss(params) -> 0-dim tensor`` with autograd: full-field data -- a scanning vibrometer's deflection shapes
         ``reference_field`` (F, n_sel) complex at the rows ``dofs`` (of the system ``[u (Lh); v (Lh); w (Mh)]``, no
         repeats; None: every row) -- fitted directly (pfr_field_loss_sweep).  With x the solution's selected rows, r
@@ -1426,6 +1534,8 @@ class Problem:
         the amplitude and phase of either shape: the form for a scan whose excitation level is not known.  x is the
         number the solver gives, not conjugated (``getTFFunction``).  The reference is validated on the host and has
         to fit the device beside the workspaces (``solveForwardField``)."""
+        if extra is not None:
+            raise NotImplementedError('the field-loss sweep has no inertia rows: extra is not supported here')
         if func_type not in _native.FIELD_LOSS_IDS:
             raise ValueError(f'Function type "{func_type}" is not a field loss {tuple(_native.FIELD_LOSS_IDS)}')
         loss_id = _native.FIELD_LOSS_IDS[func_type]
@@ -1471,8 +1581,11 @@ class Problem:
         return field_function
 
     def getLossFunction(self, frequencies, reference_fr, func_type: str, scaling_params=None,
-                        *, distributed: bool = False, axis=None) -> Callable:
+                        *, distributed: bool = False, axis=None, extra=None) -> Callable:
         """``loss(params) -> 0-dim tensor`` (``Problem.py:933-980``).
+
+        ``extra`` (names from ``EXTRA_NAMES``): a function of the extended vector ``[material params, extra values]``
+        (``getFRJacobianFunction``), its value and gradient ``2 Jr^T r / F`` from ONE inertia sweep per evaluation.
 
         ``func_type`` MSE_COMPLEX, RMSE_COMPLEX or MSE_LOG_COMPLEX: the mean over the frequencies of ``|H - ref|^2``,
         ``|H - ref|^2 / |ref|^2`` or ``|log(H / ref)|^2`` of the complex response H along ``axis`` (``getTFFunction``;
@@ -1482,6 +1595,17 @@ class Problem:
         every rank sweeps its contiguous block of the frequencies and one
         all-reduce combines loss and gradient partials.
         """
+        if extra is not None:
+            if distributed:
+                raise NotImplementedError('the inertia sweep is not distributed: use extra with distributed=False')
+            res = self.getResidualFunction(frequencies, reference_fr, func_type, scaling_params, axis, extra=extra)
+            n_freqs = np.asarray(frequencies).shape[0]
+
+            def loss_extra(params):
+                p = params if isinstance(params, torch.Tensor) else torch.as_tensor(np.asarray(params, dtype=np.float64))
+                return _ResidualLoss.apply(p, res, n_freqs)
+
+            return loss_extra
         s = self._loss_setup(frequencies, reference_fr, func_type, scaling_params, distributed, axis)
         scaling = 1.0 if scaling_params is None else torch.as_tensor(s.scaling)
         transform = self._transform()
@@ -1520,7 +1644,7 @@ class Problem:
                                scaling=1.0 if scaling_params is None else np.array(scaling_params, dtype=np.float64))
 
     def getLossHessianFunction(self, frequencies, reference_fr, func_type: str, scaling_params=None,
-                               *, distributed: bool = False) -> Callable:
+                               *, distributed: bool = False, extra=None) -> Callable:
         """``model(params) -> (loss, grad, hessian)`` (numpy) of ``getLossFunction``'s loss.
 
         Replaces the reference's forward-over-reverse Hessian (``jax.jacobian(grad)``,
@@ -1531,6 +1655,8 @@ class Problem:
         direction; the material transform's first and second derivatives come
         from torch autograd on the host.
         """
+        if extra is not None:
+            raise NotImplementedError('the Hessian sweep has no inertia rows: extra is not supported here')
         s = self._loss_setup(frequencies, reference_fr, func_type, scaling_params, distributed, no_complex='Hessian')
         c_and_dc = self._coeffs_jacobian(scaling_params)       # on the jet materials the same c (to the bit) as
         c_real = c_and_dc.c_real                               # getLossFunction's jet transform
@@ -1562,15 +1688,95 @@ class Problem:
 
         return model
 
-    def getFRJacobianFunction(self, scaling_params=None) -> Callable:
+    def getFRJacobianFunction(self, scaling_params=None, extra=None) -> Callable:
         """``fn(freqs, params) -> (fr (F,), J (F, n_params))``, float64 tensors on the device:
         ``J[q, i] = d fr_q / d params_i`` from ONE sweep (one factorisation and one adjoint solve per frequency,
         pfr_jacobian_sweep), where reverse mode through ``getFRFunction`` needs one adjoint sweep per frequency.
-        ``scaling_params``: the function is of ``params * scaling_params`` and J is with respect to ``params``."""
-        return self._jacobian_function(scaling_params, None)
+        ``scaling_params``: the function is of ``params * scaling_params`` and J is with respect to ``params``.
 
-    def _jacobian_function(self, scaling_params, axis) -> Callable:
+        ``extra``: a tuple of names from ``EXTRA_NAMES`` = ('rho', 'h', 'acc_mass') -- the plate's density, its
+        thickness and the accelerometer's mass as parameters too.  ``params`` is then ``[material params, extra
+        values]`` in physical units (``scaling_params`` spans all of it) and J gains one column per name, from the
+        inertia rows of the same sweep (pfr_inertia_sweep): ``Re(jm @ dI/dname)``, for ``h`` plus ``Re(jc @ dc/dh)``
+        (``inertia_constants``, ``thickness_scaling``).  Values other than the problem's own are set for the call --
+        the mass matrix recombined and uploaded (``_Engine.set_inertia``), no new analysis -- and the problem's own
+        put back after it: a later call without ``extra`` returns the bits it returned before."""
+        return self._jacobian_function(scaling_params, None, extra)
+
+    def extendedParameters(self, extra) -> np.ndarray:
+        """``[material parameters, the problem's own values of the names in extra]``."""
+        own = dict(rho=self.rho, h=self.geometry.height, acc_mass=self.accelerometer.mass)
+        return np.concatenate([np.asarray(self.parameters, dtype=np.float64), [own[e] for e in check_extra(extra)]])
+
+    def _extended(self, scaling_params, extra):
+        """``fn(params) -> (c (18,), dc (18, n_params), I (4,), dI (4, n_params))`` for the extended vector: the
+        coefficients at the thickness in ``params`` (the material's at the problem's thickness times
+        ``thickness_scaling``) and the inertia constants, with their derivatives with respect to ``params``."""
+        extra = check_extra(extra)
+        c_and_dc = self._coeffs_jacobian(None)
+        h0 = float(self.geometry.height)
+        power = np.repeat([1.0, 2.0, 3.0], 6)
+
+        def fn(params):
+            p = np.asarray(params.detach().cpu() if isinstance(params, torch.Tensor) else params, dtype=np.float64)
+            sc = np.ones(p.size) if scaling_params is None else \
+                np.broadcast_to(np.asarray(scaling_params, dtype=np.float64), (p.size,))
+            n_mat = p.size - len(extra)
+            if n_mat <= 0:
+                raise ValueError(f'the parameter vector holds the material parameters and then {extra}')
+            phys = p * sc
+            val = dict(rho=self.rho, h=h0, acc_mass=self.accelerometer.mass)
+            val.update(zip(extra, phys[n_mat:]))
+            c0, dc0 = c_and_dc(phys[:n_mat])
+            hs = thickness_scaling(val['h'], h0)
+            c = c0 * hs
+            I, dI3 = inertia_constants(val['rho'], val['h'], self.accelerometer, val['acc_mass'])
+            dc = np.zeros((18, p.size), dtype=np.complex128)
+            dI = np.zeros((4, p.size))
+            dc[:, :n_mat] = dc0 * hs[:, None]
+            for i, name in enumerate(extra):
+                dI[:, n_mat + i] = dI3[:, EXTRA_NAMES.index(name)]
+                if name == 'h':
+                    dc[:, n_mat + i] = power / val['h'] * c
+            return c, dc * sc[None, :], I, dI * sc[None, :]
+
+        fn.extra = extra
+        return fn
+
+    def _inertia_rows(self, f, c, I, axis, with_jc=True):
+        """One inertia sweep at the coefficients ``c`` and inertia constants ``I``: ``(response, jc or None, jm)`` on
+        the device; the problem's own constants are put back afterwards."""
+        eng = self.engine(f.numel())
+        try:
+            eng.set_inertia(I)
+            eng.set_coefficients(c)
+            out, flags, berr, jc = eng.outputs(f.numel(), torch.float64 if axis is None else torch.complex128,
+                                               jc=with_jc)
+            jm = torch.empty((f.numel(), 4), dtype=torch.complex128, device=eng.device)
+            eng.inertia_sweep(f, jm, jc=jc, fr=out, flags=flags, berr=berr, axis=axis)
+        finally:
+            eng.set_inertia(eng.own_inertia)
+        return out, jc, jm
+
+    def _jacobian_function(self, scaling_params, axis, extra=None) -> Callable:
         """``getFRJacobianFunction`` (``axis`` None) or ``getTFJacobianFunction`` along the checked ``axis``."""
+        if extra is not None:
+            ext = self._extended(scaling_params, extra)
+
+            def fn_extra(freqs, params):
+                f = self._freqs(freqs)
+                c, dc, I, dI = ext(params)
+                out, jc, jm = self._inertia_rows(f, c, I, axis)
+                eng = self._engine
+                n_mat = dc.shape[1] - len(ext.extra)
+                dev = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.complex128), device=eng.device)  # noqa: E731
+                # the material columns by the product the call without extra makes (the same bits at the problem's
+                # own values); the extra ones from the inertia rows, for h with the coefficients' share
+                J = torch.cat([jc @ dev(dc[eng.kidx][:, :n_mat]),
+                               jc @ dev(dc[eng.kidx][:, n_mat:]) + jm @ dev(dI[:, n_mat:])], dim=1)
+                return out, torch.real(J) if axis is None else J
+
+            return fn_extra
         c_and_dc = self._coeffs_jacobian(scaling_params)
 
         def fn(freqs, params):
@@ -1613,23 +1819,38 @@ class Problem:
         fn.c_real = c_real
         return fn
 
-    def getTFJacobianFunction(self, scaling_params=None, axis=(0, 0, 1)) -> Callable:
+    def getTFJacobianFunction(self, scaling_params=None, axis=(0, 0, 1), extra=None) -> Callable:
         """``fn(freqs, params) -> (H (F,), dH (F, n_params))``, complex128 tensors on the device: the complex response
         along ``axis`` (``getTFFunction``) and ``dH[q, i] = d H_q / d params_i`` from ONE sweep
         (pfr_jacobian_sweep_complex); H is holomorphic in the coefficients, so no real part is taken.
-        ``scaling_params`` as in ``getFRJacobianFunction``."""
-        return self._jacobian_function(scaling_params, _sensing_axis(axis))
+        ``scaling_params`` and ``extra`` as in ``getFRJacobianFunction``."""
+        return self._jacobian_function(scaling_params, _sensing_axis(axis), extra)
 
-    def solveForwardJacobian(self, freqs, params=None):
+    def solveForwardJacobian(self, freqs, params=None, extra=None):
         """``(fr (F,), J (F, n_params))`` (numpy): the frequency response and its derivative with respect to the
-        material parameters at every frequency."""
+        material parameters -- with ``extra`` (``getFRJacobianFunction``) also the named ones of density, thickness
+        and accelerometer mass -- at every frequency."""
         if params is None:
-            params = self.parameters
-        fr, J = self.getFRJacobianFunction()(freqs, params)
+            params = self.parameters if extra is None else self.extendedParameters(extra)
+        fr, J = self.getFRJacobianFunction(extra=extra)(freqs, params)
         return fr.cpu().numpy(), J.cpu().numpy()
 
+    def solveForwardSlope(self, freqs, params=None):
+        """``(fr (F,), d fr / d f (F,))`` (numpy), f in Hz: the response and its slope along the frequency axis from
+        one inertia sweep -- ``dA/df`` and ``db/df`` are ``(2 / f) sum_j I_j d/dI_j``, so the slope is
+        ``(2 / f) Re(jm @ I)``, with no second solve and no finite difference across a resonance."""
+        if params is None:
+            params = self.parameters
+        f = self._freqs(freqs)
+        p = torch.as_tensor(np.asarray(params, dtype=np.float64))
+        c = self._coeffs_jacobian(None)(p)[0]
+        I = np.array(self.engine(f.numel()).own_inertia)
+        fr, _, jm = self._inertia_rows(f, c, I, None, with_jc=False)
+        slope = 2.0 / f.cpu().numpy() * np.real(jm.cpu().numpy() @ I)
+        return fr.cpu().numpy(), slope
+
     def getResidualFunction(self, frequencies, reference_fr, func_type: str, scaling_params=None,
-                            axis=None) -> Callable:
+                            axis=None, extra=None) -> Callable:
         """``res(params) -> (r (F,), Jr (F, p), const)`` (numpy): ``getLossFunction``'s loss as least squares,
         ``loss = (r @ r + const) / F`` and ``grad = 2 / F * Jr.T @ r`` (``residual_terms``), for Gauss-Newton /
         Levenberg-Marquardt (``Optimizers.optimize_lm``) and ``parameterCovariance``.  The complex response's losses
@@ -1639,7 +1860,7 @@ class Problem:
         reference_fr = np.asarray(reference_fr)
         assert frequencies.shape[0] == reference_fr.shape[0]
         _, axis = _loss_id(func_type, axis)
-        fn = self._jacobian_function(scaling_params, axis)
+        fn = self._jacobian_function(scaling_params, axis, extra)
         terms = residual_terms if axis is None else complex_residual_terms
         f_dev = self._freqs(frequencies)
 
@@ -1686,7 +1907,7 @@ class Problem:
         return eng.population_sweep(f, C, jac=False)[0].cpu().numpy()
 
     def getPopulationLossFunction(self, frequencies, reference_fr, func_type: str, scaling_params=None,
-                                  with_grad: bool = False, *, distributed: bool = False) -> Callable:
+                                  with_grad: bool = False, *, distributed: bool = False, extra=None) -> Callable:
         """``fn(params (P, n_par)) -> losses (P,)`` -- with ``with_grad`` ``(losses, gradients (P, n_par))`` -- (numpy)
         of ``getLossFunction``'s loss for a whole population in one sweep.  Without ``with_grad`` the sweep is
         forward-only; with it, the per-frequency Jacobian sweep per lane, from which every member's gradient
@@ -1694,6 +1915,8 @@ class Problem:
         (``population_loss_grad``)."""
         if distributed:
             raise NotImplementedError('the population sweep is not distributed: use distributed=False')
+        if extra is not None:
+            raise NotImplementedError('the population sweep has no inertia rows: extra is not supported here')
         frequencies = np.asarray(frequencies, dtype=np.float64)
         reference_fr = np.asarray(reference_fr)
         assert frequencies.shape[0] == reference_fr.shape[0]
@@ -1713,15 +1936,16 @@ class Problem:
         return fn
 
     def parameterCovariance(self, frequencies, reference_fr, func_type: str, params=None, scaling_params=None,
-                            axis=None):
+                            axis=None, extra=None):
         """``(cov (p, p), std (p,))`` of the parameters identified from ``reference_fr``: the Gauss-Newton
         covariance ``sigma^2 (Jr^T Jr)^+`` with ``sigma^2 = (r @ r + const) / (F - p)`` at ``params`` (default: the
         material's; in the units of ``params``, i.e. scaled ones with ``scaling_params``).  A parameter the
         experiment does not determine shows as a large ``std``; a numerically singular ``Jr^T Jr`` warns."""
         if params is None:
-            params = self.parameters if scaling_params is None else \
-                self.parameters / np.asarray(scaling_params, dtype=np.float64)
-        r, Jr, const = self.getResidualFunction(frequencies, reference_fr, func_type, scaling_params, axis)(params)
+            own = self.parameters if extra is None else self.extendedParameters(extra)
+            params = own if scaling_params is None else own / np.asarray(scaling_params, dtype=np.float64)
+        r, Jr, const = self.getResidualFunction(frequencies, reference_fr, func_type, scaling_params, axis,
+                                                extra=extra)(params)
         return covariance_from_residual(r, Jr, const)
 
     def solveInverse(self, *args, **kwargs):

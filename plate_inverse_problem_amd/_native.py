@@ -112,6 +112,11 @@ _PROTOS = {
     "pfr_jacobian_sweep": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P]),
     "pfr_sweep_complex": (C.c_int, [_P, C.c_int32, _P, _DP, C.c_int32, _P, C.c_double, _P, _P, _P, _P, C.c_int32, _P]),
     "pfr_jacobian_sweep_complex": (C.c_int, [_P, C.c_int32, _P, _DP, _P, _P, _P, _P]),
+    "pfr_set_inertia": (C.c_int, [_P, C.c_int32, _P, _DP]),
+    "pfr_inertia_sweep": (C.c_int, [_P, C.c_int32, _P, _DP, _P, _P, _P, _P, _P]),
+    "pfr_symbolic_mass_list": (C.c_int32, [_P, _DP, C.c_int32, C.c_int32, _DP, _I32P, C.c_int64, _I32P, C.c_int64,
+                                           _I32P, C.c_int64, _I32P]),
+    "pfr_solver_mass_list": (C.c_int32, [_P, _I32P]),
     "pfr_field_sweep": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _I32P, _P, _P, _P, _P]),
     "pfr_field_tile_rows": (C.c_int32, []),
     "pfr_field_loss_sweep": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _I32P, _DP, C.c_int32, _P, C.c_double, _P, _P, _P,
@@ -324,6 +329,29 @@ class Symbolic:
             raise NativeError("pfr_symbolic_live: bad arguments (needs a symmetric analysis)")
         return [k for k in range(int(s.shape[1])) if (bits.value >> k) & 1]
 
+    def mass_list(self, mass_nz_j, rhs=None, prune: bool = False) -> tuple:
+        """pfr_symbolic_mass_list: (list, ptr, n_list, entries) -- the list of contraction entries the inertia
+        contraction walks for the table ``mass_nz_j`` (nnz, n_mass), wave by wave and padded with -1 to whole 4-entry
+        batches, each wave's first batch (waves + 1), the count without the padding, and the contraction entries
+        (n_uent, 4) int32 (permuted column, nz of (i, j) or -1, nz of (j, i) or -1, permuted row); ``prune``: over the
+        rows of the trees ``rhs`` loads.  Needs no device."""
+        m, mp = _f64(np.asarray(mass_nz_j, dtype=np.float64).reshape(len(mass_nz_j), -1))
+        rp = None
+        if rhs is not None:
+            r, rp = _f64(rhs)
+        counts = np.zeros(3, dtype=np.int32)
+        args = (self._h, rp, int(bool(prune)), int(m.shape[1]), mp)
+        if lib().pfr_symbolic_mass_list(*args, None, 0, None, 0, None, 0, counts.ctypes.data_as(_I32P)) < 0:
+            raise NativeError("pfr_symbolic_mass_list: bad arguments")
+        ent = np.zeros(4 * int(counts[0]), dtype=np.int32)
+        lst = np.zeros(int(counts[1]), dtype=np.int32)
+        ptr = np.zeros(int(counts[2]) + 1, dtype=np.int32)
+        n = lib().pfr_symbolic_mass_list(*args, lst.ctypes.data_as(_I32P), lst.size, ptr.ctypes.data_as(_I32P), ptr.size,
+                                         ent.ctypes.data_as(_I32P), ent.size, None)
+        if n < 0:
+            raise NativeError("pfr_symbolic_mass_list: bad arguments")
+        return lst, ptr, int(n), ent.reshape(-1, 4)
+
     def __del__(self):
         h = getattr(self, "_h", None)
         if h is not None and _lib is not None:
@@ -456,6 +484,34 @@ class Solver:
         check(lib().pfr_jacobian_sweep_complex(self._h, int(freqs.numel()), _ptr(freqs), ap, _ptr(h), _ptr(jc),
                                                _ptr(flags), self._stream(freqs) if stream is None else stream),
               "pfr_jacobian_sweep_complex")
+
+    def set_inertia(self, mass_nz_j, rhs_weights):
+        """pfr_set_inertia: the mass components ``mass_nz_j`` (nnz, n_mass) real device table, n_mass 1 .. 4, and their
+        load weights d_j (host).  M and mass_sum stay the caller's (``set_operator`` / ``set_rhs``)."""
+        self._keep["mass"] = mass_nz_j
+        w, wp = _f64(rhs_weights)
+        n_mass = int(mass_nz_j.shape[1]) if mass_nz_j.dim() == 2 else 0
+        if w.size != n_mass:
+            raise ValueError(f"set_inertia: {w.size} load weights for {n_mass} components")
+        check(lib().pfr_set_inertia(self._h, n_mass, _ptr(mass_nz_j), wp), "pfr_set_inertia")
+
+    def mass_list(self) -> tuple:
+        """pfr_solver_mass_list: (entries the inertia contraction walks on the view the sweeps run on, the padded
+        length of the device list); (-1, 0) before ``set_inertia``."""
+        padded = C.c_int32(0)
+        n = lib().pfr_solver_mass_list(self._h, C.byref(padded))
+        return int(n), int(padded.value)
+
+    def inertia_sweep(self, freqs, jm, axis=None, resp=None, jc=None, flags=None, stream=None):
+        """pfr_inertia_sweep: the Jacobian sweep (``axis`` None: of fr, ``resp`` real; else of the complex response
+        along ``axis``, ``resp`` complex) with the inertia rows ``jm`` (nfreq, n_mass) complex,
+        omega_q^2 (m_q mu_q^T G_j x_q - d_j t_q), written; ``jc`` (nfreq, n_stiff) and ``resp`` may be None."""
+        ap = None
+        if axis is not None:
+            a, ap = _axis3(axis, "inertia_sweep")
+        check(lib().pfr_inertia_sweep(self._h, int(freqs.numel()), _ptr(freqs), ap, _ptr(resp), _ptr(jc), _ptr(jm),
+                                      _ptr(flags), self._stream(freqs) if stream is None else stream),
+              "pfr_inertia_sweep")
 
     def field_sweep(self, freqs, out, rows=None, fr=None, flags=None, stream=None):
         """pfr_field_sweep: ``out`` (nfreq, n_sel) complex128, frequency-major, receives the solution's rows ``rows``

@@ -72,6 +72,9 @@ struct SolverView {
   uint32_t live = 0;
   int n_live = 0;
   double* d_se_live = nullptr;          // se_live[nz * n_live + i] on the entries of the walk's rows, or NULL
+  // the contraction entries with a non-zero mass component on the walk's rows (update_mass; pfr_set_inertia), padded
+  int32_t *d_mlist = nullptr, *d_mptr = nullptr;   // ... and each wave's batch range of it
+  int n_mlist = 0, len_mlist = 0;
   int post_n = 0;                       // Dirichlet nodes on the view's fronts, with their column entries
   int2* post_dir = nullptr;             // (k_dirichlet_post over them)
   int32_t* post_dptr = nullptr;
@@ -194,6 +197,15 @@ struct pfr_solver : SolverView {
   int4* d_uent = nullptr;
   int n_uent = 0;
   double* d_se = nullptr;               // entry-ordered S_k(i, j) (pfr_set_stiffness)
+  // inertia rows (pfr_set_inertia): the registered mass components G_j and their load weights d_j, the entry-ordered
+  // copy G_j(i, j) padded to MASS_NM columns, per matrix entry whether some component is non-zero there, and the
+  // host copy of the contraction entries the views' lists are compacted from
+  const double* mass = nullptr;
+  int n_mass = 0;
+  pfr::MassWeights mass_d{};
+  double* d_me = nullptr;
+  std::vector<char> mass_nz;
+  std::vector<pfr::I4> h_uent;
   int n_kdir = 0;
   double2 *partial = nullptr, *tq = nullptr;
   double *freqs = nullptr, *loss_terms = nullptr;
@@ -759,6 +771,30 @@ int update_live(pfr_solver* s, SolverView& v) {
   return PFR_OK;
 }
 
+// The inertia contraction's entry list of a view's walk (plan.hpp, mass_entries: decided by value from the registered
+// components, once per view and pfr_set_inertia)
+int update_mass(pfr_solver* s, SolverView& v) {
+  if (v.d_mptr) (void)hipDeviceSynchronize();   // launches that read the list
+  for (int32_t** p : {&v.d_mlist, &v.d_mptr}) {
+    if (!*p) continue;
+    s->owned.erase(std::remove(s->owned.begin(), s->owned.end(), (void*)*p), s->owned.end());
+    v.mine.erase(std::remove(v.mine.begin(), v.mine.end(), (void*)*p), v.mine.end());
+    (void)hipFree(*p);
+    *p = nullptr;
+  }
+  v.n_mlist = v.len_mlist = 0;
+  if (!s->mass) return PFR_OK;
+  std::vector<char> rows;
+  if (&v != s) rows = pfr::front_rows(s->S, v.active);
+  const pfr::MassList L = pfr::mass_entries(s->h_uent, s->n_uent, s->n, &v != s ? &rows : nullptr, s->mass_nz);
+  v.n_mlist = L.n_list;
+  v.len_mlist = (int)L.list.size();
+  int rc;
+  if ((rc = s->up_rec(&v.d_mlist, L.list, (int32_t)-1)) || (rc = s->up(&v.d_mptr, L.ptr))) return rc;
+  if (&v != s) v.mine.insert(v.mine.end(), {(void*)v.d_mlist, (void*)v.d_mptr});
+  return PFR_OK;
+}
+
 // A view of the fronts in `mask` (whole trees): its plan and schedule, the Dirichlet nodes on its fronts, and the
 // solver's current reaches restricted to it (keep0 = false: no forward reach -- the complement carries no load)
 int make_view(pfr_solver* s, const std::vector<char>& mask, bool keep0, SolverView** out) {
@@ -824,7 +860,8 @@ int update_prune(pfr_solver* s) {
   if (!s->unl_rows.empty()) s->unl_rows.resize(k + 1);
   s->unl_dirty = true;   // the rows of the unloaded trees in X / XA: exact zeros from the first pruned sweep on
   if (int rc = make_view(s, mask, true, &s->act)) return rc;
-  return update_live(s, *s->act);
+  if (int rc = update_live(s, *s->act)) return rc;
+  return update_mass(s, *s->act);
 }
 
 }  // namespace
@@ -1020,6 +1057,7 @@ int pfr_solver_create(const pfr_symbolic* sym, const int32_t* colptr, const int3
       (rc = s->up_rec(&s->d_uent, pl.uent, n4)))
     return bail(rc);
   s->n_uent = pl.n_uent;
+  s->h_uent = pl.uent;
   s->P = DevPattern{d_fronts, idx, relpos, rowf, ap, ac, an, ep, es, pm, pr, pc, S.n};
   {
     const int nf = (int)S.fronts.size();
@@ -1208,6 +1246,41 @@ int32_t pfr_solver_live(const pfr_solver* s, uint32_t* live, int32_t* compact) {
   if (live) *live = v.live;
   if (compact) *compact = v.d_se_live != nullptr;
   return v.n_live;
+}
+
+int32_t pfr_symbolic_mass_list(const pfr_symbolic* sym, const double* rhs, int32_t prune, int32_t n_mass,
+                               const double* mass_host, int32_t* list, int64_t cap, int32_t* ptr, int64_t ptr_cap,
+                               int32_t* entries, int64_t entries_cap, int32_t* counts) {
+  if (!sym || !mass_host || n_mass < 1 || n_mass > pfr::MASS_NM || (prune && (!rhs || !sym->S.symmetric))) return -1;
+  const Symbolic& S = sym->S;
+  pfr::Plan pl;
+  std::string perr;
+  if (pfr::build_plan(S, pfr::knobs_from_env(64).blk_min, pl, perr)) return -1;
+  std::vector<char> rows;
+  if (prune) {
+    std::vector<double> rp(S.n);
+    for (int p = 0; p < S.n; ++p) rp[p] = rhs[S.perm[p]];
+    rows = pfr::front_rows(S, pfr::loaded_fronts(S, rp.data()));
+  }
+  const pfr::MassList L =
+      pfr::mass_entries(pl.uent, pl.n_uent, S.n, prune ? &rows : nullptr, pfr::mass_on(mass_host, S.nnz, n_mass));
+  const std::vector<int32_t>& l = L.list;
+  if (list) std::copy(l.begin(), l.begin() + std::min<int64_t>(cap, (int64_t)l.size()), list);
+  if (ptr) std::copy(L.ptr.begin(), L.ptr.begin() + std::min<int64_t>(ptr_cap, (int64_t)L.ptr.size()), ptr);
+  if (entries)
+    for (int64_t e = 0; e < pl.n_uent && 4 * e + 3 < entries_cap; ++e) {
+      const pfr::I4& u = pl.uent[e];
+      entries[4 * e] = u.x, entries[4 * e + 1] = u.y, entries[4 * e + 2] = u.z, entries[4 * e + 3] = u.w;
+    }
+  if (counts) counts[0] = pl.n_uent, counts[1] = (int32_t)l.size(), counts[2] = (int32_t)L.ptr.size() - 1;
+  return (list && cap < (int64_t)l.size()) || (ptr && ptr_cap < (int64_t)L.ptr.size()) ? -1 : L.n_list;
+}
+
+int32_t pfr_solver_mass_list(const pfr_solver* s, int32_t* padded) {
+  if (!s) return -1;
+  const SolverView& v = sweeps_pruned(s) ? *s->act : static_cast<const SolverView&>(*s);
+  if (padded) *padded = s->mass ? v.len_mlist : 0;
+  return s->mass ? v.n_mlist : -1;
 }
 
 int pfr_set_timing(pfr_solver* s, int32_t enable) {
@@ -1409,6 +1482,32 @@ int pfr_set_stiffness(pfr_solver* s, int32_t n_stiff, const double* stiff_dev, c
   return PFR_OK;
 }
 
+int pfr_set_inertia(pfr_solver* s, int32_t n_mass, const double* mass_dev, const double* w) {
+  if (!s || n_mass < 1 || n_mass > pfr::MASS_NM || !mass_dev || !w)
+    return fail(PFR_ERR_ARG, "bad inertia arguments (n_mass must be 1 .. 4)");
+  ++s->gen;
+  HIP_TRY(hipSetDevice(s->device));
+  if (!s->d_me) {
+    int rc = s->alloc(&s->d_me, (int64_t)pfr::MASS_NM * (s->n_uent + 4));
+    if (rc) return rc;
+  }
+  // the entry-ordered copy the contraction reads (taken now: a later change of the registered buffer needs another
+  // pfr_set_inertia) and, from the table's values, the entries the views' lists keep
+  (void)hipDeviceSynchronize();   // launches that read the copy
+  pfr::launch_gather_mass(s->d_uent, s->n_uent + 4, mass_dev, n_mass, s->d_me, nullptr);
+  std::vector<double> host((size_t)s->nnz * n_mass);
+  HIP_TRY(hipMemcpy(host.data(), mass_dev, host.size() * 8, hipMemcpyDeviceToHost));
+  s->mass_nz = pfr::mass_on(host.data(), s->nnz, n_mass);
+  s->mass = mass_dev;
+  s->n_mass = n_mass;
+  s->mass_d = pfr::MassWeights{};
+  for (int j = 0; j < n_mass; ++j) s->mass_d.d[j] = w[j];
+  if (int rc = update_mass(s, *s)) return rc;
+  if (s->act)
+    if (int rc = update_mass(s, *s->act)) return rc;
+  return PFR_OK;
+}
+
 int pfr_combine(pfr_solver* s, const double* coef, double* K_out, void* stream) {
   if (!s || !coef || !K_out) return fail(PFR_ERR_ARG, "null argument");
   if (!s->stiff) return fail(PFR_ERR_STATE, "pfr_set_stiffness not called");
@@ -1529,6 +1628,8 @@ struct Response {
 // jc != NULL (the Jacobian forms; loss_type = pfr::LOSS_UNIT, scale 1, no ref / loss / w): the reverse sweep of a unit
 // cotangent per frequency whose contraction stays per frequency -- the walk's kpart (or k_contract_q's, where the walk
 // has not formed it) finished by k_jac_finish into the rows of jc instead of k_reduce_q / k_contract_eg + k_reduce into w.
+// jm != NULL (pfr_inertia_sweep): that sweep with the inertia rows too -- after k_jac_finish (skipped with its contraction
+// when jc == NULL) k_contract_mass / k_inertia_finish contract the same x and mu with the mass components into jm.
 // pop.member != NULL (pfr_population_sweep): lane group g belongs to pop.member[g] and reads the operator popK +
 // pop.member[g] * pop.nnz (chunk_op).  resp.cpx (the complex sweeps): response holds complex H, loss_type is a PFR_LOSS_C*
 // id, pfr::LOSS_UNIT or PFR_LOSS_NONE, and the functional kernels run in their CPX forms (seed kept in s->h0); every
@@ -1554,6 +1655,7 @@ struct SweepSpec {
   double* response = nullptr;           // fr per frequency, or the complex H (resp.cpx)
   double *loss = nullptr, *w = nullptr;
   double2* jc = nullptr;
+  double2* jm = nullptr;                // the inertia rows (pfr_inertia_sweep), beside or instead of jc
   int32_t* flags = nullptr;
   bool fresh = false;                   // the caller's outputs initialised by the first chunk (pfr_sweep_fresh)
   const double2* popK = nullptr;
@@ -1592,7 +1694,7 @@ SweepPasses sweep_passes(const pfr_solver* s, const SweepSpec& sp) {
   SweepPasses p;
   const int mode = s->check_mode & sp.check_mask;
   p.reverse = sp.loss_type != PFR_LOSS_NONE;
-  p.jac = sp.jc != nullptr;
+  p.jac = sp.jc != nullptr || sp.jm != nullptr;
   p.field = sp.field.out != nullptr;
   p.floss = sp.floss.ref != nullptr;
   p.functional = p.floss || !p.field || sp.response != nullptr;
@@ -1783,7 +1885,7 @@ int phase_finish(pfr_solver* s, SolverView& v, const pfr::ChunkOp& op, const Swe
   const double2* msc = ps.correct ? s->mscale : nullptr;
   if (ps.jac) {
     // the walk's kpart is final here (the refined groups redone above); without the walk k_contract_q forms it
-    if (!ps.cwalk) pfr::launch_contract_q(s->d_uent, s->n_uent, s->d_se, s->n_stiff, s->XA, s->X, s->n, Fc, s->kpart, st);
+    if (!ps.cwalk && sp.jc) pfr::launch_contract_q(s->d_uent, s->n_uent, s->d_se, s->n_stiff, s->XA, s->X, s->n, Fc, s->kpart, st);
   } else if (ps.cwalk)
     pfr::launch_reduce_q(s->kpart, pfr::residual_parts(s->n), s->n_stiff, msc, nv, Fc, s->partial, st);
   else if (ps.reverse)
@@ -1794,10 +1896,14 @@ int phase_finish(pfr_solver* s, SolverView& v, const pfr::ChunkOp& op, const Swe
     run_walk(s, v, op, Walk::checked(Walk::ADJOINT, pfr::RHS_VECTOR, rhs_vector(s->G), s->XA, q0), nv, st);
   if (ps.reverse) {
     if (!ps.scorr) pfr::launch_rhs_dot(s->rhs_sup, s->rhs_val, s->n_rhs_sup, s->XA, Fc, s->tq, st, msc);
-    if (ps.jac)
+    if (ps.jac && sp.jc)
       pfr::launch_jac_finish(s->kpart, ps.cwalk ? pfr::residual_parts(s->n) : pfr::contract_q_parts(s->n, s->n_uent),
                              s->n_stiff, msc, s->tq, s->e, nv, Fc, sp.jc + q0 * s->n_stiff, st);
-    else
+    // the inertia rows from the same x, mu, m_q and t_q; their partials take kpart's place once it has been read
+    if (ps.jac && sp.jm)
+      pfr::launch_inertia_rows(v.d_mlist, v.d_mptr, s->d_uent, s->n_uent, s->d_me, s->n_mass, s->XA, s->X, s->n, Fc,
+                               s->kpart, msc, s->tq, s->freqs, s->mass_d, nv, sp.jm + q0 * s->n_mass, st);
+    if (!ps.jac)
       pfr::launch_reduce(s->partial, ps.cwalk ? (int)(Fc / 64) : pfr::contract_eg_parts(s->n_uent), s->n_stiff, s->tq,
                          s->e, s->loss_terms, nv, Fc, reinterpret_cast<double2*>(sp.w), sp.loss, st);
   }
@@ -2007,6 +2113,24 @@ int pfr_jacobian_sweep_complex(pfr_solver* s, int32_t nfreq, const double* freqs
   if (int rc = complex_sweep_begin(s, nfreq, freqs_dev, axis, true, &resp)) return rc;
   const SweepSpec sp{.nfreq = nfreq, .freqs = freqs_dev, .loss_type = pfr::LOSS_UNIT, .response = h_dev,
                      .jc = reinterpret_cast<double2*>(jc_dev), .flags = flags_dev, .resp = resp};
+  return sweep_launches(s, sp, (hipStream_t)stream);
+}
+
+int pfr_inertia_sweep(pfr_solver* s, int32_t nfreq, const double* freqs_dev, const double* axis, double* resp_dev,
+                      double* jc_dev, double* jm_dev, int32_t* flags_dev, void* stream) {
+  if (!s || nfreq <= 0 || !freqs_dev || !jm_dev) return fail(PFR_ERR_ARG, "bad inertia sweep arguments");
+  Response resp;
+  if (axis) {
+    if (int rc = complex_sweep_begin(s, nfreq, freqs_dev, axis, jc_dev != nullptr, &resp)) return rc;
+  } else if (int rc = sweep_ready(s, jc_dev ? "jacobian rows need pfr_set_stiffness" : nullptr)) {
+    return rc;
+  }
+  if (!s->mass) return fail(PFR_ERR_STATE, "inertia sweep needs pfr_set_inertia");
+  never_captured(s);
+  HIP_TRY(hipSetDevice(s->device));
+  const SweepSpec sp{.nfreq = nfreq, .freqs = freqs_dev, .loss_type = pfr::LOSS_UNIT, .response = resp_dev,
+                     .jc = reinterpret_cast<double2*>(jc_dev), .jm = reinterpret_cast<double2*>(jm_dev),
+                     .flags = flags_dev, .resp = resp};
   return sweep_launches(s, sp, (hipStream_t)stream);
 }
 

@@ -77,6 +77,30 @@ std::string build_views(const pfr::Symbolic& S, int bm, int32_t load_row, const 
   for (int side = 0; side < 2; ++side)
     if (pfr::live_stiffness(S, &V.mask[side], bits) != (any[side] ? 1u << side : 0u)) return "live stiffness list of a view";
   if (pfr::live_stiffness(S, nullptr, bits) != ((any[0] ? 1u : 0u) | (any[1] ? 2u : 0u))) return "live stiffness list";
+  // the inertia contraction's entry lists (pfr::mass_entries) for the same table as mass components: the two views'
+  // lists partition the full one, every entry on the wave that owns it there, each run padded to whole batches
+  const pfr::Plan& P0 = V.P[0];
+  const std::vector<char> on = pfr::mass_on(stiff.data(), S.nnz, 3);
+  const pfr::MassList full = pfr::mass_entries(P0.uent, P0.n_uent, S.n, nullptr, on);
+  if (full.n_list != (int)S.nnz || full.list.size() % pfr::MASS_U) return "mass list";
+  std::vector<int32_t> wave_of(P0.n_uent, -1);
+  for (size_t w = 0; w + 1 < full.ptr.size(); ++w)
+    for (int64_t i = (int64_t)full.ptr[w] * pfr::MASS_U; i < (int64_t)full.ptr[w + 1] * pfr::MASS_U; ++i)
+      if (full.list[i] >= 0) wave_of[full.list[i]] = (int32_t)w;
+  int listed = 0;
+  for (int side = 0; side < 2; ++side) {
+    const std::vector<char> rows = pfr::front_rows(S, V.mask[side]);
+    const pfr::MassList L = pfr::mass_entries(P0.uent, P0.n_uent, S.n, &rows, on);
+    if (L.ptr.size() != full.ptr.size() || (int64_t)L.ptr.back() * pfr::MASS_U != (int64_t)L.list.size()) return "mass list of a view";
+    for (size_t w = 0; w + 1 < L.ptr.size(); ++w)
+      for (int64_t i = (int64_t)L.ptr[w] * pfr::MASS_U; i < (int64_t)L.ptr[w + 1] * pfr::MASS_U; ++i) {
+        const int32_t e = L.list[i];
+        if (e < 0) continue;
+        if (e >= P0.n_uent || wave_of[e] != (int32_t)w || !rows[P0.uent[e].w]) return "mass list entry of a view";
+        ++listed;
+      }
+    if (listed != (side == 0 ? L.n_list : full.n_list)) return "mass list count of a view";
+  }
   return "";
 }
 std::string check_views(const pfr::Symbolic& S, const Views& V, int64_t Fc, const pfr::Knobs& k) {

@@ -34,6 +34,11 @@ struct CoefPack {
   double im[COEF_MAX];
 };
 
+// The load weights d_j of the mass components (pfr_set_inertia; k_inertia_finish)
+struct MassWeights {
+  double d[4];
+};
+
 // Population sweep (pfr_population_sweep): the 64-lane group g of the chunk belongs to member[g]; its operator is
 // K + member[g] * nnz and its rhs scale beta[member[g]].  Read only by the kernels' POP instantiations.
 struct PopArgs {

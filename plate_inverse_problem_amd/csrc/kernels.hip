@@ -3628,6 +3628,104 @@ __global__ __launch_bounds__(1024) void k_jac_finish(const cplx* __restrict__ kp
   for (int i = threadIdx.x; i < nrows * NS; i += blockDim.x) out[i] = tile[(i / NS) * (NS + 1) + i % NS];
 }
 
+// ------------------------------------------------------------------ inertia rows (pfr_inertia_sweep)
+// me[NM e + j] = G_j(i, j) of contraction entry e (zeros where the entry is absent and in the columns j >= nm):
+// the entry-ordered copy of the mass components, taken once per pfr_set_inertia.
+template <int NM>
+__global__ void k_gather_mass(const int4* __restrict__ ent, int nent, const double* __restrict__ mass, int nm,
+                              double* __restrict__ me) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= nent) return;
+  const int4 en = ent[e];
+  const bool ij = en.x >= 0 && en.y >= 0;
+#pragma unroll
+  for (int j = 0; j < NM; ++j) me[(int64_t)e * NM + j] = (ij && j < nm) ? mass[(int64_t)en.y * nm + j] : 0.0;
+}
+
+// Per-frequency contraction with the mass components, k_contract_q's shape over a compacted entry list:
+//   mpart[(b NM + j) Fc + q] = sum_{listed e of workgroup b} G_j(e) Lam_i(q) X_j(q)
+// list: positions in ent / me of the entries on which some component is non-zero (on the view's rows), in ent's
+// order, wave by wave: wave 4 b + w of workgroup b walks the batches ptr[4 b + w] .. ptr[4 b + w + 1) of CQ_U
+// positions (its run padded with -1; plan.hpp, mass_entries: the wave of an entry does not depend on the view).
+// Grid (parts, Fc / 64), 4 waves.  A batch's CQ_U positions are one wave-uniform load, its 2 CQ_U 1 KiB runs of Lam
+// and X are issued before the products, the entry record and its NM values are wave-uniform loads; then the four
+// waves are summed in LDS in wave order.  A padding position (-1) loads entry 0's rows and is skipped.
+template <int NM>
+__global__ __launch_bounds__(256) void k_contract_mass(const int* __restrict__ list, const int* __restrict__ ptr,
+                                                       const int4* __restrict__ ent, const double* __restrict__ me,
+                                                       const cplx* __restrict__ Lam, const cplx* __restrict__ X,
+                                                       int64_t Fc, cplx* __restrict__ mpart) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t q = (int64_t)blockIdx.y * 64 + lane;
+  const int wv = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + w);
+  const int b1 = ptr[wv + 1];
+  cplx ms[NM];
+#pragma unroll
+  for (int j = 0; j < NM; ++j) ms[j] = make_double2(0, 0);
+  for (int b = ptr[wv]; b < b1; ++b) {
+    cplx li[CQ_U], xj[CQ_U];
+    int ee[CQ_U];
+#pragma unroll
+    for (int u = 0; u < CQ_U; ++u) {
+      ee[u] = list[(int64_t)b * CQ_U + u];
+      const int4 en = ent[max(ee[u], 0)];
+      li[u] = Lam[(int64_t)max(en.w, 0) * Fc + q];
+      xj[u] = X[(int64_t)max(en.x, 0) * Fc + q];
+    }
+#pragma unroll
+    for (int u = 0; u < CQ_U; ++u) {
+      if (ee[u] < 0) continue;               // wave-uniform
+      const cplx lx = cmul(li[u], xj[u]);
+      const double* mk = me + (int64_t)ee[u] * NM;
+#pragma unroll
+      for (int j = 0; j < NM; ++j) {
+        ms[j].x = fma(mk[j], lx.x, ms[j].x);
+        ms[j].y = fma(mk[j], lx.y, ms[j].y);
+      }
+    }
+  }
+  __shared__ cplx sms[4][64];
+#pragma unroll
+  for (int j = 0; j < NM; ++j) {
+    __syncthreads();
+    sms[w][lane] = ms[j];
+    __syncthreads();
+    if (w == 0)
+      mpart[((int64_t)blockIdx.x * NM + j) * Fc + q] =
+          cadd(cadd(sms[0][lane], sms[1][lane]), cadd(sms[2][lane], sms[3][lane]));
+  }
+}
+
+// The inertia rows' finisher, per 64-frequency tile:
+//   jm[(q0 + q) nm + j] = omega_q^2 ( m_q sum_b mpart[b][j][q] - d_j t_q )      (b ascending: a fixed order)
+// with m_q and t_q as k_jac_finish takes them and omega_q^2 as the assembly forms it from freqs[q].  Wave j sums
+// component j (lane = frequency: contiguous 1 KiB runs of mpart); the tile is staged in LDS (rows padded by one
+// entry) and the rows q < nvalid are stored as one contiguous run of nrows x nm entries.
+template <int NM>
+__global__ __launch_bounds__(64 * NM) void k_inertia_finish(const cplx* __restrict__ mpart, int nparts, int nm,
+                                                            const cplx* __restrict__ msc, const cplx* __restrict__ t_q,
+                                                            const double* __restrict__ freqs, MassWeights d, int nvalid,
+                                                            int64_t Fc, cplx* __restrict__ jm) {
+  static_assert(NM <= 4, "MassWeights");
+  __shared__ cplx tile[64 * (NM + 1)];
+  const int lane = threadIdx.x & 63, j = threadIdx.x >> 6;
+  const int64_t q = (int64_t)blockIdx.x * 64 + lane;
+  const cplx m = msc ? msc[q] : make_double2(1.0, 0.0);
+  const cplx t = t_q[q];
+  const double om = 6.283185307179586 * freqs[q];
+  const double om2 = om * om;
+  cplx s = make_double2(0, 0);
+#pragma unroll 8
+  for (int b = 0; b < nparts; ++b) s = cadd(s, mpart[((int64_t)b * NM + j) * Fc + q]);
+  const cplx msum = cmul(m, s);
+  const double dj = j == 0 ? d.d[0] : j == 1 ? d.d[1] : j == 2 ? d.d[2] : d.d[3];
+  tile[lane * (NM + 1) + j] = make_double2(om2 * fma(-dj, t.x, msum.x), om2 * fma(-dj, t.y, msum.y));
+  __syncthreads();
+  const int nrows = min(64, nvalid - (int)blockIdx.x * 64);
+  cplx* __restrict__ out = jm + (int64_t)blockIdx.x * 64 * nm;
+  for (int i = threadIdx.x; i < nrows * nm; i += blockDim.x) out[i] = tile[(i / nm) * (NM + 1) + i % nm];
+}
+
 __global__ void k_reduce(const cplx* __restrict__ partial, int nparts, int n_stiff, const cplx* __restrict__ t_q,
                          CoefPack e, const double* __restrict__ loss_terms, int nvalid, int64_t Fc,
                          cplx* __restrict__ w_out, double* __restrict__ loss_out) {
@@ -4287,6 +4385,23 @@ void launch_jac_finish(const double2* kpart, int nparts, int n_stiff, const doub
   with_int<12, 18>(n_stiff, [&](auto ns) {
     LAUNCH(k_jac_finish<CV(ns)>, dim3((unsigned)(Fc / 64)), dim3(1024), st, kpart, nparts, msc, t_q, e, nvalid, Fc, jc);
   });
+}
+
+static_assert(CQ_U == MASS_U, "k_contract_mass reads the list in the batches plan.cpp pads it to");
+
+void launch_gather_mass(const int4* ent, int nent, const double* mass, int n_mass, double* me, hipStream_t st) {
+  LAUNCH(k_gather_mass<MASS_NM>, dim3((nent + 255) / 256), dim3(256), st, ent, nent, mass, n_mass, me);
+}
+
+void launch_inertia_rows(const int* list, const int* ptr, const int4* ent, int nent, const double* me, int n_mass,
+                         const double2* Lam, const double2* X, int n, int64_t Fc, double2* mpart, const double2* msc,
+                         const double2* t_q, const double* freqs, const MassWeights& d, int nvalid, double2* jm,
+                         hipStream_t st) {
+  const int parts = contract_mass_parts(n, nent);
+  LAUNCH(k_contract_mass<MASS_NM>, dim3(parts, (unsigned)(Fc / 64)), dim3(256), st, list, ptr, ent, me, Lam, X, Fc,
+         mpart);
+  LAUNCH(k_inertia_finish<MASS_NM>, dim3((unsigned)(Fc / 64)), dim3(64 * MASS_NM), st, mpart, parts, n_mass, msc, t_q,
+         freqs, d, nvalid, Fc, jm);
 }
 
 void launch_reduce(const double2* partial, int nparts, int n_stiff, const double2* t_q, const CoefPack& e,

@@ -123,6 +123,17 @@ void launch_contract_q(const int4* ent, int nent, const double* se, int n_stiff,
                        int n, int64_t Fc, double2* kpart, hipStream_t st);
 void launch_jac_finish(const double2* kpart, int nparts, int n_stiff, const double2* msc, const double2* t_q,
                        const CoefPack& e, int nvalid, int64_t Fc, double2* jc, hipStream_t st);
+// Inertia sweep.  launch_gather_mass: me[e MASS_NM + j] = mass[nz(e) n_mass + j], the entry-ordered copy of the n_mass
+// mass components (columns j >= n_mass zero) over ent[0 .. nent).  launch_inertia_rows: k_contract_mass over a view's
+// list and per-wave batch ranges (plan.hpp, mass_entries) into mpart[(b MASS_NM + j) Fc + q] over
+// contract_mass_parts(n, nent) workgroups b, then k_inertia_finish:
+//   jm[q n_mass + j] = omega_q^2 (msc[q] sum_b mpart[b][j][q] - d_j t_q[q])   for the chunk's rows q < nvalid
+// (jm: the chunk's first row; msc NULL: 1; omega_q = 2 pi freqs[q]; written, not accumulated)
+void launch_gather_mass(const int4* ent, int nent, const double* mass, int n_mass, double* me, hipStream_t st);
+void launch_inertia_rows(const int* list, const int* ptr, const int4* ent, int nent, const double* me, int n_mass,
+                         const double2* Lam, const double2* X, int n, int64_t Fc, double2* mpart, const double2* msc,
+                         const double2* t_q, const double* freqs, const MassWeights& d, int nvalid, double2* jm,
+                         hipStream_t st);
 // symmetric mode: forward right-hand-side corrections (RHS_OPERATOR: operator rhs -> Bc; RHS_VECTOR: G in
 // place) and the adjoint's Dirichlet rows (X in place); pop (population sweep): K and the rhs scale of the
 // group's member

@@ -476,6 +476,43 @@ uint32_t live_stiffness(const Symbolic& S, const std::vector<char>* mask, const 
   return live;
 }
 
+std::vector<char> mass_on(const double* mass, int64_t nnz, int n_mass) {
+  std::vector<char> on(nnz, 0);
+  for (int64_t nz = 0; nz < nnz; ++nz)
+    for (int j = 0; j < n_mass; ++j)
+      if (mass[nz * n_mass + j] != 0.0) on[nz] = 1;
+  return on;
+}
+
+std::vector<char> front_rows(const Symbolic& S, const std::vector<char>& mask) {
+  std::vector<char> row_on(S.n, 0);
+  for (size_t t = 0; t < S.fronts.size() && t < mask.size(); ++t)
+    if (mask[t])
+      for (int a = 0; a < S.fronts[t].ns; ++a) row_on[S.fronts[t].col0 + a] = 1;
+  return row_on;
+}
+
+MassList mass_entries(const std::vector<I4>& uent, int n_uent, int n, const std::vector<char>* row_on,
+                      const std::vector<char>& on) {
+  MassList L;
+  n_uent = std::min<int64_t>(n_uent, (int64_t)uent.size());
+  const int waves = 4 * contract_mass_parts(n, n_uent), seg = mass_segment(n, n_uent);
+  L.ptr.assign(1, 0);
+  for (int w = 0; w < waves; ++w) {
+    for (int64_t e = (int64_t)w * seg; e < std::min<int64_t>((int64_t)(w + 1) * seg, n_uent); ++e) {
+      const I4& u = uent[e];
+      if (u.x < 0 || u.y < 0 || u.y >= (int64_t)on.size() || u.w < 0) continue;
+      if (row_on && (u.w >= (int64_t)row_on->size() || !(*row_on)[u.w])) continue;
+      if (!on[u.y]) continue;
+      L.list.push_back((int32_t)e);
+      ++L.n_list;
+    }
+    while (L.list.size() % MASS_U) L.list.push_back(-1);
+    L.ptr.push_back((int32_t)(L.list.size() / MASS_U));
+  }
+  return L;
+}
+
 std::vector<int32_t> rows_in(const Symbolic& S, const std::vector<char>& mask, const std::vector<int32_t>& prows) {
   std::vector<char> row_on(S.n, 0);
   for (size_t t = 0; t < S.fronts.size(); ++t)
@@ -723,6 +760,9 @@ std::string check_plan(const Symbolic& S, const Plan& P, int64_t Fc) {
   if ((int64_t)residual_parts(S.n) * Fc > W.cpart) return "k_residual partials";                  // cpart[bx Fc + q]
   if ((int64_t)residual_parts(S.n) * 18 * Fc > W.kpart) return "k_residual contraction partials"; // kpart[(bx 18 + k) Fc + q]
   if ((int64_t)contract_q_parts(S.n, P.n_uent) * 18 * Fc > W.kpart) return "k_contract_q contraction partials";
+  // mpart[(bx MASS_NM + j) Fc + q] reuses kpart once k_jac_finish has read it; every entry has its wave
+  if ((int64_t)4 * contract_mass_parts(S.n, P.n_uent) * mass_segment(S.n, P.n_uent) < P.n_uent) return "k_contract_mass segments";
+  if ((int64_t)contract_mass_parts(S.n, P.n_uent) * MASS_NM * Fc > W.kpart) return "k_contract_mass inertia partials";
   {
     const int64_t partial = (int64_t)std::max<int64_t>(contract_eg_parts(P.n_uent), Fc / 64) * 18;   // api.cpp's size
     if ((int64_t)contract_eg_parts(P.n_uent) * 18 > partial || (Fc / 64) * 18 > partial) return "gradient partials";

@@ -70,6 +70,13 @@ inline int contract_eg_parts(int nent) { return ((nent + CEG_EW - 1) / CEG_EW + 
 inline int contract_q_parts(int n, int nent) {
   return (int)std::max<int64_t>(1, std::min<int64_t>(residual_parts(n), ((int64_t)nent + 63) / 64));
 }
+// k_contract_mass: MASS_NM component columns (fewer registered: zero columns), MASS_U list entries per batch; grid.x
+// from the contraction entries (not from a view's list): at least 16 entries per wave, never more workgroups than
+// k_residual's (mpart lives in kpart)
+constexpr int MASS_NM = 4, MASS_U = 4;
+inline int contract_mass_parts(int n, int nlist) {
+  return (int)std::max<int64_t>(1, std::min<int64_t>(residual_parts(n), ((int64_t)nlist + 63) / 64));
+}
 // dynamic LDS of k_factor_sym_lds for a level whose largest pivot block is maxns (triangle + 8 W columns)
 inline int64_t fac_lds_bytes(int maxns) { return ((int64_t)maxns * (maxns + 1) / 2 + (int64_t)maxns * 8) * 16; }
 // k_lsolve_level_z's NAR form: the level's largest pivot block's values in dynamic LDS (ns x 64 x 16 B), beside
@@ -173,6 +180,27 @@ std::vector<char> loaded_fronts(const Symbolic& S, const double* rhs_perm);
 // list), every row for mask == NULL.  A matrix outside the set holds exact zeros on every entry the walk multiplies.
 std::vector<uint32_t> stiffness_bits(const double* stiff, int64_t nnz, int n_stiff);
 uint32_t live_stiffness(const Symbolic& S, const std::vector<char>* mask, const std::vector<uint32_t>& bits);
+// The entries the inertia contraction walks (k_contract_mass), by value: the positions e of the
+// contraction entries uent[0 .. n_uent) -- in that order -- with an entry (i, j) of A (x, y >= 0) on which some mass
+// component is non-zero (on[uent[e].y] != 0; mass_on gives `on` from the (nnz, n_mass) table) and whose row uent[e].w
+// is on in row_on (per permuted row; front_rows: the pivot rows of the fronts in a view's mask; NULL: every row).
+// Wave w of the launch's 4 contract_mass_parts(n, n_uent) waves owns the entries [w seg, (w + 1) seg), seg =
+// mass_segment(n, n_uent) -- whatever the list keeps of them, so that an entry is accumulated by the same wave in the
+// same order on every view and a view's rows match the full walk's bit for bit (what it drops adds exact zeros there).
+// list: the kept positions wave by wave, each wave's run padded with -1 to whole MASS_U-entry batches (a wave reads a
+// batch at once); ptr (waves + 1): each run's first batch; n_list: the kept positions.
+struct MassList {
+  std::vector<int32_t> list, ptr;
+  int n_list = 0;
+};
+inline int mass_segment(int n, int n_uent) {
+  const int64_t waves = 4 * (int64_t)contract_mass_parts(n, n_uent);
+  return (int)std::max<int64_t>(MASS_U, ((n_uent + waves - 1) / waves + MASS_U - 1) / MASS_U * MASS_U);
+}
+std::vector<char> mass_on(const double* mass, int64_t nnz, int n_mass);
+std::vector<char> front_rows(const Symbolic& S, const std::vector<char>& mask);
+MassList mass_entries(const std::vector<I4>& uent, int n_uent, int n, const std::vector<char>* row_on,
+                      const std::vector<char>& on);
 // rows of `prows` on fronts of the mask (a reach restricted to a view)
 std::vector<int32_t> rows_in(const Symbolic& S, const std::vector<char>& mask, const std::vector<int32_t>& prows);
 

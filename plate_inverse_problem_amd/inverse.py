@@ -10,6 +10,8 @@ evaluation, every rank runs the identical optimiser).  Extra optimizers:
 Full-field data: a ``FIELD_MSE`` / ``FIELD_RMSE`` / ``FIELD_MAC`` loss type with ``ref_field=(freqs, field)``,
 ``field_dofs`` and ``field_weights`` fits ``Problem.getFieldLossFunction`` with the gradient optimisers and the
 non-vectorised ``de`` / ``shgo``.
+Nuisance parameters: ``extra=('rho', 'h', 'acc_mass')`` (any of them) extends the vector to ``[material params, extra
+values]`` -- ``arg0`` spans all of it -- for ``lm`` and the gradient optimisers (``Problem.getFRJacobianFunction``).
 """
 from __future__ import annotations
 
@@ -37,8 +39,18 @@ def solve_inverse(prob, arg0, loss_type: str, optimizer: str, compression=(False
                   ref_fr=None, use_rel: bool = False, use_scaling: bool = False, use_constraints: bool = False,
                   report: bool = True, log: bool = True, case_name: str = '', uid: str = None,
                   extra_info: str = '', log_dir: str = None, distributed: bool = False, ref_field=None,
-                  field_dofs=None, field_weights=None, **opt_kwargs):
+                  field_dofs=None, field_weights=None, extra=None, **opt_kwargs):
     field = loss_type in _native.FIELD_LOSS_IDS
+    if extra is not None:
+        no = {'the field-loss sweep has no inertia rows': field,
+              'the trust region needs the Hessian sweep, which has no inertia rows': optimizer in ('trust_region', 'tr'),
+              'the population sweep has no inertia rows': bool(opt_kwargs.get('vectorized', False)),
+              'the inertia sweep is not distributed': distributed}
+        for why, hit in no.items():
+            if hit:
+                raise NotImplementedError(f'solveInverse with extra={extra}: {why}')
+    own = None if getattr(prob, 'parameters', None) is None else \
+        np.asarray(prob.parameters) if extra is None else prob.extendedParameters(extra)
     if field:
         # full-field data: (frequencies, field (F, n_sel)) in place of ref_fr; the loss is Problem.getFieldLossFunction
         if ref_field is None:
@@ -73,10 +85,10 @@ def solve_inverse(prob, arg0, loss_type: str, optimizer: str, compression=(False
     scaling = None
     if arg0.ndim == 1:
         if use_rel:
-            if getattr(prob, 'parameters', None) is None:
+            if own is None:
                 raise ValueError('Cannot use `arg0` as relative coefficients of correction as Problem object has '
                                  'no `parameters` attribute.')
-            x0 = np.asarray(prob.parameters) * (arg0 + 1)
+            x0 = own * (arg0 + 1)
             if use_scaling:
                 scaling, x0 = x0, arg0 + 1
         else:
@@ -96,6 +108,8 @@ def solve_inverse(prob, arg0, loss_type: str, optimizer: str, compression=(False
         raise NotImplementedError('the Jacobian sweep is not distributed: use `lm` with distributed=False')
     if field:
         loss = prob.getFieldLossFunction(ref_fr[0], ref_fr[1], loss_type, field_dofs, field_weights, scaling)
+    elif extra is not None:
+        loss = prob.getLossFunction(ref_fr[0], ref_fr[1], loss_type, scaling, extra=extra)
     else:
         loss = prob.getLossFunction(ref_fr[0], ref_fr[1], loss_type, scaling, distributed=distributed)
     scale_arr = np.ones_like(x0) if scaling is None else (np.tile(scaling, (2, 1)).T if x0.ndim == 2 else scaling)
@@ -110,7 +124,7 @@ def solve_inverse(prob, arg0, loss_type: str, optimizer: str, compression=(False
         opt_kwargs.pop('exact_hessian', None)
         if local is opt.optimize_lm:
             # least squares: the residual and its per-frequency Jacobian (one sweep) in place of the loss
-            loss = prob.getResidualFunction(ref_fr[0], ref_fr[1], loss_type, scaling)
+            loss = prob.getResidualFunction(ref_fr[0], ref_fr[1], loss_type, scaling, **({} if extra is None else {'extra': extra}))
     elif optimizer in ('de', 'shgo'):
         def np_loss(x):
             return float(loss(torch.as_tensor(np.asarray(x, dtype=np.float64))))
@@ -160,8 +174,8 @@ def solve_inverse(prob, arg0, loss_type: str, optimizer: str, compression=(False
         or torch.distributed.get_rank() == 0
     if report and rank0:
         rel1 = rel2 = 'Unknown'
-        if getattr(prob, 'parameters', None) is not None:
-            p0 = np.asarray(prob.parameters)
+        if own is not None:
+            p0 = own
             if arg0.ndim != 2:
                 rel1 = (np.asarray(x0) * scale_arr - p0) / p0
             rel2 = (np.asarray(result.x) - p0) / p0
